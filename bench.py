@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — training interactions/s (+ full-catalogue scores/s) of the HIP SingleBranchNet engine on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL. Either an external launcher provides RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*
 (``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``), or — WORLD_SIZE unset — this script starts
@@ -16,9 +16,15 @@ forward, sampled-softmax loss, backward, dense AdamW over every parameter. Featu
 state are resident in HBM before the timed region; only the index tensors of each batch cross PCIe.
 
 Prints ONE JSON line (rank 0). ``value`` = interactions (positive rows) per second over all ranks, weak scaling (per-GPU
-batch fixed). Extra objects: ``roofline`` (dominant training kernel, HIP-event timed live), ``scoring`` (fused fp16
+batch fixed); ``ms_per_step`` = milliseconds per timed step. A plain run does only what that figure needs: set up, W warm-up
+steps (+ SETTLE), the K timed steps, the ``--dump-outputs`` files, the line. ``--full`` adds every other measurement (the
+``--no-*`` switches trim it): ``roofline`` (dominant training kernel, HIP-event timed live), ``scoring`` (fused fp16
 score+mask+top-k over the full catalogue: scores/s and its own roofline), ``cpu_baseline`` (the CPU oracle restatement of
-the same step timed on this box's host cores, rank 0, N=1 only), ``b256`` (the same step at the reference's default batch).
+the same step timed on this box's host cores, rank 0, N=1 only), ``b256`` (the same step at the reference's default batch),
+``c1`` / ``c3`` / ``c5_shard`` (N=1) or ``c4_dp`` / ``c5`` and the replica checksum (N>1), and the per-kernel tables side file.
+
+``--dump-outputs DIR`` writes what the timed path computed in its last timed step as DIR/<name>.npy (``dump_outputs``); the
+inputs are fixed by seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -83,7 +89,9 @@ def run_steps(S, trainer, loader_iter, n, world):
     return out
 
 
-def bench_training(S, ds, net, device, batch, steps, warmup, rank, world, time_kernels, loss=None):
+def bench_training(S, ds, net, device, batch, steps, warmup, rank, world, time_kernels, loss=None, after_timed=None):
+    """-> (seconds of the `steps` timed steps, per-kernel timings). ``after_timed(last)`` is called with what the last timed step
+    returned, before any further step runs."""
     import torch.distributed as dist
     if loss is None:
         loss = S.RecSampledSoftmaxLoss(n_items=ds.n_items, aggregator='mean', train_neg_strategy='uniform_recbole',
@@ -126,6 +134,8 @@ def bench_training(S, ds, net, device, batch, steps, warmup, rank, world, time_k
     LAST_LOSS[batch] = float(last[0]) if last is not None else None      # sanity of the timed steps (read after the clock)
     if LAST_LOSS[batch] is not None and not (0.0 < LAST_LOSS[batch] < 1e3):
         raise RuntimeError(f'training loss after the timed region is {LAST_LOSS[batch]}: the timed steps did not train')
+    if after_timed is not None:
+        after_timed(last)
     timings = {}
     if time_kernels:
         # per-kernel HIP events cannot be recorded inside a hipGraph replay: the next `steps` batches of the same loader are
@@ -151,6 +161,19 @@ def bench_training(S, ds, net, device, batch, steps, warmup, rank, world, time_k
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     return dt, timings
+
+
+def dump_outputs(last, out_dir):
+    """``--dump-outputs DIR``: what the timed path hands its caller, for the last timed step: the loss tensors ``Trainer.train_step``
+    returns, as DIR/loss_total.npy, loss_rec.npy and loss_reg.npy (float64 scalars). The batches are the same in every run (seeded
+    streams), but the model state is not written: the float-atomic gradient scatter rounds in a different order in every run and AdamW
+    turns that into diverging trajectories on this synthetic data (loss near ln 11, gradients mostly noise). Two runs of one build
+    agree to ~1e-11 in the loss after one step and to ~1e-3 after a few hundred, while their parameters then differ at the scale of
+    the parameters themselves."""
+    total, rec, regs = last
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (('loss_total', total), ('loss_rec', rec), ('loss_reg', regs['reg_loss'])):
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().double().cpu().numpy())
 
 
 def gemm_bytes(mode, M, N, K):
@@ -1011,7 +1034,14 @@ def main():
     ap.add_argument('--small', action='store_true', help='1/10-size workload (debug only; never a reportable number)')
     ap.add_argument('--only', choices=['c3', 'c5'], default=None,
                     help='profiling passes (tools/profile_round.sh): run ONLY the c3 step (B = 4096) or the c5 shard scoring and print its object')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beside the headline figure (roofline, b256, scoring, CPU baselines, c1 / c3 / c5_shard '
+                         'on one GPU, c4_dp / c5 and the replica checksum on N > 1, per-kernel tables); the --no-* switches trim it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last timed step to DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # no launcher around us: become the launcher (nothing in this process has touched the GPU yet)
@@ -1075,7 +1105,9 @@ def main():
         cfg.update(n_users=10_000, n_items=5_000, nnz=500_000)
     ds, net = build(S, cfg, device)
 
-    dt, timings = bench_training(S, ds, net, device, args.batch_size, args.steps, args.warmup, rank, world, time_kernels=True)
+    dump = (lambda last: dump_outputs(last, args.dump_outputs)) if args.dump_outputs and rank == 0 else None
+    dt, timings = bench_training(S, ds, net, device, args.batch_size, args.steps, args.warmup, rank, world, time_kernels=args.full,
+                                 after_timed=dump)
     value = args.batch_size * world * args.steps / dt
     out = {
         'metric': 'training interactions/s', 'value': round(value, 1), 'unit': 'interactions/s', 'n_gpus': world,
@@ -1092,24 +1124,26 @@ def main():
                    'loss_after_timed_steps': LAST_LOSS.get(args.batch_size)},
     }
     if world > 1:
-        spread, chk = replica_checksum(net, device)
-        out['config']['replica_param_checksum_spread'] = spread
-        out['config']['param_checksum'] = chk
+        if args.full:
+            spread, chk = replica_checksum(net, device)
+            out['config']['replica_param_checksum_spread'] = spread
+            out['config']['param_checksum'] = chk
         out['config']['user_table_gradient_exchange'] = EXCHANGE.get(args.batch_size)
-    n_params = sum(p.numel() for p in net.parameters())
-    utab = net.user_embedding_module.embedding_layer.weight
-    roof = step_roofline(timings, args.steps, args.batch_size, n_params, utab.numel(), utab.shape[1]) if rank == 0 else None
-    if roof:
-        out['roofline'] = compact_roofline(roof)
+    if args.full and rank == 0:
+        n_params = sum(p.numel() for p in net.parameters())
+        utab = net.user_embedding_module.embedding_layer.weight
+        roof = step_roofline(timings, args.steps, args.batch_size, n_params, utab.numel(), utab.shape[1])
+        if roof:
+            out['roofline'] = compact_roofline(roof)
     b256 = sc = c5 = c3 = c1 = None
-    if not args.no_b256:
+    if args.full and not args.no_b256:
         dt256, _ = bench_training(S, ds, net, device, 256, max(args.steps, 30), args.warmup, rank, world, time_kernels=False)
         b256 = {'value': round(256 * world * max(args.steps, 30) / dt256, 1), 'unit': 'interactions/s',
                 'ms_per_step': round(dt256 / max(args.steps, 30) * 1e3, 3), 'batch_per_gpu': 256}
-    if not args.no_scoring:
+    if args.full and not args.no_scoring:
         sc = bench_scoring(S, ds, net, device, rank, world)
         sc['value'] = round(sc['value'], 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(S, ds, net, args.batch_size)
         TABLES['cpu_baseline_step_seconds'] = cb.pop('step_seconds')
         cb['speedup_vs_cpu'] = round(value / cb['value'], 1)
@@ -1117,16 +1151,16 @@ def main():
         if sc is not None:
             sc['cpu_baseline'] = cpu_scoring_sample(S, ds, net)
             sc['cpu_baseline']['speedup_vs_cpu'] = round(sc['value'] / sc['cpu_baseline']['value'], 1)
-    if rank == 0 and world == 1 and not args.no_configs and not args.small:
+    if args.full and rank == 0 and world == 1 and not args.no_configs and not args.small:
         del ds, net
         c5 = bench_c5_shard(S, device)
         c3 = bench_c3(S, device, args.steps)
         if 'roofline' in c3:
             c3['roofline'] = compact_roofline(c3['roofline'])
-    if rank == 0 and world == 1 and not args.no_c1 and not args.small:
+    if args.full and rank == 0 and world == 1 and not args.no_c1 and not args.small:
         c1 = bench_c1(S, device, args.steps)
     c4dp = c5d = None
-    if world > 1 and not args.no_configs:
+    if args.full and world > 1 and not args.no_configs:
         # the two BASELINE configs that name 8 GPUs, at their own sizes, next to the c2 curve (every rank takes part)
         del ds, net
         torch.cuda.empty_cache()
@@ -1143,7 +1177,8 @@ def main():
         for key, obj in (('c1', c1), ('c3', c3), ('c4_dp', c4dp), ('c5', c5d), ('b256', b256), ('c5_shard', c5), ('scoring', sc)):
             if obj is not None:
                 out[key] = obj
-        out['tables'] = write_tables()
+        if args.full:
+            out['tables'] = write_tables()
         line = json.dumps(out)
         if len(line) > 7600:                                  # the record keeps an 8 KB tail: shed prose before numbers
             for path in (('c1', 'workload'), ('c3', 'workload'), ('c1', 'trained_ndcg', 'what'), ('scoring', 'exclusion_mask'),

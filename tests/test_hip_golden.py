@@ -593,8 +593,8 @@ def test_two_rank_data_parallel_rehearsal_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'LOCAL_WORLD_SIZE', 'MASTER_PORT')}
     env['SBR_DIST_BACKEND'] = 'gloo'
-    # no external launcher: `bench.py --gpus 2` starts its two ranks itself (bench.launch_ranks)
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--small', '--steps', '20', '--warmup', '3', '--no-b256']
+    # no external launcher: `bench.py --gpus 2` starts its two ranks itself (bench.launch_ranks); --full: scoring, c4_dp and c5
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--small', '--steps', '20', '--warmup', '3', '--no-b256', '--full']
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     line = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')][-1]
@@ -614,6 +614,36 @@ def test_two_rank_data_parallel_rehearsal_on_one_gpu():
         assert 0.0 < c4[b]['loss_after_timed_steps'] < 2.45
     assert c5['sharding'] == 'items/2' and c5['lists_sorted_and_in_range'] and c5['value'] > 0 and c5['chunks'] == 3
     assert len(line) < 8000, f'the bench line is {len(line)} bytes: the record keeps an 8 KB tail'
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_their_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline line only (everything else is behind --full), times exactly --steps steps, and
+    --dump-outputs writes the losses the last timed step returned as float64 .npy files."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'LOCAL_WORLD_SIZE', 'MASTER_PORT')}
+    out_dir = tmp_path / 'outputs'
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--small', '--steps', '7', '--warmup', '2',
+           '--dump-outputs', str(out_dir)]
+    res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    out = json.loads([l for l in res.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert out['metric'] == 'training interactions/s' and out['unit'] == 'interactions/s' and out['higher_is_better'] is True
+    assert out['dtype'] == 'f32' and out['steps'] == 7 and out['warmup'] == 2
+    assert out['ms_per_step'] > 0 and out['value'] > 0
+    assert abs(out['value'] - 8192 * 1e3 / out['ms_per_step']) <= 1e-2 * out['value']      # ms_per_step: 3 decimals
+    for key in ('roofline', 'cpu_baseline', 'scoring', 'b256', 'c1', 'c3', 'c5_shard', 'tables'):
+        assert key not in out, f'{key} belongs to bench.py --full'
+    assert sorted(p.name for p in out_dir.iterdir()) == ['loss_rec.npy', 'loss_reg.npy', 'loss_total.npy']
+    files = {p.stem: np.load(p) for p in out_dir.iterdir()}
+    assert all(a.dtype == np.float64 and a.size == 1 and np.isfinite(a).all() for a in files.values())
+    total = float(files['loss_total'].reshape(-1)[0])
+    assert total == out['config']['loss_after_timed_steps']
+    assert abs(total - float(files['loss_rec'].reshape(-1)[0]) - float(files['loss_reg'].reshape(-1)[0])) <= 1e-6 * abs(total)
 
 
 @pytest.mark.gpu

@@ -61,7 +61,7 @@ if fetch or write:
     keys = sorted(set(fetch) | set(write), key=lambda k: -(2 * sum(fetch.get(k, [0])) + sum(write.get(k, [0]))))
     with open(os.path.join(out, f'{tag}_bench_hbm_traffic.csv'), 'w') as f:
         f.write('# rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, tools/profile_round.sh) -- python3 bench.py '
-                '--steps 50 --warmup 5 --no-cpu-baseline --no-b256 --no-c1\n')
+                '--full --steps 50 --warmup 5 --no-cpu-baseline --no-b256 --no-c1\n')
         import hashlib, glob
         h = hashlib.sha256()
         for p_ in sorted(glob.glob(os.path.join(root, 'sibrar---single-branch-recommender_amd', 'csrc', '*.h*'))):
@@ -98,7 +98,7 @@ if mf['GRBM_GUI_ACTIVE']:
     keys.sort(key=lambda k: -mean(mf['GRBM_GUI_ACTIVE'], k) * len(mf['GRBM_GUI_ACTIVE'][k]))
     with open(os.path.join(out, f'{tag}_bench_mfma_util.csv'), 'w') as f:
         f.write('# rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 '
-                'SQ_INSTS_VALU_MFMA_MOPS_F16 GRBM_GUI_ACTIVE -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-b256 --no-c1\n')
+                'SQ_INSTS_VALU_MFMA_MOPS_F16 GRBM_GUI_ACTIVE -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-b256 --no-c1\n')
         f.write('# per dispatch means. elapsed_cycles = GRBM_GUI_ACTIVE / 8 (the counter is summed over the 8 XCDs); '
                 'mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (elapsed_cycles * 1024 SIMDs); mfma_tflop = MOPS * 512 / 1e12; '
                 'clock_GHz needs the kernel trace duration of the same dispatch (profiles/<tag>_bench_kernel_by_shape.csv)\n')
