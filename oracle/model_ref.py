@@ -29,6 +29,15 @@ BN_EPS = 1e-5        # torch.nn.BatchNorm1d default, polylinear.py:61
 BN_MOMENTUM = 0.1    # torch.nn.BatchNorm1d default
 
 
+def float_dtype(sd) -> torch.dtype:
+    """The dtype the oracle computes in: that of the state dict's floating-point tensors (float32 as captured from the
+    reference; float64 for a widened copy, the high-precision yardstick of the GPU tests)."""
+    for v in sd.values():
+        if torch.is_tensor(v) and v.dtype.is_floating_point:
+            return v.dtype
+    return torch.float32
+
+
 def _act(name: Optional[str], x: torch.Tensor) -> torch.Tensor:
     """modules/polylinear.py:5-10 (ACTIVATION_FN_MAP)."""
     if name is None:
@@ -143,7 +152,8 @@ def feature_embedding(sd: Dict[str, torch.Tensor], prefix: str, table: RefTable,
     """FeatureEmbedding.forward (sgd_alg.py:1373-1389) for flat ``idx`` [n] -> [n, out]."""
     flat = idx.reshape(-1).cpu().numpy()
     if table.kind in ('dense', 'csr'):
-        x = torch.from_numpy(np.ascontiguousarray(table.fetch(flat))).float()        # sgd_alg.py:1380 x.float()
+        # sgd_alg.py:1380 x.float(); a float64 state dict widens the fp32-rounded rows exactly
+        x = torch.from_numpy(np.ascontiguousarray(table.fetch(flat))).float().to(float_dtype(sd))
         cfg = [table.dim] + list(hidden or []) + ([embedding_dim] if embedding_dim is not None else [])
         if len(cfg) > 1:
             # sgd_alg.py:1356: output_fn == activation_fn (activation also on the projector output)
@@ -236,7 +246,8 @@ class RefEntity:
         self.trailing_bn = bn and every == 0                                             # sgd_alg.py:1834-1837
         self.p = 1 if self.dropout is not None else 0     # index of PolyLinear inside nn.Sequential
         self.rng = np.random.default_rng(_cfg(cfg, 'sampling_seed', 42))                 # sgd_alg.py:1848
-        self.reg_loss = torch.zeros(1)
+        self.dtype = float_dtype(sd)
+        self.reg_loss = torch.zeros(1, dtype=self.dtype)
 
     # -- sampling (sgd_alg.py:1904-1932) ---------------------------------------------------
     def sample_modalities(self, shape, training: bool) -> np.ndarray:
@@ -261,7 +272,7 @@ class RefEntity:
         k = mods.shape[-1]
         flat_idx = torch.repeat_interleave(idx.reshape(-1), k)
         flat_mods = mods.reshape(-1)
-        out = torch.zeros(flat_idx.numel(), self.C)
+        out = torch.zeros(flat_idx.numel(), self.C, dtype=self.dtype)
         parts, rows_of = [], []
         for m in sorted(set(flat_mods.tolist())):                                        # np.unique order
             rows = np.flatnonzero(flat_mods == m)
@@ -298,7 +309,7 @@ class RefEntity:
         e = self.embed(idx, mods, training, dropout_mask)
         if training:
             if self.reg_type == 'no_regularization':
-                self.reg_loss = torch.zeros(1)
+                self.reg_loss = torch.zeros(1, dtype=self.dtype)
             else:
                 if e.shape[-2] != 2:
                     raise SystemError('second last dimension of embeddings should be of size 2')
@@ -309,7 +320,7 @@ class RefEntity:
 
     def get_and_reset_other_loss(self):
         loss = self.reg_loss * self.reg_weight                                           # sgd_alg.py:2001-2006
-        self.reg_loss = torch.zeros(1)
+        self.reg_loss = torch.zeros(1, dtype=self.dtype)
         return {'reg_loss': loss}
 
 
@@ -362,7 +373,7 @@ class RefSingleBranchNet:
 
     def get_and_reset_other_loss(self):
         """sgd_alg.py:2127-2140."""
-        losses = {'reg_loss': torch.zeros(1)}
+        losses = {'reg_loss': torch.zeros(1, dtype=float_dtype(self.sd))}
         for side in ('user', 'item'):
             s = self.sides[side]
             if isinstance(s, RefEntity):
@@ -444,7 +455,7 @@ def dropoutnet_forward(sd, cfg: dict, user_tables, item_tables, inter, inter_t, 
     2 = NoPreference (zero preference vector), one per user and one per ROW of ``i_idx``; None = all Normal (evaluation)."""
     def prefs(idx, matrix, strategy):
         flat = idx.reshape(-1).numpy()
-        dense = torch.from_numpy(np.asarray(matrix[flat].toarray())).float().reshape(*idx.shape, matrix.shape[1])
+        dense = torch.from_numpy(np.asarray(matrix[flat].toarray())).to(float_dtype(sd)).reshape(*idx.shape, matrix.shape[1])
         if strategy is not None:
             drop = torch.from_numpy(np.asarray(strategy) != 1)
             dense[drop] = 0.

@@ -366,7 +366,7 @@ def test_c3_step_at_full_shapes_against_the_cpu_oracle():
     """BASELINE configs[2] (Onion18 shape): 13,610 items with a 1024-d dense modality, an 853-tag bag and the CSR interactions
     modality (5,192 columns), C = 512, five hidden layers [512, 512, 512, 256, 256], D = 128, pairwise InfoNCE (tau 0.1),
     BPR, batch 256 x 11 -> 5,632 rows through the shared network. One fused step against the CPU oracle on the same parameters,
-    batch and modality draw: rec loss, reg loss and every parameter gradient."""
+    batch and modality draw: rec loss, reg loss, every parameter gradient and the BatchNorm running statistics after the step."""
     from oracle import losses_ref, model_ref
     ds = S().SyntheticDataset(5192, 13610, 326_000, item_dense={'audio': 1024}, item_tags={'genres': (853, 5)}, seed=0,
                               n_negative_samples=10)
@@ -379,6 +379,7 @@ def test_c3_step_at_full_shapes_against_the_cpu_oracle():
     np.random.seed(42)
     net = S().SingleBranchNet(S().SingleBranchNetConfig.from_dict(cfg), ds).to(DEV).train()
     sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
+    sd_before = {k: v.clone() for k, v in sd.items()}
     for k, v in sd.items():
         if v.dtype.is_floating_point and 'running' not in k:
             v.requires_grad_(True)
@@ -399,6 +400,7 @@ def test_c3_step_at_full_shapes_against_the_cpu_oracle():
     _lib.CALL_LOG = []
     total, rec, reg = fused.step(u, i, labels, draws)
     names, _lib.CALL_LOG = [n_ for n_, _ in _lib.CALL_LOG], None
+    after = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     # 5,632 rows: the 256 -> 128 output layer on the bf16-split projector kernel, the weight gradients on the bf16-split dW kernel; the
     # 512- and 256-wide forward / input-gradient products stay on the fp32 ring kernel at this batch (22 x 2 tiles of 256 x 256 do not
     # fill the chip: ops._wide_ok) and move to the wide bf16-split kernel from ~22k rows on
@@ -423,7 +425,28 @@ def test_c3_step_at_full_shapes_against_the_cpu_oracle():
     # (measured: 2.5e-4 on one bias element); losses stay within the north star's 1e-4
     for k_, g in grads.items():
         close(seen[0][k_].cpu(), g, what=f'grad {k_}', rtol=5e-4, atol=1e-6, scale=sc, norm_rtol=5e-4)
+    # the BatchNorm running statistics the step's forward pass updated, against the oracle's after its forward (the gradients'
+    # tolerances); a running mean that absorbs a bias in front of the BatchNorm drifts with that bias and is left out
+    _same_running_stats(after, sd, sd_before, rtol=5e-4, atol=1e-6, norm_rtol=5e-4)
     fused.close()
+
+
+def _same_running_stats(gpu, ref, before, rtol, **tol):
+    """BatchNorm running statistics after the GPU's forward passes against the oracle's: the counter exactly, every statistic
+    element-wise within (rtol, tol), and norm-wise within rtol their change since ``before`` — the momentum term, which a wrong
+    momentum or batch statistic moves by a relative amount that the element-wise bound on the statistic itself would dilute."""
+    shadowed = bn_shadowed_biases(ref.keys())
+    n = 0
+    for k_, v in ref.items():
+        if 'num_batches_tracked' in k_:
+            assert int(gpu[k_]) == int(v), f'{k_}: {int(gpu[k_])} vs {int(v)}'
+        elif 'running_' in k_ and k_ not in shadowed:
+            close(gpu[k_], v.detach(), what=k_, rtol=rtol, **tol)
+            d_gpu, d_ref = (gpu[k_] - before[k_]).double(), (v.detach() - before[k_]).double()
+            err = float((d_gpu - d_ref).norm())
+            assert err <= rtol * float(d_ref.norm()), f'change of {k_}: norm err {err:.3e}, norm {float(d_ref.norm()):.3e}'
+            n += 1
+    assert n >= 1
 
 
 def test_c2_step_at_the_bench_batch_against_the_cpu_oracle():
@@ -431,7 +454,8 @@ def test_c2_step_at_the_bench_batch_against_the_cpu_oracle():
     x 11 slots with its recorded modality draw, ``FusedTrainStep.step`` five times — three passes of plain launches (the arena is sized, grown,
     re-sighted), hipGraph capture + replay, replay — with the optimizer launch replaced by a recorder, against the CPU oracle (oracle/model_ref.py restating
     train/trainer.py:204-223 -> sgd_alg.py:2116-2125, rec_losses.py:88-113) on the same parameters, batch and draw: the
-    sampled-softmax loss (1e-4 relative) and EVERY gradient incl. both embedding tables (norm-wise 1e-4). The call log of the
+    sampled-softmax loss (1e-4 relative), EVERY gradient incl. both embedding tables (norm-wise 1e-4) and the BatchNorm running
+    statistics after the five passes (the oracle's after five forward passes). The call log of the
     plain-launch pass must show the launch mix the bench line is timed on: bf16-split projector, bf16-split K = N = 128 products
     (forward with the BatchNorm statistics epilogue, backward), bf16-split dW products, the fused scorer + loss + statistics kernel,
     the one-launch lookup."""
@@ -443,6 +467,7 @@ def test_c2_step_at_the_bench_batch_against_the_cpu_oracle():
     net.train()
     cfg = bench.model_config(bench.C2['emb_dim'])
     sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
+    sd_before = {k: v.clone() for k, v in sd.items()}
     for k, v in sd.items():
         if v.dtype.is_floating_point and 'running' not in k:
             v.requires_grad_(True)
@@ -472,6 +497,7 @@ def test_c2_step_at_the_bench_batch_against_the_cpu_oracle():
             log, _lib.CALL_LOG = _lib.CALL_LOG, None
         recs.append(rec.cpu())
     assert fused.n_replays == 2 and len(seen) == n_rep
+    after = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     # ---- the launch mix of the timed path
     names = [n_ for n_, _ in log]
     lib = _lib.lib()
@@ -496,6 +522,12 @@ def test_c2_step_at_the_bench_batch_against_the_cpu_oracle():
     rl = losses_ref.RefRecLoss('sampled_softmax', n_items=ds.n_items, aggregator='mean', train_neg_strategy='uniform_recbole',
                                neg_train=ds.n_negative_samples).compute_loss(logits, labels)
     rl.backward()
+    # the recorder left the parameters as they were: the GPU's running statistics took n_rep momentum updates with the same batch
+    # statistics, so the oracle's forward runs n_rep times too (training mode: the output does not read the running statistics)
+    with torch.no_grad():
+        for _ in range(n_rep - 1):
+            ref.forward(u, i, True, None, mods)
+    _same_running_stats(after, sd, sd_before, rtol=2e-4, atol=1e-7, norm_rtol=1e-4)
     grads = {k: v.grad for k, v in sd.items() if v.requires_grad and v.grad is not None}
     assert {'user_embedding_module.embedding_layer.weight'} <= set(grads) and len(grads) == len(seen[0])
     sc = gscale(grads.values())
