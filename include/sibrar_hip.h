@@ -422,14 +422,29 @@ int sbr_score_topk_f16(const void* U_f16, const void* I_f16, int D, long Bu, int
  * and read by the final-selection launch of the same call; contents need no initialisation) + their fill counts. */
 long sbr_score_topk_f16_workspace(long Bu, int I, int k);
 long sbr_score_topk_f16_events_bytes(long Bu, long excl_nnz);
-/* ABI 4: which of the two fused scorers sbr_score_topk_f16 runs. 0 (default): the two-pass scorer (csrc/score_topk_f16_2p.hip: a pure
- * MFMA + group-maxima pass, then the ~3 % of the scores at or above each user's bound are recomputed group by group) for catalogues of
- * >= 8,192 items, the one-pass kernel (csrc/score_topk_f16_n.hip) below; 1: always one-pass; 2: two-pass or an error. Both return the same
- * lists bit for bit (same MFMA chain per score); the switch exists for tests and A/B timing. Returns the previous setting; a value
- * outside 0..2 only queries. Process-wide. */
+/* ABI 4: which of the two fused scorers sbr_score_topk_f16 runs. 0 (default): the one-pass kernel (csrc/score_topk_f16_n.hip) for every
+ * shape (automatic: it stays there until the two-pass scorer is the faster one); 1: always one-pass; 2: the two-pass scorer
+ * (csrc/score_topk_f16_2p.hip: a pure MFMA + group-maxima pass, then the ~3 % of the scores at or above each user's bound are recomputed
+ * group by group) for catalogues of >= 8,192 items, or an error. Both return the same lists bit for bit (same MFMA chain per score); the
+ * switch exists for tests and A/B timing. Returns the previous setting; a value outside 0..2 only queries. Process-wide. */
 int sbr_score_topk_f16_route(int route);
 /* fp32 -> fp16 cast of an embedding matrix (row-major, contiguous) */
 int sbr_cast_f32_to_f16(const float* X, void* Y_f16, long n, void* stream);
+/* fused scorer with fp32-class products (eval/eval.py:216-222: einsum('be,ce->bc') in fp32, -inf on the exclusions, top-k): the
+ * contract of sbr_score_topk_f16 (output order, global indices, u_idx, (-inf, -1) padding, event-buffer protocol) on fp32 user rows
+ * U_f32 [Bu, D] and the three bf16 planes of the item matrix (sbr_split_f32_to_bf16x3), multiplied on the bf16 matrix pipe as the six
+ * leading partial products of the exact splits with fp32 accumulation (csrc/score_topk_f32s.hip). D in {64, 128}, k <= 32. The event
+ * buffer has sbr_score_topk_f16_events_bytes(Bu, excl_nnz) bytes, but the stream in it is laid out for this kernel's 32-item tiles:
+ * a buffer built by sbr_score_topk_f16 must not be passed with build_events = 0, nor the other way round. New (additive to ABI 4). */
+int sbr_score_topk_f32s(const float* U_f32, const void* I_bf16x3, int D, long Bu, int I, const long* u_idx,
+                        const long* excl_indptr, const int* excl_indices, long excl_nnz, int item_offset, int k, float* out_val,
+                        int* out_idx, void* workspace, long workspace_bytes, void* events, long events_bytes, int build_events,
+                        void* stream);
+/* bytes of `workspace` for sbr_score_topk_f32s (candidate buffers + fill counts of this route only; eval/eval.py:216-222) */
+long sbr_score_topk_f32s_workspace(long Bu, int I, int k);
+/* X (fp32, n elements, contiguous) -> three bf16 planes Y[0..n), Y[n..2n), Y[2n..3n) with X = Y0 + Y1 + Y2 exactly (each plane rounded to
+ * nearest even from the remainder): the item operand of sbr_score_topk_f32s (eval/eval.py:216-222) */
+int sbr_split_f32_to_bf16x3(const float* X, void* Y_bf16x3, long n, void* stream);
 
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference

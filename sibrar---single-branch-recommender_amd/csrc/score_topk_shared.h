@@ -240,21 +240,22 @@ static int s5_n_cu() {
 // when the units do not divide evenly over the CUs — one PARTIAL wave on each of the first n_part workgroups: the remainder units are
 // cut into P parts by item tile (see the kernel). 100k users = 3,125 units on 256 CUs: 12 full waves everywhere + 53 remainder units
 // in 4 parts each on 212 workgroups (3.25 consumer waves on the fullest SIMD instead of 4).
+// maxw: consumer wave slots per workgroup, the partial wave's included (S5_MAXW for the fp16 kernels; F3_MAXW for score_topk_f32s.hip).
 struct S5Plan { int W, n_wg, n_part, P; };
-static S5Plan s5_plan(long Bu) {
+static S5Plan s5_plan(long Bu, int maxw = S5_MAXW) {
   const int G = s5_n_cu();
   const long units = sbr_cdiv(Bu, 32);
   S5Plan p;
   const long Wf = units / G;
   const long R = units - Wf * G;
-  if (Wf >= 1 && Wf + 1 <= S5_MAXW && R > 0 && G / R >= 2) {
+  if (Wf >= 1 && Wf + 1 <= maxw && R > 0 && G / R >= 2) {
     p.W = (int)Wf; p.n_wg = G; p.P = (int)(G / R < 8 ? G / R : 8); p.n_part = (int)(R * p.P);
     return p;
   }
   // one round of whole units: the smallest W that keeps the number of rounds (workgroups per CU) at its minimum
-  const long rounds = sbr_cdiv(units, (long)G * S5_MAXW);
+  const long rounds = sbr_cdiv(units, (long)G * maxw);
   long w = sbr_cdiv(units, rounds * G);
-  p.W = (int)(w < 1 ? 1 : (w > S5_MAXW ? S5_MAXW : w));
+  p.W = (int)(w < 1 ? 1 : (w > maxw ? maxw : w));
   p.n_wg = (int)sbr_cdiv(units, p.W); p.n_part = 0; p.P = 1;
   return p;
 }

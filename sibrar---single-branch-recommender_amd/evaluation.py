@@ -5,7 +5,10 @@ The reference scores a user batch against all items (``einsum('be,ce->bc')``), s
 host-densified CSR mask, and hands the dense [Bu, I_s] logits plus dense label rows to the third-party ``rmet.calculate``.
 Here the exclusion CSR and the label CSR are resident on the device; per user batch the engine runs either
   * ``scorer='fp32'``      : fp32-MFMA GEMM -> CSR mask kernel -> exact radix-select top-k, or
-  * ``scorer='fp16_fused'``: the fused fp16-MFMA score+mask+top-k kernel (scores never written),
+  * ``scorer='fp16_fused'``: the fused fp16-MFMA score+mask+top-k kernel (scores never written), or
+  * ``scorer='fp32_fused'``: the same fusion with fp32-class products (fp32 user rows and the item matrix split once into three
+    exact bf16 planes, six bf16-MFMA partial products per score, fp32 accumulation): the fp32 route's ranking without its score
+    matrix; k <= 32 and D in {64, 128}, anything else falls back to ``'fp32'``,
 followed by the ranking-metric kernel (NDCG / recall / precision as defined in eval/metrics.py:4-105; ``rmet`` itself is
 absent offline, so w.r.t. ``rmet`` the metric arithmetic is parity-unpinned). ``eval_batch`` keeps the reference's
 dense-logits entry point for callers that already hold a score matrix.
@@ -300,25 +303,33 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
             except Exception:
                 pass
         bs = int(getattr(eval_loader, 'batch_size', 256) or 256)
-        if scorer not in ('fp32', 'fp16_fused'):
+        if scorer not in ('fp32', 'fp16_fused', 'fp32_fused'):
             raise ValueError(f'unknown scorer {scorer!r}')
+        if scorer == 'fp32_fused' and (not plain or not ops.score_topk_f32s_supported(int(i_repr.shape[1]), kmax)):
+            # the fp32-class fused kernel keeps at most 32 candidates per user and is built for D in {64, 128} (the user planes of
+            # D = 256 do not fit its registers): everything else takes the exact fp32 GEMM + radix-select path
+            logging.info(f'fp32_fused scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
+                         f'the fused kernel, using the fp32 path')
+            scorer = 'fp32'
         if scorer == 'fp16_fused' and (not plain or kmax > 32 or i_repr.shape[1] not in (64, 128, 256)):
             # the fused kernel keeps at most 32 candidates per user on chip and is built for D in {64, 128, 256}: larger
             # cut-offs (the reference's default evaluator asks for top-100) take the exact fp32 GEMM + radix-select path
             logging.info(f'fp16_fused scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
                          f'the fused kernel, using the fp32 path')
             scorer = 'fp32'
-        i16 = ops.cast_f16(i_repr) if scorer == 'fp16_fused' else None
+        fused = scorer in ('fp16_fused', 'fp32_fused')
+        # item operand of the fused kernel, made once per call: fp16 [I, D] or three bf16 planes [3, I, D]
+        i_op = ops.cast_f16(i_repr) if scorer == 'fp16_fused' else (ops.split_bf16x3(i_repr) if scorer == 'fp32_fused' else None)
         if user_chunk is not None:
             bs = int(user_chunk)
-        elif scorer == 'fp16_fused':
+        elif fused:
             bs = max(bs, 262144)                                    # one launch for up to 256k users (fp16 rows: 64 MB at D = 128)
         else:
             bs = max(bs, min(16384, max(1, (1 << 31) // max(hi - lo, 1))))      # <= 8 GiB of fp32 scores per chunk
         for s in range(0, len(users), bs):
             u_idxs = torch.from_numpy(users[s:s + bs].astype(np.int64)).to(device)
             u_repr = alg.get_user_representations(u_idxs)
-            if scorer == 'fp16_fused' and torch.is_tensor(u_repr):
+            if fused and torch.is_tensor(u_repr):
                 # the split's exclusion mask in the scorer's layout, built once per (user chunk, item shard, D) and kept with the
                 # split like the resident CSR it is made from
                 cache = getattr(dataset, '_scorer_excl', None)
@@ -331,9 +342,14 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
                 # (the key carries a fingerprint of the chunk's user ids: a split whose users_in_split changed between two evaluations
                 # must not meet the mask of the old users)
                 chunk = users[s:s + bs].astype(np.int64)
-                holder = cache.setdefault((s, int(chunk.size), int(chunk[0]), int(chunk[-1]), int(chunk.sum()), lo, hi, int(i16.shape[1])),
-                                          ops.ScorerExclusions())
-                val, idx = ops.score_topk_f16(ops.cast_f16(u_repr), i16, kmax, u_idxs, excl[0], excl[1], item_offset=lo, exclusions=holder)
+                # (and the route: the two fused kernels lay the stream out for different tile widths)
+                holder = cache.setdefault((scorer, s, int(chunk.size), int(chunk[0]), int(chunk[-1]), int(chunk.sum()), lo, hi,
+                                           int(i_op.shape[-1])), ops.ScorerExclusions())
+                if scorer == 'fp16_fused':
+                    val, idx = ops.score_topk_f16(ops.cast_f16(u_repr), i_op, kmax, u_idxs, excl[0], excl[1], item_offset=lo,
+                                                  exclusions=holder)
+                else:
+                    val, idx = ops.score_topk_f32s(u_repr, i_op, kmax, u_idxs, excl[0], excl[1], item_offset=lo, exclusions=holder)
             else:
                 out = alg.combine_user_item_representations(u_repr, i_repr)
                 ops.mask_scores_(out, u_idxs, excl[0], excl[1], item_offset=lo if sharded else None)

@@ -783,10 +783,23 @@ class ScorerExclusions:
         self.buf, self.key = None, None
 
 
+def _scorer_events(exclusions, key, Bu, nnz, device):
+    """-> (event buffer or None, build flag) for one fused-scorer call. ``key`` names the route and its geometry first: the two routes
+    lay the stream out for different tile widths, so a holder built for one is rebuilt, never reused, by the other."""
+    if nnz <= 0:
+        return None, 1
+    holder = exclusions if exclusions is not None else ScorerExclusions()
+    if holder.buf is not None and holder.key == key:
+        return holder.buf, 0                   # built by an earlier call for the same users / mask / item range (the caller's promise)
+    holder.buf = torch.empty(int(lib().sbr_score_topk_f16_events_bytes(Bu, nnz)) + 16, device=device, dtype=torch.uint8)
+    holder.key = key
+    return holder.buf, 1
+
+
 def score_topk_route(route: int = -1) -> int:
-    """Which fused scorer ``score_topk_f16`` runs (process-wide; returns the previous setting): 0 automatic — the two-pass scorer
-    (csrc/score_topk_f16_2p.hip) for catalogues of >= 8,192 items, the one-pass kernel below —, 1 always one-pass, 2 two-pass or an
-    error; -1 only queries. Both return the same lists bit for bit; the switch exists for tests and A/B timing."""
+    """Which fused scorer ``score_topk_f16`` runs (process-wide; returns the previous setting): 0 automatic — the one-pass kernel for
+    every shape until the two-pass scorer (csrc/score_topk_f16_2p.hip) is the faster one —, 1 always one-pass, 2 two-pass (catalogues
+    of >= 8,192 items) or an error; -1 only queries. Both return the same lists bit for bit; the switch exists for tests and A/B timing."""
     return int(lib().sbr_score_topk_f16_route(int(route)))
 
 
@@ -799,18 +812,44 @@ def score_topk_f16(u16: torch.Tensor, i16: torch.Tensor, k: int, u_idx=None, exc
     idx = torch.empty(Bu, k, device=u16.device, dtype=torch.int32)
     nnz = 0 if excl_indices is None else int(excl_indices.numel())
     ws = torch.empty(max(int(lib().sbr_score_topk_f16_workspace(Bu, I, k)), 8), device=u16.device, dtype=torch.uint8)
-    ev, build = None, 1
-    if nnz > 0:
-        key = (Bu, I, D, int(item_offset), nnz)
-        holder = exclusions if exclusions is not None else ScorerExclusions()
-        if holder.buf is not None and holder.key == key:
-            build = 0                          # built by an earlier call for the same users / mask / item range (the caller's promise)
-        else:
-            holder.buf = torch.empty(int(lib().sbr_score_topk_f16_events_bytes(Bu, nnz)) + 16, device=u16.device, dtype=torch.uint8)
-            holder.key = key
-        ev = holder.buf
+    ev, build = _scorer_events(exclusions, ('f16', Bu, I, D, int(item_offset), nnz), Bu, nnz, u16.device)
     _timed(('score_topk_f16', Bu, I, D, k),
            lambda: call('sbr_score_topk_f16', ptr(u16), ptr(i16), D, Bu, I, ptr(u_idx), ptr(excl_indptr), ptr(excl_indices), nnz,
+                        item_offset, k, ptr(val), ptr(idx), ptr(ws), ws.numel(), ptr(ev), 0 if ev is None else ev.numel(), build, stream()))
+    return val, idx
+
+
+def split_bf16x3(x: torch.Tensor) -> torch.Tensor:
+    """fp32 [..., D] -> bfloat16 [3, ..., D]: three planes whose sum is x exactly (the item operand of ``score_topk_f32s``)."""
+    _need_cuda(x)
+    x = _f32c(x)
+    y = torch.empty((3,) + tuple(x.shape), device=x.device, dtype=torch.bfloat16)
+    call('sbr_split_f32_to_bf16x3', ptr(x), ptr(y), x.numel(), stream())
+    return y
+
+
+def score_topk_f32s_supported(D: int, k: int) -> bool:
+    return D in (64, 128) and 1 <= k <= 32
+
+
+def score_topk_f32s(u32: torch.Tensor, i_planes: torch.Tensor, k: int, u_idx=None, excl_indptr=None, excl_indices=None,
+                    item_offset: int = 0, exclusions: 'ScorerExclusions' = None):
+    """The fused scorer with fp32-class products (eval/eval.py:216-222): fp32 user rows ``u32`` [Bu, D] against the item planes
+    ``i_planes`` = ``split_bf16x3(items)`` [3, I, D]; the output contract of ``score_topk_f16``. D in {64, 128}, k <= 32."""
+    _need_cuda(u32, i_planes)
+    u32 = _f32c(u32)
+    Bu, D = u32.shape
+    if i_planes.dtype != torch.bfloat16 or i_planes.dim() != 3 or i_planes.shape[0] != 3 or i_planes.shape[2] != D:
+        raise ValueError(f'score_topk_f32s: item planes must be bfloat16 [3, I, {D}] (split_bf16x3), got {i_planes.dtype} {tuple(i_planes.shape)}')
+    i_planes = i_planes.contiguous()
+    I = i_planes.shape[1]
+    val = torch.empty(Bu, k, device=u32.device, dtype=torch.float32)
+    idx = torch.empty(Bu, k, device=u32.device, dtype=torch.int32)
+    nnz = 0 if excl_indices is None else int(excl_indices.numel())
+    ws = torch.empty(max(int(lib().sbr_score_topk_f32s_workspace(Bu, I, k)), 8), device=u32.device, dtype=torch.uint8)
+    ev, build = _scorer_events(exclusions, ('f32s', Bu, I, D, int(item_offset), nnz), Bu, nnz, u32.device)
+    _timed(('score_topk_f32s', Bu, I, D, k),
+           lambda: call('sbr_score_topk_f32s', ptr(u32), ptr(i_planes), D, Bu, I, ptr(u_idx), ptr(excl_indptr), ptr(excl_indices), nnz,
                         item_offset, k, ptr(val), ptr(idx), ptr(ws), ws.numel(), ptr(ev), 0 if ev is None else ev.numel(), build, stream()))
     return val, idx
 

@@ -50,7 +50,7 @@ class Trainer:
         self.max_batches = _get(learn, 'max_batches_per_epoch')
         self.model_path = _get(conf, 'results_path')
         self.batch_verbose = _get(_get(conf, 'run_settings'), 'batch_verbose', False)
-        self.scorer = _get(conf, 'scorer', 'fp32')
+        self.scorer = _get(conf, 'scorer', 'fp32')          # 'fp32' | 'fp16_fused' | 'fp32_fused' (evaluation.evaluate_recommender_algorithm)
         self.best_value = self.best_metrics = self.best_epoch = None
         # the fused launch choreography (engine.FusedTrainStep) replaces autograd when the model is a SingleBranchNet with
         # an entity item side; `conf.fused_step = False` keeps the autograd path (same kernels, same results)
