@@ -418,8 +418,10 @@ int sbr_score_topk_f16(const void* U_f16, const void* I_f16, int D, long Bu, int
                        const long* excl_indptr, const int* excl_indices, long excl_nnz, int item_offset, int k, float* out_val,
                        int* out_idx, void* workspace, long workspace_bytes, void* events, long events_bytes, int build_events,
                        void* stream);
-/* bytes of `workspace` for the call above: per-user candidate buffers (4 KB per user: scratch written by the wave that owns the user
- * and read by the final-selection launch of the same call; contents need no initialisation) + their fill counts. */
+/* bytes of `workspace` for the call above on the route selected now (sbr_score_topk_f16_route): per-user candidate buffers (4 KB per
+ * user: scratch written by the wave that owns the user and read by the final-selection launch of the same call; contents need no
+ * initialisation) + their fill counts; under route 2 the larger of that and the two-pass scorer's buffers. Query again after switching
+ * the route: a call with a workspace too small for its route fails with an error. */
 long sbr_score_topk_f16_workspace(long Bu, int I, int k);
 long sbr_score_topk_f16_events_bytes(long Bu, long excl_nnz);
 /* ABI 4: which of the two fused scorers sbr_score_topk_f16 runs. 0 (default): the one-pass kernel (csrc/score_topk_f16_n.hip) for every

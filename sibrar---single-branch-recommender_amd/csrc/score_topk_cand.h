@@ -83,14 +83,7 @@ __device__ __forceinline__ void s5_append(unsigned long long* block, int pos, u3
 // (~item = il - C, score bits) at their byte cursor and advance it. The vector ALU writes EXEC itself (v_cmpx), so the
 // sequence has no vector -> scalar hand-over and no branch; all lanes are active on entry and on exit. rs: buffer descriptor of
 // the wave's candidate block (s5_block_rsrc).
-#ifndef S5_NOSTORE
-#define S5_NOSTORE 0                      // lab (timing only, wrong results): the append stores nothing
-#endif
-#if S5_NOSTORE
-#define S5_STORE_ASM
-#else
 #define S5_STORE_ASM "buffer_store_dword %[tmp], %[pos], %[rs], 0 offen\n\t" "buffer_store_dword %[a], %[pos], %[rs], 0 offen offset:4\n\t"
-#endif
 // CML (D = 256: the user fragments alone take 64 registers): the class maxima live in LDS ([register][lane] floats per wave, the lane's
 // slot of class r at cm_addr + 256 r) and the append updates them with a no-return ds_max_f32 under the same EXEC mask.
 template <unsigned int BIT, int C, bool EX, bool CML, int R>

@@ -31,16 +31,13 @@
 // among the candidates; at least k such items exist; so the k best of the candidates are the k best of the catalogue. Users whose
 // candidate list overflows (massive ties: every group ties at the bound) or who have fewer than k scoreable items are HARD: their wave
 // of the final kernel streams the whole catalogue itself with the same MFMA chain (slow, exact).
-#include "score_topk_shared.h"
+#include "score_topk_stream.h"
 
 #define S2_SUPER 512                     // items per supertile
 #define S2_CAND_CAP 128                  // candidate entries per user (typical: ~45)
 #define S2_MIN_ITEMS 8192                // below: the one-pass kernel (all 32 threshold classes need groups)
 #define S2_STAGE 256                     // candidates a wave of the final kernel can stage (the hard path compacts beyond)
 #define S2_CHUNK 512                     // pairs of a work item staged in LDS at a time
-#ifndef S2_ABL
-#define S2_ABL 0                         // lab builds only (timing, wrong results): 1 = no atomics in pass 2's flush, 2 = no flush, 3 = no user-row gather, 4 = no epilogue, 5 = no epilogue and no MFMA, 6 = set-up only
-#endif
 #define S2_ROWCAP 256                    // exclusion-row entries a wave keeps in LDS (longer rows: binary search in memory)
 
 typedef float f32x4q __attribute__((ext_vector_type(4)));
@@ -69,15 +66,8 @@ __global__ __launch_bounds__(1024) void score_max_f16_kernel(const _Float16* __r
   constexpr int D = KS * 16;
   constexpr int ST_TILE = 32 * NJ;
   constexpr int X = S2_SUPER / ST_TILE;                    // tiles per supertile
-  constexpr int PF = NJ == 1 ? S5_PF1 : S5_PF2;
-  constexpr int ROWB = D * 2;
-  constexpr int TILEB = ST_TILE * ROWB;
-  constexpr int CPR = D / 8;
-  constexpr int SWZ = (CPR >= 16) ? 15 : (CPR - 1);
-  constexpr int PER_T = (ST_TILE * CPR) / 64;
-  constexpr int LFL0 = (NS - 2) / S5_NL >= 1 ? (NS - 2) / S5_NL : 1;
-  constexpr int LFL = LFL0 * PER_T <= 63 ? LFL0 : 63 / PER_T;
-  static_assert(LFL >= 1 && LFL * PER_T <= 63, "vmcnt field");
+  typedef StF16<KS, NJ> Pol;
+  constexpr int TILEB = ST_TILE * D * 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   lds_int* full_lds = (lds_int*)(smem + NS * TILEB);
   lds_int* free_lds = full_lds + NS;
@@ -87,14 +77,9 @@ __global__ __launch_bounds__(1024) void score_max_f16_kernel(const _Float16* __r
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int l31 = lane & 31, half = lane >> 5;
-  // units as in the one-pass kernel: W full consumer waves per workgroup; remainder units are cut into P parts — here by supertile
-  // PAIR (supertiles 2q, 2q + 1 belong to part q % P), so that every 16-byte row of M is produced whole by one wave
-  const int Wb = W + ((int)blockIdx.x < n_part ? 1 : 0);
-  const bool partial = wave == W && (int)blockIdx.x < n_part;
-  const int part = partial ? (int)blockIdx.x % P : 0, n_parts = partial ? P : 1;
-  const long n_full_units = (long)gridDim.x * W;
-  const long unit = partial ? n_full_units + (int)blockIdx.x / P : (long)blockIdx.x * W + wave;
-  const long n_units = (Bu + 31) >> 5;
+  // units as in the one-pass kernel (StUnit); remainder units are cut into P parts — here by supertile PAIR (supertiles 2q, 2q + 1 belong
+  // to part q % P), so that every 16-byte row of M is produced whole by one wave
+  const StUnit un(Bu, W, n_part, P, wave);
   const int n_tiles = (I + ST_TILE - 1) / ST_TILE;
   const int n_st = (n_tiles + X - 1) / X;
   const int n_st2 = (n_st + 1) >> 1;                       // 16-byte rows of M per lane: two supertiles each
@@ -103,153 +88,50 @@ __global__ __launch_bounds__(1024) void score_max_f16_kernel(const _Float16* __r
   __syncthreads();
 
   const int cslots = W + (n_part > 0 ? 1 : 0);
-  if (wave == W && n_part > 0 && !partial) return;
+  if (wave == W && n_part > 0 && !un.partial) return;
   if (wave >= cslots) {
-    // ---------------------------------------------- loader waves (as in the one-pass kernel) ---------------------------------------
-    const int lw = wave - cslots;
-    int n_mine = 0, v_last = -1;
-    for (int v = lw; v < n_tiles; v += S5_NL) {
-      const int slot = v % NS;
-      if (v >= NS) {
-        const int need = Wb * (v / NS);
-        while (st_peek(free_lds + slot) < need) __builtin_amdgcn_s_sleep(1);
-      }
-      const int j0 = v * ST_TILE;
-      unsigned char* dst = smem + slot * TILEB;
-#pragma unroll
-      for (int q = 0; q < PER_T; ++q) {
-        const int Pq = q * 64 + lane;
-        const int i = Pq / CPR, cp = Pq % CPR;
-        int gi = j0 + i;
-        gi = gi < I ? gi : I - 1;
-        const _Float16* src = It + (long)gi * D + ((cp ^ (i & SWZ)) << 3);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(dst + q * 1024), 16, 0, 0);
-      }
-      v_last = v;
-      if (++n_mine > LFL) {
-        st_wait_vmcnt<LFL * PER_T>();
-        st_wave_fence();
-        const int vp = v - LFL * S5_NL;
-        *(volatile lds_int*)(full_lds + vp % NS) = vp + 1;
-      }
-    }
-    st_wait_vmcnt<0>();
-    st_wave_fence();
-    if (v_last >= 0) {
-      int vp = v_last - (LFL - 1) * S5_NL;
-      if (vp < lw) vp = lw;
-      for (; vp <= v_last; vp += S5_NL) *(volatile lds_int*)(full_lds + vp % NS) = vp + 1;
-    }
+    st_loader<1, ST_TILE, D, NS, S5_NL>(smem, full_lds, free_lds, It, I, 0, n_tiles, un.Wb, wave - cslots, lane);
     return;
   }
 
   // ------------------------------------------------ consumer waves ------------------------------------------------------------------
-  f16x8 ufrag[KS];
+  Pol pol;
   {
-    const long r = unit * 32 + l31;
-    const long ur = r < Bu ? r : Bu - 1;
-    const f16x8* src = reinterpret_cast<const f16x8*>(U + ur * D);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) ufrag[s] = src[2 * s + half];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) s5_pin8(ufrag[s]);
+    const long r = un.unit * 32 + l31;
+    pol.load_users(U, r < Bu ? r : Bu - 1, half);
   }
   // exclusion events (same stream as the one-pass kernel reads): tile << 11 | lane << 5 | accumulator bit (nj * 16 + register)
-  const bool has_excl = events != nullptr && unit < n_units;
-  typedef const __attribute__((address_space(4))) unsigned int* ev_ptr;
-  typedef unsigned int ev_quad __attribute__((ext_vector_type(4)));
-  typedef const __attribute__((address_space(4))) ev_quad* ev_quad_ptr;
-  ev_ptr evp = nullptr;
-  unsigned int w0 = S5_EV_NONE, w1 = S5_EV_NONE, w2 = S5_EV_NONE, w3 = S5_EV_NONE, n0 = S5_EV_NONE, n1 = S5_EV_NONE, n2 = S5_EV_NONE, n3 = S5_EV_NONE;
-  int ev_rem = 4, ev_q = 8;
-  if (has_excl) {
-    evp = (ev_ptr)events + ((const __attribute__((address_space(4))) int*)group_base)[unit];
-    const ev_quad qa = *(ev_quad_ptr)(evp), qb = *(ev_quad_ptr)(evp + 4);
-    w0 = qa.x; w1 = qa.y; w2 = qa.z; w3 = qa.w; n0 = qb.x; n1 = qb.y; n2 = qb.z; n3 = qb.w;
-  }
-#define S2_EV_NEXT()                                                                                                     \
-        w0 = w1; w1 = w2; w2 = w3;                                                                                       \
-        if (--ev_rem == 0) {                                                                                             \
-          w0 = n0; w1 = n1; w2 = n2; w3 = n3;                                                                            \
-          const ev_quad qn = *(ev_quad_ptr)(evp + ev_q);                                                                 \
-          n0 = qn.x; n1 = qn.y; n2 = qn.z; n3 = qn.w;                                                                    \
-          ev_rem = 4; ev_q += 4;                                                                                         \
-        }
-  int peek = 0;
-  int slot_next = 0;
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  StEvents ev(events, group_base, un.unit, events != nullptr && un.unit < un.n_units);
+  StRing<NS> ring{full_lds, free_lds, 0, 0};
 
   float cm[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) cm[c] = -INFINITY;
 #pragma unroll
   for (int r = 0; r < 16; ++r) *(__attribute__((address_space(3))) float*)(size_t)(tc_addr + r * 256) = -INFINITY;
-  uint4* mrow = M + (unit * n_st2) * 64 + lane;            // this lane's slot of supertile pair 0 (a unit's rows are contiguous)
+  uint4* mrow = M + (un.unit * n_st2) * 64 + lane;         // this lane's slot of supertile pair 0 (a unit's rows are contiguous)
   unsigned int pk0 = 0xFF80FF80u, pk1 = 0xFF80FF80u;       // the even supertile's packed maxima, kept until the odd one is done (-inf)
 
   int st = 0, tin = 0;                                      // supertile of the tile, tile inside the supertile
   int st_part = 0;                                          // st % n_parts
   for (int tl = 0; tl < n_tiles; ++tl) {
-    const int slot = slot_next;
-    slot_next = slot + 1 == NS ? 0 : slot + 1;
-    const bool mine = st_part == part;                      // wave-uniform (full waves: always)
+    const bool mine = st_part == un.part;                   // wave-uniform (full waves: always)
     if (!mine) {
       // another part's tile: wait for it, release it, pass its events by (the ring's bookkeeping counts every consumer wave)
-      while (st_peek(full_lds + slot) != tl + 1) __builtin_amdgcn_s_sleep(1);
-      st_wave_fence();
-      s5_lds_add_lane0(free_lds + slot, 1);
-      peek = 0;
-      if (has_excl) {
-        const unsigned int tkey = (unsigned int)tl;
-        while ((w0 >> 11) == tkey) { S2_EV_NEXT() }
-      }
+      ring.skip(tl);
+      ev.for_tile((unsigned int)tl, [](unsigned int) {});
     } else {
-      if (__builtin_amdgcn_readfirstlane(peek) != tl + 1) {
-        while (st_peek(full_lds + slot) != tl + 1) __builtin_amdgcn_s_sleep(1);
-      }
-      st_wave_fence();
       f32x16 acc[NJ];
-      f16x8 bf[PF + 1][NJ];
-      const unsigned char* rowp = smem + slot * TILEB + l31 * ROWB;
-      unsigned int lxh = (unsigned int)(((l31 & SWZ) << 4) ^ (half << 4));
-      asm volatile("" : "+v"(lxh));
-#pragma unroll
-      for (int s = 0; s < PF && s < KS; ++s) {
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj) bf[s][nj] = *reinterpret_cast<const f16x8*>(rowp + nj * 32 * ROWB + (((unsigned int)s << 5) ^ lxh));
-      }
-      if constexpr (S5_PRIO != 0) __builtin_amdgcn_s_setprio(S5_PRIO);
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        if (s + PF < KS) {
-#pragma unroll
-          for (int nj = 0; nj < NJ; ++nj)
-            bf[(s + PF) % (PF + 1)][nj] = *reinterpret_cast<const f16x8*>(rowp + nj * 32 * ROWB + (((unsigned int)(s + PF) << 5) ^ lxh));
-        }
-        if (s == KS / 2) peek = *(volatile lds_int*)(full_lds + slot_next);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj)
-          acc[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[s % (PF + 1)][nj], ufrag[s], s == 0 ? zero16 : acc[nj], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if constexpr (S5_PRIO != 0) __builtin_amdgcn_s_setprio(0);
-      s5_lds_done(acc[0], acc[NJ - 1]);
-      s5_lds_add_lane0(free_lds + slot, 1);
+      st_tile_mma<Pol, NS, Pol::PF>(ring, smem, pol, tl, l31, half, acc);
       // exclusion events of this tile: one bit per excluded score in the lane that holds it (ex), and — scalar — which accumulator
       // registers are named by any event of the tile (sbits). The accumulators themselves are never written: a register-indirect write
       // (s_set_gpr_idx) made hipcc copy a whole 16-register tuple per tile and per event, a scalar switch over single-register
       // v_cndmasks merged every case through copies.
       unsigned int ex = 0u, sbits = 0u;
-      if (has_excl) {
-        const unsigned int tkey = (unsigned int)tl;
-        while ((w0 >> 11) == tkey) {
-          ex |= lane == (int)((w0 >> 5) & 63u) ? 1u << (w0 & 31u) : 0u;
-          sbits |= 1u << (w0 & 31u);
-          S2_EV_NEXT()
-        }
-      }
+      ev.for_tile((unsigned int)tl, [&](unsigned int e) {
+        ex |= lane == (int)((e >> 5) & 63u) ? 1u << (e & 31u) : 0u;
+        sbits |= 1u << (e & 31u);
+      });
       const int j0 = tl * ST_TILE;
       if (j0 + ST_TILE > I) {                               // catalogue end inside the tile: padded columns do not count
         const int lim = I - j0 - 4 * half;
@@ -303,22 +185,21 @@ __global__ __launch_bounds__(1024) void score_max_f16_kernel(const _Float16* __r
         for (int c = 0; c < 4; ++c) cm[c] = -INFINITY;
       }
       tin = 0;
-      if (st & 1) st_part = st_part + 1 == n_parts ? 0 : st_part + 1;
+      if (st & 1) st_part = st_part + 1 == un.n_parts ? 0 : st_part + 1;
       ++st;
     } else {
       ++tin;
     }
   }
-#undef S2_EV_NEXT
   // L = the k-th largest of the user's 32 threshold-class maxima. A part wave has seen only its own supertiles: the selection kernel
   // recomputes the bound of remainder units from M.
-  if (!partial) {
+  if (!un.partial) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     float tc[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) tc[r] = *(volatile __attribute__((address_space(3))) float*)(size_t)(tc_addr + r * 256);
     const float L = s5_kth_of_32(tc, k);
-    const long user = unit * 32 + l31;
+    const long user = un.unit * 32 + l31;
     if (half == 0 && user < Bu) Lbuf[user] = L;
   }
 }
@@ -493,9 +374,8 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
   auto flush = [&]() {
     st_wave_fence();
     for (int e = lane; e < wn; e += 64) {
-      if (S2_ABL == 2) break;
       const int user = l_user[e];
-      const int at = S2_ABL == 1 ? (e & 63) : atomicAdd(cnt + user, 1);
+      const int at = atomicAdd(cnt + user, 1);
       if (at < S2_CAND_CAP) cand[(long)user * S2_CAND_CAP + at] = l_raw[e];
     }
     st_wave_fence();
@@ -516,7 +396,6 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
       }
     }
     __syncthreads();
-    if (S2_ABL == 6) continue;
     // the wave's MFMA blocks: 32 pairs each; the rows and the bound of the NEXT block are requested before the epilogue of the current one
     f16x8 ufrag[KS];
     int mb = wave;
@@ -524,20 +403,11 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
     float L = INFINITY;
     if (mb * 32 < cn) {
       const int q = mb * 32 + l31;
-      user = S2_ABL == 3 ? l31 : ch_user[q < cn ? q : 0];
+      user = ch_user[q < cn ? q : 0];
       L = q < cn ? Lbuf[user] : INFINITY;
       const f16x8* src = reinterpret_cast<const f16x8*>(U + (long)user * D);
-      if (S2_ABL == 7) {
-        // lab (timing only): the same rows with whole-row wave instructions — instruction s reads rows 4 s .. 4 s + 3 of the block, 16 lanes per row
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          const int qq = mb * 32 + (4 * s + (lane >> 4)) % 32;
-          ufrag[s] = reinterpret_cast<const f16x8*>(U + (long)ch_user[qq < cn ? qq : 0] * D)[lane & 15];
-        }
-      } else {
 #pragma unroll
       for (int s = 0; s < KS; ++s) ufrag[s] = src[2 * s + half];
-      }
     }
     for (; mb * 32 < cn; mb += 4) {
       const int cur_user = user;
@@ -548,25 +418,16 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
           const f16x8 af = *reinterpret_cast<const f16x8*>(rowp + rb * 32 * ROWB + (((unsigned int)s << 5) ^ lxh));
-          if (S2_ABL == 5 || S2_ABL == 7) { asm volatile("" ::"v"(af), "v"(ufrag[s])); acc[rb] = zero16; }      // lab: no MFMA
-          else acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, ufrag[s], s == 0 ? zero16 : acc[rb], 0, 0, 0);
+          acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, ufrag[s], s == 0 ? zero16 : acc[rb], 0, 0, 0);
         }
       }
       if ((mb + 4) * 32 < cn) {
         const int qn = (mb + 4) * 32 + l31;
-        user = S2_ABL == 3 ? l31 : ch_user[qn < cn ? qn : 0];
+        user = ch_user[qn < cn ? qn : 0];
         L = qn < cn ? Lbuf[user] : INFINITY;
         const f16x8* src = reinterpret_cast<const f16x8*>(U + (long)user * D);
-        if (S2_ABL == 7) {
-#pragma unroll
-          for (int s = 0; s < KS; ++s) {
-            const int qq = (mb + 4) * 32 + (4 * s + (lane >> 4)) % 32;
-            ufrag[s] = reinterpret_cast<const f16x8*>(U + (long)ch_user[qq < cn ? qq : 0] * D)[lane & 15];
-          }
-        } else {
 #pragma unroll
         for (int s = 0; s < KS; ++s) ufrag[s] = src[2 * s + half];
-        }
       }
       if (tail_st) {
 #pragma unroll
@@ -576,7 +437,6 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
         }
       }
       int n = 0;
-      if (S2_ABL == 4 || S2_ABL == 5 || S2_ABL == 7) { asm volatile("" ::"v"(acc[0]), "v"(acc[1])); continue; }      // lab: no epilogue
 #define S2_AP(RB, R) s2_try_append<(RB) * 256 + ((R) >> 2) * 64 + ((R) & 3)>(acc[RB][R], cur_L, n, priv_addr, il);
 #define S2_AP16(RB) S2_AP(RB, 0) S2_AP(RB, 1) S2_AP(RB, 2) S2_AP(RB, 3) S2_AP(RB, 4) S2_AP(RB, 5) S2_AP(RB, 6) S2_AP(RB, 7) \
                     S2_AP(RB, 8) S2_AP(RB, 9) S2_AP(RB, 10) S2_AP(RB, 11) S2_AP(RB, 12) S2_AP(RB, 13) S2_AP(RB, 14) S2_AP(RB, 15)

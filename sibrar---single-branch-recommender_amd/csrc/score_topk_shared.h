@@ -1,4 +1,4 @@
-// Shared between the two fused scorers (score_topk_f16_n.hip: the one-pass narrow-wave kernel; score_topk_f16_2p.hip: the two-pass
+// Shared between the fused scorers (score_topk_f16_n.hip / score_topk_f32s.hip: the one-pass kernels; score_topk_f16_2p.hip: the two-pass
 // scorer): ring / wave geometry constants, small device helpers, the lane-parallel k-th-of-32 selection, the exclusion event stream
 // builder and the unit plan. Everything here has internal linkage (each translation unit compiles its own copy).
 #pragma once
@@ -21,9 +21,6 @@
 #endif
 #ifndef S5_NS
 #define S5_NS 6                          // LDS ring slots of 16 KB (D = 128: 64-item tiles, D = 256: 32-item tiles)
-#endif
-#ifndef S5_EVABL
-#define S5_EVABL 0                        // lab (timing only, wrong results): 1 = the event window is never refilled
 #endif
 #define S5_EV_NONE 0xFFFFFFFFu            // padding event: its tile field matches no tile
 // all LDS reads of the tile have returned (the accumulators are named so that the wait stays behind the MFMAs that consume the

@@ -305,21 +305,22 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
         bs = int(getattr(eval_loader, 'batch_size', 256) or 256)
         if scorer not in ('fp32', 'fp16_fused', 'fp32_fused'):
             raise ValueError(f'unknown scorer {scorer!r}')
-        if scorer == 'fp32_fused' and (not plain or not ops.score_topk_f32s_supported(int(i_repr.shape[1]), kmax)):
-            # the fp32-class fused kernel keeps at most 32 candidates per user and is built for D in {64, 128} (the user planes of
-            # D = 256 do not fit its registers): everything else takes the exact fp32 GEMM + radix-select path
-            logging.info(f'fp32_fused scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
+        # the fused routes: (shape the kernel takes (D, k), item operand made once per call, user operand made per chunk, call).
+        # fp16_fused keeps at most 32 candidates per user on chip and is built for D in {64, 128, 256}; fp32_fused also keeps 32 and is
+        # built for D in {64, 128} (the user planes of D = 256 do not fit its registers). Everything else — larger cut-offs (the
+        # reference's default evaluator asks for top-100), tuple item sides — takes the exact fp32 GEMM + radix-select path.
+        fused_routes = {
+            'fp16_fused': (lambda D, k: k <= 32 and D in (64, 128, 256), ops.cast_f16, ops.cast_f16, ops.score_topk_f16),
+            'fp32_fused': (ops.score_topk_f32s_supported, ops.split_bf16x3, lambda u: u, ops.score_topk_f32s),
+        }
+        if scorer in fused_routes and (not plain or not fused_routes[scorer][0](int(i_repr.shape[1]), kmax)):
+            logging.info(f'{scorer} scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
                          f'the fused kernel, using the fp32 path')
             scorer = 'fp32'
-        if scorer == 'fp16_fused' and (not plain or kmax > 32 or i_repr.shape[1] not in (64, 128, 256)):
-            # the fused kernel keeps at most 32 candidates per user on chip and is built for D in {64, 128, 256}: larger
-            # cut-offs (the reference's default evaluator asks for top-100) take the exact fp32 GEMM + radix-select path
-            logging.info(f'fp16_fused scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
-                         f'the fused kernel, using the fp32 path')
-            scorer = 'fp32'
-        fused = scorer in ('fp16_fused', 'fp32_fused')
-        # item operand of the fused kernel, made once per call: fp16 [I, D] or three bf16 planes [3, I, D]
-        i_op = ops.cast_f16(i_repr) if scorer == 'fp16_fused' else (ops.split_bf16x3(i_repr) if scorer == 'fp32_fused' else None)
+        fused = scorer in fused_routes
+        if fused:
+            _, item_operand, user_operand, score_fused = fused_routes[scorer]
+            i_op = item_operand(i_repr)                             # made once per call: fp16 [I, D] or three bf16 planes [3, I, D]
         if user_chunk is not None:
             bs = int(user_chunk)
         elif fused:
@@ -345,11 +346,7 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
                 # (and the route: the two fused kernels lay the stream out for different tile widths)
                 holder = cache.setdefault((scorer, s, int(chunk.size), int(chunk[0]), int(chunk[-1]), int(chunk.sum()), lo, hi,
                                            int(i_op.shape[-1])), ops.ScorerExclusions())
-                if scorer == 'fp16_fused':
-                    val, idx = ops.score_topk_f16(ops.cast_f16(u_repr), i_op, kmax, u_idxs, excl[0], excl[1], item_offset=lo,
-                                                  exclusions=holder)
-                else:
-                    val, idx = ops.score_topk_f32s(u_repr, i_op, kmax, u_idxs, excl[0], excl[1], item_offset=lo, exclusions=holder)
+                val, idx = score_fused(user_operand(u_repr), i_op, kmax, u_idxs, excl[0], excl[1], item_offset=lo, exclusions=holder)
             else:
                 out = alg.combine_user_item_representations(u_repr, i_repr)
                 ops.mask_scores_(out, u_idxs, excl[0], excl[1], item_offset=lo if sharded else None)

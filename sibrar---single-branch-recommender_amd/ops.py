@@ -803,20 +803,28 @@ def score_topk_route(route: int = -1) -> int:
     return int(lib().sbr_score_topk_f16_route(int(route)))
 
 
+def _score_topk_fused(entry: str, route: str, u: torch.Tensor, i_op: torch.Tensor, I: int, k: int, u_idx, excl_indptr, excl_indices,
+                      item_offset: int, exclusions):
+    """One call of a fused scorer C entry (``entry`` and ``entry + '_workspace'``): output, workspace and exclusion-event plumbing
+    shared by ``score_topk_f16`` and ``score_topk_f32s``. ``route`` keys the cached event stream (the routes lay it out for different
+    tile widths)."""
+    Bu, D = u.shape
+    val = torch.empty(Bu, k, device=u.device, dtype=torch.float32)
+    idx = torch.empty(Bu, k, device=u.device, dtype=torch.int32)
+    nnz = 0 if excl_indices is None else int(excl_indices.numel())
+    ws = torch.empty(max(int(getattr(lib(), entry + '_workspace')(Bu, I, k)), 8), device=u.device, dtype=torch.uint8)
+    ev, build = _scorer_events(exclusions, (route, Bu, I, D, int(item_offset), nnz), Bu, nnz, u.device)
+    _timed((entry[len('sbr_'):], Bu, I, D, k),
+           lambda: call(entry, ptr(u), ptr(i_op), D, Bu, I, ptr(u_idx), ptr(excl_indptr), ptr(excl_indices), nnz, item_offset, k,
+                        ptr(val), ptr(idx), ptr(ws), ws.numel(), ptr(ev), 0 if ev is None else ev.numel(), build, stream()))
+    return val, idx
+
+
 def score_topk_f16(u16: torch.Tensor, i16: torch.Tensor, k: int, u_idx=None, excl_indptr=None, excl_indices=None,
                    item_offset: int = 0, exclusions: 'ScorerExclusions' = None):
     _need_cuda(u16, i16)
-    Bu, D = u16.shape
-    I = i16.shape[0]
-    val = torch.empty(Bu, k, device=u16.device, dtype=torch.float32)
-    idx = torch.empty(Bu, k, device=u16.device, dtype=torch.int32)
-    nnz = 0 if excl_indices is None else int(excl_indices.numel())
-    ws = torch.empty(max(int(lib().sbr_score_topk_f16_workspace(Bu, I, k)), 8), device=u16.device, dtype=torch.uint8)
-    ev, build = _scorer_events(exclusions, ('f16', Bu, I, D, int(item_offset), nnz), Bu, nnz, u16.device)
-    _timed(('score_topk_f16', Bu, I, D, k),
-           lambda: call('sbr_score_topk_f16', ptr(u16), ptr(i16), D, Bu, I, ptr(u_idx), ptr(excl_indptr), ptr(excl_indices), nnz,
-                        item_offset, k, ptr(val), ptr(idx), ptr(ws), ws.numel(), ptr(ev), 0 if ev is None else ev.numel(), build, stream()))
-    return val, idx
+    return _score_topk_fused('sbr_score_topk_f16', 'f16', u16, i16, i16.shape[0], k, u_idx, excl_indptr, excl_indices, item_offset,
+                             exclusions)
 
 
 def split_bf16x3(x: torch.Tensor) -> torch.Tensor:
@@ -842,16 +850,8 @@ def score_topk_f32s(u32: torch.Tensor, i_planes: torch.Tensor, k: int, u_idx=Non
     if i_planes.dtype != torch.bfloat16 or i_planes.dim() != 3 or i_planes.shape[0] != 3 or i_planes.shape[2] != D:
         raise ValueError(f'score_topk_f32s: item planes must be bfloat16 [3, I, {D}] (split_bf16x3), got {i_planes.dtype} {tuple(i_planes.shape)}')
     i_planes = i_planes.contiguous()
-    I = i_planes.shape[1]
-    val = torch.empty(Bu, k, device=u32.device, dtype=torch.float32)
-    idx = torch.empty(Bu, k, device=u32.device, dtype=torch.int32)
-    nnz = 0 if excl_indices is None else int(excl_indices.numel())
-    ws = torch.empty(max(int(lib().sbr_score_topk_f32s_workspace(Bu, I, k)), 8), device=u32.device, dtype=torch.uint8)
-    ev, build = _scorer_events(exclusions, ('f32s', Bu, I, D, int(item_offset), nnz), Bu, nnz, u32.device)
-    _timed(('score_topk_f32s', Bu, I, D, k),
-           lambda: call('sbr_score_topk_f32s', ptr(u32), ptr(i_planes), D, Bu, I, ptr(u_idx), ptr(excl_indptr), ptr(excl_indices), nnz,
-                        item_offset, k, ptr(val), ptr(idx), ptr(ws), ws.numel(), ptr(ev), 0 if ev is None else ev.numel(), build, stream()))
-    return val, idx
+    return _score_topk_fused('sbr_score_topk_f32s', 'f32s', u32, i_planes, i_planes.shape[1], k, u_idx, excl_indptr, excl_indices,
+                             item_offset, exclusions)
 
 
 # ---- optimizer steps ----------------------------------------------------------------------------------------------------------

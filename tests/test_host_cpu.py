@@ -1,6 +1,7 @@
 """CPU (-m "not gpu"): host logic of the product — C-ABI library loads and exports every declared symbol (no compute
 calls), bit-exact samplers against the oracle and the golden streams, config parsing, state_dict contract, flat-buffer
 optimizer plumbing, and the multi-GPU paths on 2 gloo ranks."""
+import ctypes
 import os
 import re
 import subprocess
@@ -32,21 +33,55 @@ def test_library_exports_every_declared_symbol():
     assert handle.sbr_last_error() is not None
 
 
-def test_product_library_carries_no_lab_switches():
+def test_product_library_holds_exactly_the_scorer_kernels_and_no_lab_switches():
     """The timing-only ablations of the fused scorer (wrong results by design) and the environment switches that selected them are
-    compiled only into lab builds (-DSBR_LAB, tools/lab/build_scorer_variants.sh): the product library holds ONE instantiation of the
-    scorer kernel per supported D and never mentions the variables."""
+    gone from the product library: it holds exactly ONE instantiation of each one-pass scorer kernel per supported D, one final
+    selection kernel shared by both routes, and never mentions the variables."""
     from importlib import import_module
     _lib = import_module('sibrar---single-branch-recommender_amd._lib')
     if not os.path.exists(_lib.LIB_PATH):
         import __graft_entry__
         __graft_entry__.build()
     out = subprocess.run(['nm', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    kernels = set(re.findall(r' [VW] (_Z\d+score_topk_f16_n_kernelI\w+)', out))
-    assert len(kernels) == 3, kernels                                   # D = 64, 128, 256
-    assert all(re.search(r'ELi0ELb[01]EEv', k) for k in kernels), kernels     # template argument DBG = 0
+    handles = re.findall(r' [VWDT] (_Z\d+score_topk_\w+)', out)                # kernel handles (host stubs are __device_stub__ symbols)
+    f16 = sorted(re.fullmatch(r'_Z23score_topk_f16_n_kernelILi(\d+)ELi\d+ELi\d+EEv\w+', h).group(1) for h in handles
+                 if h.startswith('_Z23score_topk_f16_n_kernel'))
+    assert f16 == ['16', '4', '8'], handles                            # KS = D / 16: D = 64, 128, 256, no further template argument
+    f32s = sorted(re.fullmatch(r'_Z22score_topk_f32s_kernelILi(\d+)ELi\d+EEv\w+', h).group(1) for h in handles
+                  if h.startswith('_Z22score_topk_f32s_kernel'))
+    assert f32s == ['4', '8'], handles                                 # D = 64, 128
+    fin = [h for h in handles if 'finalize' in h]
+    assert fin == ['_Z26score_topk_finalize_kernelliliPKiPKyPfPi'], handles
     blob = open(_lib.LIB_PATH, 'rb').read()
     assert b'SBR_ST_DEBUG' not in blob and b'SBR_ST_PRE' not in blob
+
+
+def test_fused_scorer_workspace_follows_the_route():
+    """sbr_score_topk_f16_workspace sizes the workspace for the route that will run: the one-pass size under routes 0 and 1, the
+    larger of the one-pass and two-pass sizes only while route 2 is selected. At 100k x 50k the two-pass buffers are the smaller
+    ones; for a 1M-item catalogue at the evaluator's 262,144-user chunk they are several times the one-pass buffers and must not be
+    allocated by a one-pass call. The query needs no device (256 CUs assumed without one)."""
+    from importlib import import_module
+    _lib = import_module('sibrar---single-branch-recommender_amd._lib')
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    handle = ctypes.CDLL(_lib.LIB_PATH)
+    handle.sbr_score_topk_f16_workspace.restype = ctypes.c_long
+    handle.sbr_score_topk_f16_workspace.argtypes = [ctypes.c_long, ctypes.c_int, ctypes.c_int]
+    handle.sbr_score_topk_f16_route.restype = ctypes.c_int
+    handle.sbr_score_topk_f16_route.argtypes = [ctypes.c_int]
+    prev = handle.sbr_score_topk_f16_route(-1)
+    try:
+        sizes = {}
+        for route in (0, 1, 2):
+            handle.sbr_score_topk_f16_route(route)
+            sizes[route] = [handle.sbr_score_topk_f16_workspace(Bu, I, 20) for Bu, I in ((100000, 50000), (262144, 1000000))]
+    finally:
+        handle.sbr_score_topk_f16_route(prev)
+    assert sizes[0] == sizes[1], sizes
+    assert 0 < sizes[0][0] == sizes[2][0], sizes
+    assert 4 * sizes[0][1] < sizes[2][1], sizes
 
 
 def test_ops_fail_loudly_without_gpu_tensors():

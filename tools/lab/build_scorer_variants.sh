@@ -1,7 +1,7 @@
 #!/bin/bash
-# Lab: variants of the fused scorer, always built with -DSBR_LAB (the SBR_ST_DEBUG / SBR_ST_PRE environment switches and the ablation
-# instantiations exist only in these libraries, never in the product library): variants of the fused scorer (any -D switches of csrc/score_topk_f16_n.hip: S5_PF1 / S5_PF2 prefetch distances, S5_NL loader
-# waves, S5_CAPH, S5_RF, S5_NOSTORE ...) as separate libraries under tools/lab/bin/, selected through SBR_LAB_LIB.
+# Lab: variants of the fp16 fused scorer, built with -DSBR_LAB: any -D tuning knobs of csrc/score_topk_f16_n.hip and
+# csrc/score_topk_stream.h (S5_PF1 / S5_PF2 prefetch distances, S5_NL loader waves, S5_CAPH, S5_RF, S5_PRE_TILES ...) as separate
+# libraries under tools/lab/bin/, selected through SBR_LAB_LIB or timed against the product by tools/lab/scorer_ab.py.
 #   usage: bash tools/lab/build_scorer_variants.sh "tag -DS5_RF=16 ..." "tag2 ..."
 set -e
 cd "$(dirname "$0")/../.."

@@ -1,6 +1,6 @@
 """Fused scorer on the GPU box: correctness against an fp32 GEMM + top-k on a small shape, then launch times of the c2 shape
 (100k x 50k x 128) and the c5 shard shape (100k x 25k x 256), with and without exclusions, exclusion mask resident / rebuilt.
-SBR_ST_PRE (prefix tiles) is read per call by the library: pass a list to sweep.   usage: python tools/lab/scorer_time.py [pre ...]"""
+usage: python tools/lab/scorer_time.py"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch, scipy.sparse as sp
@@ -47,7 +47,6 @@ def t_ms(fn, warm=6, reps=12):
 ok = all([check(300, 1000, 128, 20), check(1000, 5000, 256, 20, 1), check(2000, 20000, 128, 20, 2), check(257, 3299, 64, 10, 3)])
 if not ok:
     print('MISMATCH'); sys.exit(1)
-pres = sys.argv[1:] or ['default']
 for (U, I, D) in ((100_000, 50_000, 128), (100_000, 25_000, 256)):
     g = torch.Generator().manual_seed(1)
     u = (torch.randn(U, D, generator=g) / 8).half().to(dev)
@@ -55,12 +54,9 @@ for (U, I, D) in ((100_000, 50_000, 128), (100_000, 25_000, 256)):
     ex = excl_csr(U, I, 50, 5)
     users = torch.arange(U, device=dev)
     flop = 2.0 * U * I * D
-    for pre in pres:
-        if pre == 'default': os.environ.pop('SBR_ST_PRE', None)
-        else: os.environ['SBR_ST_PRE'] = pre
-        h = ops.ScorerExclusions()
-        a = t_ms(lambda: ops.score_topk_f16(u, it, 20))
-        b = t_ms(lambda: ops.score_topk_f16(u, it, 20, users, ex[0], ex[1], exclusions=h))
-        c = t_ms(lambda: ops.score_topk_f16(u, it, 20, users, ex[0], ex[1]))
-        print(f'{U}x{I}x{D} pre={pre}: no excl {a:.3f} ms ({flop / a / 1e9 / 2500 * 100:.1f} %)  excl resident {b:.3f} ms ({flop / b / 1e9 / 2500 * 100:.1f} %)  '
-              f'excl rebuilt {c:.3f} ms', flush=True)
+    h = ops.ScorerExclusions()
+    a = t_ms(lambda: ops.score_topk_f16(u, it, 20))
+    b = t_ms(lambda: ops.score_topk_f16(u, it, 20, users, ex[0], ex[1], exclusions=h))
+    c = t_ms(lambda: ops.score_topk_f16(u, it, 20, users, ex[0], ex[1]))
+    print(f'{U}x{I}x{D}: no excl {a:.3f} ms ({flop / a / 1e9 / 2500 * 100:.1f} %)  excl resident {b:.3f} ms ({flop / b / 1e9 / 2500 * 100:.1f} %)  '
+          f'excl rebuilt {c:.3f} ms', flush=True)

@@ -1,6 +1,6 @@
 """Fused scorer on the bench's own model representations (c2 after a few training steps) against random data of the same shape:
-launch time with the catalogue in its own order and in a random permutation, with and without the exclusion CSR, and the
-candidates per user from the cycle stamps.   usage: python tools/scorer_on_model.py [train_steps]"""
+launch time with the catalogue in its own order and in a random permutation, with and without the exclusion CSR.
+usage: python tools/scorer_on_model.py [train_steps]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -45,27 +45,12 @@ def timed(u, it, ex, warm=10, reps=20):
     return ts[len(ts) // 2], ts[0]
 
 
-def candidates(u, it):
-    os.environ['SBR_ST_DEBUG'] = '4'
-    ws.zero_()
-    for _ in range(2):
-        L.call('sbr_score_topk_f16', u.data_ptr(), it.data_ptr(), D, Bu, I, None, None, None, 0, 0, K, val.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), None, 0, 1, L.stream())
-    torch.cuda.synchronize()
-    os.environ.pop('SBR_ST_DEBUG')
-    units = -(-Bu // 32); W = max(1, min(14, -(-units // 256)))
-    n_wg = -(-Bu // (32 * W)); off = n_wg * 32 * W * 2 * 64 * 8
-    raw = ws[off:off + n_wg * 14 * 64].view(torch.int64).cpu().numpy().reshape(n_wg * 14, 8)
-    raw = raw[raw[:, 0] > 0]
-    return (raw[:, 5] & 0xFFFFF).mean() / 32, (raw[:, 4] & 0xFFFFF).mean()
-
-
 g = torch.Generator(device=dev).manual_seed(1)
 perm = torch.randperm(I, device=dev, generator=g)
 ur = (torch.randn(Bu, D, device=dev, generator=g) / 8).half(); ir = (torch.randn(I, D, device=dev, generator=g) / 8).half()
 for name, u, it in (('random data', ur, ir), ('model, catalogue order', u16, i16), ('model, items permuted', u16, i16[perm].contiguous())):
     t0 = timed(u, it, None); t1 = timed(u, it, excl if name != 'model, items permuted' else None)
-    c = candidates(u, it)
-    print(f'{name:26s}: {t0[0]:.3f} ms (min {t0[1]:.3f}) without exclusions, {t1[0]:.3f} ms with | compactions per user {c[0]:.2f}, fired pairs per wave {c[1]:.0f}')
+    print(f'{name:26s}: {t0[0]:.3f} ms (min {t0[1]:.3f}) without exclusions, {t1[0]:.3f} ms with')
 
 # exclusion rows: degree distribution of the bench's train matrix and what the long tail costs
 ip = excl[0].cpu().numpy(); deg = np.diff(ip)
