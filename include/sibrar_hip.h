@@ -382,7 +382,8 @@ int sbr_adam_rows(int kind, int mode, float* p, float* g, float* m, float* v, lo
  * sweep_lo on, cyclically, which are brought up to `step` beside the dense part's memory stream: a caller that sweeps 1 / W of the
  * table per step bounds every row's backlog — the length of a catch-up or flush replay — by W steps. n_sweep > 0 requires that
  * the step's catch-up (sbr_adam_rows mode 0 with the same ids and step) ran before: the sweep recognises the batch's rows by its
- * claims and leaves them to their update (new in ABI 3). */
+ * claims and leaves them to their update (new in ABI 3). p / g / m / v need only 4-byte alignment: the dense part uses 16-byte
+ * accesses when lo, hi, n are multiples of 4 and all four pointers are 16-byte aligned, and the element loop (same bits) otherwise. */
 int sbr_adam_step_rows(int kind, float* p, float* g, float* m, float* v, long n, long lo, long hi, int D, const long* ids64,
                        const int* ids32, const int* rowmap, long n_ids, int* claim, int* last, void* sched, double lr, double b1,
                        double b2, double eps, double wd, long step, long sweep_lo, long n_sweep, const double* copy_src,
@@ -444,8 +445,9 @@ int sbr_score_topk_f32s(const float* U_f32, const void* I_bf16x3, int D, long Bu
                         void* stream);
 /* bytes of `workspace` for sbr_score_topk_f32s (candidate buffers + fill counts of this route only; eval/eval.py:216-222) */
 long sbr_score_topk_f32s_workspace(long Bu, int I, int k);
-/* X (fp32, n elements, contiguous) -> three bf16 planes Y[0..n), Y[n..2n), Y[2n..3n) with X = Y0 + Y1 + Y2 exactly (each plane rounded to
- * nearest even from the remainder): the item operand of sbr_score_topk_f32s (eval/eval.py:216-222) */
+/* X (fp32, n elements, contiguous) -> three bf16 planes Y[0..n), Y[n..2n), Y[2n..3n) (each plane rounded to nearest even from the
+ * remainder); X = Y0 + Y1 + Y2 exactly for x = 0 and 2^-100 <= |x| <= 3.38e38 (below, the third plane underflows; above, and for inf / NaN,
+ * the remainder planes are NaN: such item values are not supported): the item operand of sbr_score_topk_f32s (eval/eval.py:216-222) */
 int sbr_split_f32_to_bf16x3(const float* X, void* Y_bf16x3, long n, void* stream);
 
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------

@@ -258,9 +258,10 @@ __global__ __launch_bounds__(256) void adam_step_rows_kernel(float* __restrict__
     return;
   }
   const long span = hi - lo, n_rest = n - span;
-  if (((lo | hi | n) & 3) == 0) {
-    // 16 bytes per lane (the flat buffers' segments are 256-byte aligned: a quad never straddles the table): a quarter of the memory
-    // instructions of the element loop below for the same bytes; the arithmetic per element is the same function, bit for bit
+  if (((lo | hi | n) & 3) == 0 && ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0) {
+    // 16 bytes per lane when lo, hi, n are multiples of 4 AND the four base pointers are 16-byte aligned (a uniform test, as in
+    // adamw_kernel; the engine's flat buffers always are, a caller's sliced views take the element loop below): a quad never
+    // straddles the table; a quarter of the memory instructions of the element loop below for the same bytes; the arithmetic per element is the same function, bit for bit
     const long n4 = n_rest >> 2;
     for (long d4 = idx * (long)blockDim.x + threadIdx.x; d4 < n4; d4 += (long)n_dense * blockDim.x) {
       const long d = d4 << 2;

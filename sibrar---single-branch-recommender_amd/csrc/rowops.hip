@@ -725,11 +725,6 @@ __global__ void colsum_kernel(const float* __restrict__ X, long ld, long n, int 
   if (rg == 0 && cg < C) atomicAdd(&acc[cg], sm[threadIdx.x] + sm[threadIdx.x + 64] + sm[threadIdx.x + 128] + sm[threadIdx.x + 192]);
 }
 
-__global__ void d2f_kernel(const double* __restrict__ a, float* __restrict__ out, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (float)a[i];
-}
-
 // workspace: C doubles, zeroed by this call
 __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ X, long ld, long n, int C,
                                                       double* __restrict__ acc) {

@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void score_select_kernel(const uint4* __restri
       unsigned int my = 0u;                                  // lane e < 16 of the wave keeps the word of group slot e of this row
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const unsigned long long m = __ballot(f[e] >= L && f[e] > -INFINITY);
+        const unsigned long long m = __ballot(uvalid && f[e] >= L && f[e] > -INFINITY);     // by index: a +inf score equals the L = +inf of a lane without a user
         // supertile 2 (s8 + q) + (e >> 2), class e & 3: half 0 = lanes 0 .. 31, half 1 = lanes 32 .. 63
         my = lane == e * 2 ? (unsigned int)m : my;
         my = lane == e * 2 + 1 ? (unsigned int)(m >> 32) : my;
@@ -401,8 +401,10 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
     int mb = wave;
     int user = 0;
     float L = INFINITY;
+    bool valid = false;                                      // this lane holds a staged pair (q < cn), not the padding of the last block
     if (mb * 32 < cn) {
       const int q = mb * 32 + l31;
+      valid = q < cn;
       user = ch_user[q < cn ? q : 0];
       L = q < cn ? Lbuf[user] : INFINITY;
       const f16x8* src = reinterpret_cast<const f16x8*>(U + (long)user * D);
@@ -412,6 +414,7 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
     for (; mb * 32 < cn; mb += 4) {
       const int cur_user = user;
       const float cur_L = L;
+      const bool cur_valid = valid;
       f32x16 acc[2];
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
@@ -423,6 +426,7 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
       }
       if ((mb + 4) * 32 < cn) {
         const int qn = (mb + 4) * 32 + l31;
+        valid = qn < cn;
         user = ch_user[qn < cn ? qn : 0];
         L = qn < cn ? Lbuf[user] : INFINITY;
         const f16x8* src = reinterpret_cast<const f16x8*>(U + (long)user * D);
@@ -444,6 +448,9 @@ __global__ __launch_bounds__(256) void score_rescore_kernel(const _Float16* __re
       S2_AP16(1)
 #undef S2_AP16
 #undef S2_AP
+      // a padding lane (q >= cn) scores a copy of pair 0 against L = +inf, which a +inf score still passes (L <= a): validity is by
+      // index, its private slots are dropped here
+      n = cur_valid ? n : 0;
       // the block's candidates move from the private slots to the wave's list
       if (n > 4) { hard[cur_user] = 1; n = 4; }              // a fifth candidate in one half group: the exact path takes the user
       int incl_n = n;

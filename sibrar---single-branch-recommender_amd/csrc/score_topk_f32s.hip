@@ -104,7 +104,9 @@ extern "C" int sbr_score_topk_f32s(const float* U, const void* I_bf16x3, int D, 
                                  excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, events, events_bytes, build_events, s);
 }
 
-// X (fp32, n elements) -> Y = three bf16 planes of n elements each, X = Y[0] + Y[1] + Y[2] exactly (round to nearest even per plane)
+// X (fp32, n elements) -> Y = three bf16 planes of n elements each (round to nearest even per plane), X = Y[0] + Y[1] + Y[2] exactly for
+// x = 0 and 2^-100 <= |x| <= 3.38e38: below, the third plane (up to 2^-16 |x|) underflows bf16; above ~3.3961e38 the first plane rounds
+// to inf and the residual is NaN, as for inf / NaN inputs — the fused fp32-class scorer does not take such item values (ops.py)
 __global__ void split_bf16x3_kernel(const float* __restrict__ X, unsigned short* __restrict__ Y, long n) {
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
     unsigned int p0, p1, p2;

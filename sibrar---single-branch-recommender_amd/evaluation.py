@@ -8,7 +8,7 @@ Here the exclusion CSR and the label CSR are resident on the device; per user ba
   * ``scorer='fp16_fused'``: the fused fp16-MFMA score+mask+top-k kernel (scores never written), or
   * ``scorer='fp32_fused'``: the same fusion with fp32-class products (fp32 user rows and the item matrix split once into three
     exact bf16 planes, six bf16-MFMA partial products per score, fp32 accumulation): the fp32 route's ranking without its score
-    matrix; k <= 32 and D in {64, 128}, anything else falls back to ``'fp32'``,
+    matrix; k <= 32, D in {64, 128} and finite item values, anything else falls back to ``'fp32'``,
 followed by the ranking-metric kernel (NDCG / recall / precision as defined in eval/metrics.py:4-105; ``rmet`` itself is
 absent offline, so w.r.t. ``rmet`` the metric arithmetic is parity-unpinned). ``eval_batch`` keeps the reference's
 dense-logits entry point for callers that already hold a score matrix.
@@ -316,6 +316,10 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
         if scorer in fused_routes and (not plain or not fused_routes[scorer][0](int(i_repr.shape[1]), kmax)):
             logging.info(f'{scorer} scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
                          f'the fused kernel, using the fp32 path')
+            scorer = 'fp32'
+        if scorer == 'fp32_fused' and not ops.split_bf16x3_supported(i_repr):
+            # an inf / NaN (or > 3.38e38) item value splits into NaN planes: every score of that item would be NaN in the fused kernel
+            logging.info('fp32_fused scorer: non-finite item representations, using the fp32 path')
             scorer = 'fp32'
         fused = scorer in fused_routes
         if fused:

@@ -828,12 +828,22 @@ def score_topk_f16(u16: torch.Tensor, i16: torch.Tensor, k: int, u_idx=None, exc
 
 
 def split_bf16x3(x: torch.Tensor) -> torch.Tensor:
-    """fp32 [..., D] -> bfloat16 [3, ..., D]: three planes whose sum is x exactly (the item operand of ``score_topk_f32s``)."""
+    """fp32 [..., D] -> bfloat16 [3, ..., D]: three planes (round to nearest even each) whose sum is x — exactly for x = 0 and
+    2^-100 <= |x| <= 3.38e38 (the item operand of ``score_topk_f32s``). Below 2^-100 the third plane underflows bf16 and the sum is
+    x only to ~2^-133 absolute; above ~3.3961e38 the first plane rounds to inf and the sum is NaN; inf and NaN give (x, NaN, NaN).
+    tests/test_hip_rowops.py asserts the range. Non-finite values are therefore NOT supported by the fp32-class scorer (every score
+    of such an item row is NaN): check with ``split_bf16x3_supported`` and use the 'fp32' route instead, as the evaluator does."""
     _need_cuda(x)
     x = _f32c(x)
     y = torch.empty((3,) + tuple(x.shape), device=x.device, dtype=torch.bfloat16)
     call('sbr_split_f32_to_bf16x3', ptr(x), ptr(y), x.numel(), stream())
     return y
+
+
+def split_bf16x3_supported(x: torch.Tensor) -> bool:
+    """True when every value of x is finite and within the first plane's range (|x| <= 3.38e38): the bf16 split of anything else
+    holds NaN planes (one reduction and one host read; the evaluator asks once per evaluation, where the planes are built)."""
+    return bool((x.abs() <= 3.38e38).all())
 
 
 def score_topk_f32s_supported(D: int, k: int) -> bool:

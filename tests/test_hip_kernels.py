@@ -924,6 +924,51 @@ def test_deferred_adam_with_the_sweep_of_the_optimizer_launch_is_bit_identical(n
     assert torch.equal(opts[1].m.cpu(), opts[0].m.cpu()) and torch.equal(opts[1].v.cpu(), opts[0].v.cpu())
 
 
+@pytest.mark.parametrize('kind', [0, 1])
+def test_adam_step_rows_on_views_off_a_16_byte_boundary_gives_the_same_bits(kind):
+    """sbr_adam_step_rows takes its 16-byte path when lo, hi, n are multiples of 4 AND p, g, m, v are 16-byte aligned
+    (adam_step_rows_kernel tests the pointers, like adamw_kernel). The same three steps on buffers sliced at element 1 of a larger
+    NaN-filled allocation (4 bytes off: the element loop) give the bits of the aligned call — parameters, both moments and the reset
+    gradient — leave the table range [lo, hi) alone (no ids, no sweep) and write nothing outside [0, n)."""
+    import sibrar_amd as S
+    from importlib import import_module
+    lib_ = import_module(S.ops.__name__.rsplit('.', 1)[0] + '._lib')
+    n, lo, hi, D = 6000, 1024, 1024 + 8 * 80, 80
+    gen = torch.Generator().manual_seed(21)
+    init = [torch.randn(n, generator=gen) * 0.1, None, torch.randn(n, generator=gen) * 0.01, torch.rand(n, generator=gen) * 1e-3]
+    grads = [torch.randn(n, generator=gen) for _ in range(3)]
+    for gr in grads:
+        gr[::5] = 0.0
+    res = []
+    for off in (0, 1, 0):
+        bufs = []
+        for q in range(4):
+            flat = torch.full((64 + off + n + 64,), float('nan'), device=DEV)
+            view = flat[64 + off: 64 + off + n]
+            assert view.data_ptr() % 16 == 4 * off
+            view.copy_(init[q] if init[q] is not None else torch.zeros(n))
+            bufs.append((flat, view))
+        (_, p), (_, g), (_, m), (_, v) = bufs
+        claim, last = torch.zeros(16, dtype=torch.int32, device=DEV), torch.zeros(16, dtype=torch.int32, device=DEV)
+        sched = torch.zeros(16, 2, device=DEV)
+        for t in range(3):
+            g.copy_(grads[t])
+            lib_.call('sbr_adam_step_rows', kind, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lo, hi, D, None, None, None, 0,
+                      claim.data_ptr(), last.data_ptr(), sched.data_ptr(), 3e-3, 0.9, 0.999, 1e-8, 1e-2, t + 1, 0, 0, None, None, 0, S.ops.stream())
+            torch.cuda.synchronize()
+        for flat, view in bufs:
+            assert bool(torch.isnan(flat[:64 + off]).all()) and bool(torch.isnan(flat[64 + off + n:]).all()), 'wrote outside [0, n)'
+        res.append([view.cpu() for _, view in bufs])
+    inside = torch.zeros(n, dtype=torch.bool)
+    inside[lo:hi] = True
+    for q, name in enumerate(('p', 'g', 'm', 'v')):
+        assert torch.equal(res[0][q].view(torch.int32), res[2][q].view(torch.int32)), f'{name}: two aligned runs differ'
+        assert torch.equal(res[0][q].view(torch.int32), res[1][q].view(torch.int32)), f'{name}: the misaligned call differs from the aligned one'
+        if name != 'g':
+            assert torch.equal(res[1][q][inside], init[q][inside]), f'{name}: the table range was touched'
+    assert bool((res[1][1][~inside] == 0).all()) and bool((res[1][0][~inside] != init[0][~inside]).any())
+
+
 @pytest.mark.parametrize('every', [0, 16])
 def test_deferred_adamw_replay_of_idle_rows_is_bit_identical(every):
     """The replay's short cut for rows whose first moment is exactly zero (csrc/optim.hip, adam_wave_is_idle: never touched, or idle
