@@ -36,6 +36,26 @@ extern "C" {
 const char* sbr_last_error(void);
 int sbr_abi_version(void);
 
+/* ---- deterministic mode — utilities/utils.py:22-27 (reproducible(seed): the seeds + torch.backends.cudnn.deterministic) ------
+ * A process-wide switch (additive to ABI 4; off by default). While it is on, no entry point launches a kernel that accumulates
+ * floats or doubles with atomics in arrival order: an entry point that has such a path takes its fixed-order form (every sum has one
+ * owner and a fixed order of addition, so repeated runs give the same bits) or returns an error whose message names the entry point
+ * and says "no deterministic form" — never the atomic path. The fixed-order forms keep a library-owned scratch block per device:
+ * drive one stream per device while the mode is on, and run a step once with plain launches before capturing it into a graph.
+ * sbr_nondeterministic_launches(): how many launches of arrival-order float accumulation the entry points have made since the last
+ * sbr_reset_nondeterministic_launches(), counted on the host in BOTH modes (0 over a training = it stayed on fixed-order paths). */
+int sbr_set_deterministic(int on);
+int sbr_get_deterministic(void);
+long sbr_nondeterministic_launches(void);
+int sbr_reset_nondeterministic_launches(void);
+
+/* The fixed-order form of sbr_scatter_add_rows (what that entry point runs while the mode is on; callable in either mode) —
+ * utilities/utils.py:22-27 applied to the dense nn.Embedding gradient of algorithms/sgd_alg.py:144-145: the rows are grouped by
+ * destination on the device, one wave owns a destination row and adds its source rows in ascending j. D <= 512; source rows that
+ * are all zero are skipped (the padded slots of a captured step). */
+int sbr_scatter_add_rows_det(const float* dOut, long ldo, const int* in_idx, const int* rows, float* dW, long ldw, long n, int D,
+                             void* stream);
+
 /* ---- dense products on the matrix cores (fp32 in / fp32 accumulate, v_mfma_f32_32x32x2_f32) -------------------------
  * mode 0 (NT): C[ci(m), n] = act(sum_k A[ai(m), k] * B[n, k] + bias[n])     nn.Linear forward — modules/polylinear.py:51,
  *              the modality projectors algorithms/sgd_alg.py:1342-1357 with the row gather of sgd_alg.py:1960-1974 fused

@@ -25,6 +25,21 @@ from .datasets import NegativeSamplingDataLoader, SyntheticDataset              
 from .splitdata import SplitDataset, load_split_dataset                                     # noqa: F401
 from . import ops, parallel, sampling                                                       # noqa: F401
 
+
+def reproducible(seed: int, deterministic: bool = True) -> None:
+    """utilities/utils.py:22-27 (``reproducible(seed)``): seeds Python's, NumPy's and torch's generators and switches the engine's
+    deterministic mode on (``ops.set_deterministic``) — the counterpart of ``torch.backends.cudnn.deterministic = True``: the same
+    seed then gives the same model, bit for bit, on one GPU."""
+    import random
+    import numpy as np
+    import torch
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(seed)
+    ops.set_deterministic(deterministic)
+
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf -> class (algorithms/algorithms_utils.py:14,17,36)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet}

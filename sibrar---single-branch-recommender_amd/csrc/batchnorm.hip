@@ -6,6 +6,7 @@
 // Train backward: pass 1 column sums of dz and dz*xhat        -> ws[2*D] ; pass 2 dx = w*rstd*(dz - mean(dz) - xhat*mean(dz*xhat)).
 // HBM-bound: forward reads X twice and writes Y once (12 B/element), backward reads X, Y, dY twice and writes dX.
 #include "common.h"
+#include "det.h"
 
 // grid: (row chunks, column groups of 64); block 256 = 4 row lanes x 64 columns
 __global__ void bn_stats_kernel(const float* __restrict__ X, long n, int D, double* __restrict__ ws) {
@@ -29,12 +30,13 @@ __global__ void bn_stats_kernel(const float* __restrict__ X, long n, int D, doub
   }
 }
 
-__global__ __launch_bounds__(256) void bn_stats4_kernel(const float* __restrict__ X, long n, int D, double* __restrict__ ws) {
+__global__ __launch_bounds__(256) void bn_stats4_kernel(const float* __restrict__ X, long n, int D, double* __restrict__ ws,
+                                                        double* __restrict__ slots) {
   sbr_col_reduce<2>(n, D, ws, [&](long j, int cg, float4* v) {
     const float4 x = *reinterpret_cast<const float4*>(X + j * D + 4 * cg);
     v[0] = x;
     v[1] = make_float4(x.x * x.x, x.y * x.y, x.z * x.z, x.w * x.w);
-  });
+  }, slots);
 }
 
 // one thread per column: batch mean / rstd, running-stat update
@@ -86,9 +88,19 @@ static int grid1d(long total) {
 // leaves the replica part zeroed again (no memset per call)
 static int bn_train_stats(const float* X, long n, int D, float* running_mean, float* running_var, long* num_batches_tracked,
                           float* save_mean, float* save_rstd, double* ws, float eps, float momentum, hipStream_t s) {
-  if (sbr_col_reduce_ok(X, D, D)) {
-    bn_stats4_kernel<<<sbr_col_reduce_blocks(n, D), 256, 0, s>>>(X, n, D, ws);
+  if (sbr_det_on()) {            // fixed-slot form: one slot per block, folded into replica 1 in slot order
+    SBR_REQUIRE(sbr_col_reduce_ok(X, D, D), "sbr_bn_train_fwd/stats: no deterministic form for D=%d (needs D %% 4 == 0, D <= 1024, 16-byte aligned rows)", D);
+    const int nb = sbr_col_reduce_blocks(n, D);
+    double* slots = (double*)sbr_det_scratch(SBR_SCRATCH_COLRED, (size_t)nb * 2 * D * sizeof(double), s, "sbr_bn_train_fwd/stats");
+    if (!slots) return SBR_ERR_HIP;
+    bn_stats4_kernel<<<nb, 256, 0, s>>>(X, n, D, ws, slots);
+    const int rc = sbr_det_fold_slots(slots, nb, 2 * D, ws, s, "sbr_bn_train_fwd/stats");
+    if (rc) return rc;
+  } else if (sbr_col_reduce_ok(X, D, D)) {
+    sbr_note_arrival_order();
+    bn_stats4_kernel<<<sbr_col_reduce_blocks(n, D), 256, 0, s>>>(X, n, D, ws, nullptr);
   } else {                       // generic path: atomics straight into replica 1
+    sbr_note_arrival_order();
     int bx = sbr_cdiv(n, 64);
     if (bx > 512) bx = 512;
     bn_stats_kernel<<<dim3(bx, sbr_cdiv(D, 64)), 256, 0, s>>>(X, n, D, ws + 2 * D);
@@ -175,7 +187,7 @@ __global__ void bn_bwd_stats_kernel(const float* __restrict__ dY, const float* _
 __global__ __launch_bounds__(256) void bn_bwd_stats4_kernel(const float* __restrict__ dY, const float* __restrict__ Y,
                                                             const float* __restrict__ X, long n, int D,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                            int act, double* __restrict__ ws) {
+                                                            int act, double* __restrict__ ws, double* __restrict__ slots) {
   const int cg0 = threadIdx.x % (D >> 2);
   const float4 m = *reinterpret_cast<const float4*>(mean + 4 * cg0), r = *reinterpret_cast<const float4*>(rstd + 4 * cg0);
   sbr_col_reduce<2>(n, D, ws, [&](long j, int cg, float4* v) {
@@ -188,7 +200,7 @@ __global__ __launch_bounds__(256) void bn_bwd_stats4_kernel(const float* __restr
     v[0] = dz;
     v[1] = make_float4(dz.x * ((x.x - m.x) * r.x), dz.y * ((x.y - m.y) * r.y), dz.z * ((x.z - m.z) * r.z),
                        dz.w * ((x.w - m.w) * r.w));
-  });
+  }, slots);
 }
 
 __global__ void bn_bwd_apply_kernel(const float* __restrict__ dY, const float* __restrict__ Y, const float* __restrict__ X,
@@ -216,9 +228,20 @@ extern "C" int sbr_bn_train_bwd(const float* dY, const float* Y, const float* X,
   SBR_REQUIRE(dY && Y && X && dX && weight && save_mean && save_rstd && dWeight && dBias && ws, "sbr_bn_train_bwd: null operand");
   SBR_REQUIRE(n >= 1, "sbr_bn_train_bwd: empty batch");
   hipStream_t s = (hipStream_t)stream;
-  if (sbr_col_reduce_ok(X, D, D) && ((((uintptr_t)dY) | ((uintptr_t)Y) | ((uintptr_t)save_mean) | ((uintptr_t)save_rstd)) & 15) == 0) {
-    bn_bwd_stats4_kernel<<<sbr_col_reduce_blocks(n, D), 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, ws);
+  const bool vec_ok = sbr_col_reduce_ok(X, D, D) && ((((uintptr_t)dY) | ((uintptr_t)Y) | ((uintptr_t)save_mean) | ((uintptr_t)save_rstd)) & 15) == 0;
+  if (sbr_det_on()) {            // fixed-slot form (see bn_train_stats)
+    SBR_REQUIRE(vec_ok, "sbr_bn_train_bwd: no deterministic form for D=%d (needs D %% 4 == 0, D <= 1024, 16-byte aligned operands)", D);
+    const int nb = sbr_col_reduce_blocks(n, D);
+    double* slots = (double*)sbr_det_scratch(SBR_SCRATCH_COLRED, (size_t)nb * 2 * D * sizeof(double), s, "sbr_bn_train_bwd");
+    if (!slots) return SBR_ERR_HIP;
+    bn_bwd_stats4_kernel<<<nb, 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, ws, slots);
+    const int rc = sbr_det_fold_slots(slots, nb, 2 * D, ws, s, "sbr_bn_train_bwd");
+    if (rc) return rc;
+  } else if (vec_ok) {
+    sbr_note_arrival_order();
+    bn_bwd_stats4_kernel<<<sbr_col_reduce_blocks(n, D), 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, ws, nullptr);
   } else {                       // generic path: atomics straight into replica 1
+    sbr_note_arrival_order();
     int bx = sbr_cdiv(n, 64);
     if (bx > 512) bx = 512;
     bn_bwd_stats_kernel<<<dim3(bx, sbr_cdiv(D, 64)), 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, ws + 2 * D);

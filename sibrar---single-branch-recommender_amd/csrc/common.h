@@ -110,13 +110,15 @@ static inline bool sbr_attr_stale(int* slot) {
 // finishing kernel (sbr_colred_take) leaves it zero again.
 //   K: reduced quantities per element; f(row, cg, v) fills v[K] (float4 each) for columns 4*cg .. 4*cg+3 of `row`.
 // Block = 256 threads = RL row lanes x (D/4) column groups (D <= 1024).
+// `slots` (deterministic mode, det.h): [gridDim.x][K*D] doubles — every block stores its sums in the slot of its own blockIdx
+// instead of adding them to a replica; nothing then depends on the order in which blocks finish.
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void sbr_f4_add(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 
 #define SBR_COLRED_REP 16
 
 template <int K, class F>
-__device__ __forceinline__ void sbr_col_reduce(long n, int D, double* __restrict__ ws, F f) {
+__device__ __forceinline__ void sbr_col_reduce(long n, int D, double* __restrict__ ws, F f, double* __restrict__ slots = nullptr) {
   __shared__ float4 sm[K][256];
   const int C4 = D >> 2, RL = 256 / C4;
   const int t = threadIdx.x, cg = t % C4, rl = t / C4;
@@ -150,6 +152,11 @@ __device__ __forceinline__ void sbr_col_reduce(long n, int D, double* __restrict
       for (int r = 0; r < RL; ++r) {
         const float4 p = sm[k][r * C4 + t];
         s0 += (double)p.x; s1 += (double)p.y; s2 += (double)p.z; s3 += (double)p.w;
+      }
+      if (slots) {               // deterministic mode: this block's own slot, plain stores; det.h: sbr_det_fold_slots adds the slots
+        double* o = slots + (long)blockIdx.x * K * D + (long)k * D + 4 * t;
+        o[0] = s0; o[1] = s1; o[2] = s2; o[3] = s3;
+        continue;
       }
       double* o = ws + (long)(1 + (blockIdx.x % SBR_COLRED_REP)) * K * D + (long)k * D + 4 * t;
       atomicAdd(o, s0); atomicAdd(o + 1, s1); atomicAdd(o + 2, s2); atomicAdd(o + 3, s3);

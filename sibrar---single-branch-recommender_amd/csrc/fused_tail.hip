@@ -17,6 +17,7 @@
 // sums of its output (the bias gradient of its layer) into a column-reduction workspace; all pending workspaces of a step
 // are turned into float vectors by ONE launch at the end of the backward pass.
 #include "loss_common.h"
+#include "det.h"
 
 // The three kernels that walk the rows of Z (scorer forward, backward pass A, and the fused forward + loss + pass A kernel) go
 // through these functions — explicit fused multiply-adds, no contraction left to the compiler — so that they produce the same bits
@@ -341,6 +342,7 @@ extern "C" int sbr_bn_score_loss_fwd_bwd(const float* Z, const float* U, const f
   SBR_REQUIRE(sbr_bn_score_loss_supported(D, N) && tail_ok(Z, U, save_mean, D) && tail_ok(save_rstd, weight, bias, D) && tail_ok(dU, dU, dU, D),
               "sbr_bn_score_loss_fwd_bwd: D=%d N=%d / alignment not supported", D, N);
   SBR_REQUIRE(lws && lws_bytes >= sbr_bn_score_loss_workspace(), "sbr_bn_score_loss_fwd_bwd: workspace too small");
+  SBR_ARRIVAL_ORDER("sbr_bn_score_loss_fwd_bwd");      // BatchNorm backward column sums: double atomics into the replicas
   const int RL = 256 / (D >> 2);
   long blocks = (B + (long)BSL_USERS * RL - 1) / ((long)BSL_USERS * RL);
   if (blocks > BSL_MAX_BLOCKS) blocks = BSL_MAX_BLOCKS;
@@ -423,6 +425,7 @@ extern "C" int sbr_bn_score_bwd_stats(const float* G, const float* U, const floa
   SBR_REQUIRE(G && U && Z && weight && bias && save_mean && save_rstd && ws, "sbr_bn_score_bwd_stats: null operand");
   SBR_REQUIRE(sbr_bn_score_supported(D) && tail_ok(Z, U, save_mean, D) && tail_ok(save_rstd, weight, bias, D) && tail_ok(dU, dU, dU, D),
               "sbr_bn_score_bwd_stats: D=%d / alignment not supported", D);
+  SBR_ARRIVAL_ORDER("sbr_bn_score_bwd_stats");
   hipStream_t s = (hipStream_t)stream;
   const int RL = 256 / (D >> 2);
   long blocks = (B + 2L * RL - 1) / (2L * RL);               // >= 2 users per row lane
@@ -442,6 +445,7 @@ extern "C" int sbr_bn_score_bwd_apply(const float* G, const float* U, const floa
   SBR_REQUIRE(G && U && Z && dX && weight && save_mean && save_rstd && ws && dWeight && dBias, "sbr_bn_score_bwd_apply: null operand");
   SBR_REQUIRE(sbr_bn_score_supported(D) && tail_ok(Z, U, save_mean, D) && tail_ok(save_rstd, weight, dX, D),
               "sbr_bn_score_bwd_apply: D=%d / alignment not supported", D);
+  if (ws_colsum) SBR_ARRIVAL_ORDER("sbr_bn_score_bwd_apply");       // the folded bias-gradient column sums
   hipStream_t s = (hipStream_t)stream;
   const long R = B * N;
   const int blocks = sbr_col_reduce_blocks(R, D);
@@ -478,6 +482,7 @@ extern "C" int sbr_act_grad_gather_colsum(const float* dY, const float* Y, long 
   SBR_REQUIRE(sbr_act_grad_colsum_supported(C) && (ld & 3) == 0 && (ldz & 3) == 0 &&
                   ((((uintptr_t)dY) | ((uintptr_t)Y) | ((uintptr_t)dZ)) & 15) == 0,
               "sbr_act_grad_gather_colsum: C=%d / alignment not supported (use sbr_act_grad_gather + sbr_colsum)", C);
+  SBR_ARRIVAL_ORDER("sbr_act_grad_gather_colsum");                   // (fixed-order form: sbr_act_grad_gather + sbr_colsum)
   act_grad_colsum4_kernel<<<sbr_col_reduce_blocks(n, C), 256, 0, (hipStream_t)stream>>>(dY, Y, ld, in_idx, dZ, ldz, n, C, act, ws);
   SBR_CHECK_LAUNCH("sbr_act_grad_gather_colsum");
   return SBR_OK;

@@ -15,6 +15,7 @@
 // MFMAs of slab t). Within each 8-wide k group lane-half h supplies k = 4h + s to MFMA step s, so one 16-byte LDS
 // read feeds four MFMAs.
 #include "gemm_args.h"
+#include "det.h"
 #include <stdlib.h>
 
 #define BK 32
@@ -325,6 +326,7 @@ extern "C" int sbr_gemm_f32(int mode, const float* A, long lda, const int* a_idx
   if (M == 0 || N == 0) return SBR_OK;
   SBR_REQUIRE(A && B && C, "sbr_gemm_f32: null operand");
   SBR_REQUIRE(!(accumulate_atomic && act != SBR_ACT_NONE), "sbr_gemm_f32: activation with atomic accumulate");
+  if (accumulate_atomic) SBR_ARRIVAL_ORDER("sbr_gemm_f32");          // (fixed-order forms: sbr_gemm_tn_f32, sbr_gemm_nt_splitk_f32)
   hipStream_t s = (hipStream_t)stream;
   GemmArgs g;
   g.A = A; g.lda = lda; g.a_idx = a_idx; g.B = B; g.ldb = ldb; g.b_idx = b_idx; g.bias = bias;

@@ -25,6 +25,7 @@
 //   * epilogue options of the training step as in gemm_wres_f32.hip: bias + activation (forward); multiply by the activation
 //     derivative of a second matrix Y and accumulate column sums (backward: dZ_prev = (dZ W) * act'(Y) and its bias gradient).
 #include "gemm_split_common.h"
+#include "det.h"
 #include <type_traits>
 
 #define SP_N 128
@@ -319,6 +320,10 @@ static int gemm_split_impl(int mode, const float* A, long lda, const float* W, l
   SBR_REQUIRE(!(Y && mode == 0) && !(colsum_ws && !Y && mode == 1) && !(Y && bias), "sbr_gemm_split_f32: Y belongs to mode 1 without bias");
   SplitArgs g;
   g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.C = C; g.ldc = ldc; g.M = M; g.act = act; g.Y = Y; g.ldy = ldy;
+  if (colsum_ws) {                 // column-sum / statistics epilogue (fixed-order form: sbr_colsum / sbr_bn_train_stats over the output)
+    if (fin) SBR_ARRIVAL_ORDER("sbr_gemm_split_bnstats_f32");
+    else SBR_ARRIVAL_ORDER("sbr_gemm_split_f32");
+  }
   g.colsum_ws = colsum_ws;
   g.fin_arrive = fin ? fin->arrive : nullptr; g.fin_mean = fin ? fin->mean : nullptr; g.fin_rstd = fin ? fin->rstd : nullptr;
   g.fin_running_mean = fin ? fin->running_mean : nullptr; g.fin_running_var = fin ? fin->running_var : nullptr;

@@ -18,6 +18,7 @@
 //     gradient of that layer), accumulated per workgroup over all its tiles and flushed once into a column-reduction workspace.
 // Persistent: 2 workgroups per CU (64 KB of LDS, ~200 VGPRs), workgroup b walks tiles b, b + grid, ...
 #include "gemm_args.h"
+#include "det.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -264,6 +265,7 @@ extern "C" int sbr_gemm_wres_f32(int mode, const float* A, long lda, const float
   SBR_REQUIRE(!(Y && mode == 0) && !(colsum_ws && !Y) && !(Y && bias), "sbr_gemm_wres_f32: Y / colsum_ws belong to mode 1 without bias");
   WresArgs g;
   g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.C = C; g.ldc = ldc; g.M = M; g.act = act; g.Y = Y; g.ldy = ldy;
+  if (colsum_ws) SBR_ARRIVAL_ORDER("sbr_gemm_wres_f32");             // the column-sum epilogue (fixed-order form: sbr_colsum over the output)
   g.colsum_ws = colsum_ws;
   const int n_tiles = sbr_cdiv(M, WR_BM);
   int grid = 512;

@@ -5,6 +5,7 @@
 // BCEWithLogits in float64 and return a float64 scalar; sampled-softmax and InfoNCE stay in float32 (we accumulate their
 // sums in double and round once).
 #include "loss_common.h"
+#include "det.h"
 
 // loss scalars are zeroed by a one-thread kernel, not by hipMemsetAsync: inside a replayed hipGraph the 8-byte memset node was
 // observed to stop taking effect while another host thread issued copies (the scalar then kept a stale value for every later
@@ -90,7 +91,8 @@ __global__ void rec_loss_kernel(int kind, const float* __restrict__ logits, cons
         }
       }
     } else if (threadIdx.x == 0) {
-      atomicAdd(loss_out, t * scale);
+      if (ws) ws[blockIdx.x] = t * scale;          // deterministic mode: this block's slot, summed by det.h: sbr_det_sum_partials
+      else atomicAdd(loss_out, t * scale);
     }
   }
 }
@@ -103,7 +105,15 @@ extern "C" int sbr_rec_loss_fwd(int kind, const float* logits, const double* lab
   hipStream_t s = (hipStream_t)stream;
   zero_f64_kernel<<<1, 1, 0, s>>>(loss_out);
   if (B == 0) return SBR_OK;
-  rec_loss_kernel<0><<<sbr_cdiv(B, 256), 256, 0, s>>>(kind, logits, labels, B, N, scale, shift, loss_out, nullptr, 0, nullptr);
+  const int nb = sbr_cdiv(B, 256);
+  if (sbr_det_on()) {              // block partial sums in slots, added in a fixed pattern
+    double* part = (double*)sbr_det_scratch(SBR_SCRATCH_LOSS, (size_t)nb * sizeof(double), s, "sbr_rec_loss_fwd");
+    if (!part) return SBR_ERR_HIP;
+    rec_loss_kernel<0><<<nb, 256, 0, s>>>(kind, logits, labels, B, N, scale, shift, loss_out, nullptr, 0, nullptr, part);
+    return sbr_det_sum_partials(part, nb, loss_out, s, "sbr_rec_loss_fwd");
+  }
+  sbr_note_arrival_order();
+  rec_loss_kernel<0><<<nb, 256, 0, s>>>(kind, logits, labels, B, N, scale, shift, loss_out, nullptr, 0, nullptr);
   SBR_CHECK_LAUNCH("sbr_rec_loss_fwd");
   return SBR_OK;
 }
@@ -127,7 +137,15 @@ extern "C" int sbr_rec_loss_fwd_bwd(int kind, const float* logits, const double*
   hipStream_t s = (hipStream_t)stream;
   zero_f64_kernel<<<1, 1, 0, s>>>(loss_out);
   if (B == 0) return SBR_OK;
-  rec_loss_kernel<2><<<sbr_cdiv(B, 256), 256, 0, s>>>(kind, logits, labels, B, N, scale, shift, loss_out, nullptr, 0, dlogits);
+  const int nb = sbr_cdiv(B, 256);
+  if (sbr_det_on()) {              // block partial sums in slots, added in a fixed pattern
+    double* part = (double*)sbr_det_scratch(SBR_SCRATCH_LOSS, (size_t)nb * sizeof(double), s, "sbr_rec_loss_fwd_bwd");
+    if (!part) return SBR_ERR_HIP;
+    rec_loss_kernel<2><<<nb, 256, 0, s>>>(kind, logits, labels, B, N, scale, shift, loss_out, nullptr, 0, dlogits, part);
+    return sbr_det_sum_partials(part, nb, loss_out, s, "sbr_rec_loss_fwd_bwd");
+  }
+  sbr_note_arrival_order();
+  rec_loss_kernel<2><<<nb, 256, 0, s>>>(kind, logits, labels, B, N, scale, shift, loss_out, nullptr, 0, dlogits);
   SBR_CHECK_LAUNCH("sbr_rec_loss_fwd_bwd");
   return SBR_OK;
 }
@@ -159,7 +177,7 @@ extern "C" int sbr_rec_loss_fwd_bwd_ws(int kind, const float* logits, const doub
 template <bool BWD>
 __global__ void infonce_kernel(const float* __restrict__ A, const float* __restrict__ Bm, long ld, int N, int D,
                                float inv_tau, double scale, double* __restrict__ loss_out, const float* __restrict__ gout,
-                               float* __restrict__ dA, float* __restrict__ dB, long ldg) {
+                               float* __restrict__ dA, float* __restrict__ dB, long ldg, double* __restrict__ part = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int LN = N + 1;
   float* L = sm;                 // [N][N+1]
@@ -190,7 +208,10 @@ __global__ void infonce_kernel(const float* __restrict__ A, const float* __restr
     for (int i = threadIdx.x; i < N; i += blockDim.x) acc += (double)(lse_r[i] - L[i * LN + i]) + (double)(lse_c[i] - L[i * LN + i]);
     __shared__ double red[4];
     const double t = block_sum_d(acc, red);
-    if (threadIdx.x == 0) atomicAdd(loss_out, t * scale);
+    if (threadIdx.x == 0) {
+      if (part) part[blockIdx.x] = t * scale;       // deterministic mode
+      else atomicAdd(loss_out, t * scale);
+    }
   } else {
     const float up = gout[0] * (float)scale * inv_tau;
     // G[i][j] = up * (softmax_row + softmax_col - 2*delta)
@@ -229,7 +250,7 @@ template <bool BWD>
 __global__ __launch_bounds__(256) void infonce_small_kernel(const float* __restrict__ A, const float* __restrict__ Bm, long ld, long G,
                                                             int N, int D, float inv_tau, double scale, double* __restrict__ loss_out,
                                                             const float* __restrict__ gout, float* __restrict__ dA,
-                                                            float* __restrict__ dB, long ldg) {
+                                                            float* __restrict__ dB, long ldg, double* __restrict__ part = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int LD = D + 4, LN = N + 1;
@@ -319,7 +340,10 @@ __global__ __launch_bounds__(256) void infonce_small_kernel(const float* __restr
   if constexpr (!BWD) {
     __shared__ double red[4];
     const double t = block_sum_d(loss_acc, red);                // every wave of the workgroup arrives here
-    if (threadIdx.x == 0) atomicAdd(loss_out, t * scale);
+    if (threadIdx.x == 0) {
+      if (part) part[blockIdx.x] = t * scale;                   // deterministic mode
+      else atomicAdd(loss_out, t * scale);
+    }
   }
 }
 static bool infonce_small_ok(const float* A, const float* B, long ld, int N, int D, const float* dA, const float* dB, long ldg) {
@@ -342,17 +366,28 @@ extern "C" int sbr_infonce_fwd(const float* A, const float* B, long ld, long G, 
   hipStream_t s = (hipStream_t)stream;
   zero_f64_kernel<<<1, 1, 0, s>>>(loss_out);
   if (G == 0) return SBR_OK;
-  if (infonce_small_ok(A, B, ld, N, D, nullptr, nullptr, 0)) {
+  const bool small = infonce_small_ok(A, B, ld, N, D, nullptr, nullptr, 0);
+  const long nb = small ? sbr_cdiv(G, 4 * INF_S_GPW(false)) : G;
+  double* part = nullptr;          // deterministic mode: one slot per workgroup, added in a fixed pattern behind the kernel
+  if (sbr_det_on()) {
+    SBR_REQUIRE(nb < (1L << 30), "sbr_infonce_fwd: no deterministic form for %ld groups", G);
+    part = (double*)sbr_det_scratch(SBR_SCRATCH_LOSS, (size_t)nb * sizeof(double), s, "sbr_infonce_fwd");
+    if (!part) return SBR_ERR_HIP;
+  } else {
+    sbr_note_arrival_order();
+  }
+  if (small) {
     const int ls = infonce_small_lds(N, D);
     if (ls > 64 * 1024) (void)hipFuncSetAttribute((const void*)infonce_small_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ls);
-    infonce_small_kernel<false><<<(unsigned)sbr_cdiv(G, 4 * INF_S_GPW(false)), 256, ls, s>>>(A, B, ld, G, N, D, 1.f / tau, scale, loss_out, nullptr, nullptr, nullptr, 0);
+    infonce_small_kernel<false><<<(unsigned)nb, 256, ls, s>>>(A, B, ld, G, N, D, 1.f / tau, scale, loss_out, nullptr, nullptr, nullptr, 0, part);
     SBR_CHECK_LAUNCH("sbr_infonce_fwd (small groups)");
-    return SBR_OK;
+  } else {
+    const int lds = infonce_lds(N);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)infonce_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    infonce_kernel<false><<<(unsigned)G, 256, lds, s>>>(A, B, ld, N, D, 1.f / tau, scale, loss_out, nullptr, nullptr, nullptr, 0, part);
+    SBR_CHECK_LAUNCH("sbr_infonce_fwd");
   }
-  const int lds = infonce_lds(N);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)infonce_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  infonce_kernel<false><<<(unsigned)G, 256, lds, s>>>(A, B, ld, N, D, 1.f / tau, scale, loss_out, nullptr, nullptr, nullptr, 0);
-  SBR_CHECK_LAUNCH("sbr_infonce_fwd");
+  if (part) return sbr_det_sum_partials(part, (int)nb, loss_out, s, "sbr_infonce_fwd");
   return SBR_OK;
 }
 
@@ -453,6 +488,7 @@ extern "C" int sbr_infonce_gemm_fwd(const float* A, const float* B, long ld, lon
   SBR_REQUIRE(A && B && loss_out, "sbr_infonce_gemm_fwd: null operand");
   SBR_REQUIRE(N >= 1 && D >= 1, "sbr_infonce_gemm_fwd: bad shape");
   SBR_REQUIRE(workspace && workspace_bytes >= sbr_infonce_gemm_workspace(N, D), "sbr_infonce_gemm_fwd: workspace too small");
+  SBR_ARRIVAL_ORDER("sbr_infonce_gemm_fwd");           // the loss scalar: one double atomic per block and group
   hipStream_t s = (hipStream_t)stream;
   zero_f64_kernel<<<1, 1, 0, s>>>(loss_out);
   float* S = (float*)workspace;

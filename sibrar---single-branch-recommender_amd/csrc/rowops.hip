@@ -4,6 +4,7 @@
 // All of them move rows of C..D floats; lanes run along the feature dimension so that every wave instruction
 // touches one contiguous 256-byte (or wider) segment of a row.
 #include "common.h"
+#include "det.h"
 
 #define SBR_MAX_SEG 16
 
@@ -336,6 +337,9 @@ extern "C" int sbr_scatter_add_rows(const float* dOut, long ldo, const int* in_i
                                     long ldw, long n, int D, void* stream) {
   if (n == 0) return SBR_OK;
   SBR_REQUIRE(dOut && rows && dW, "sbr_scatter_add_rows: null operand");
+  // deterministic mode: the segmented form — one owner per destination row, source rows added in ascending position
+  if (sbr_det_on()) return sbr_det_scatter_add_rows(dOut, ldo, in_idx, rows, dW, ldw, n, D, (hipStream_t)stream, "sbr_scatter_add_rows");
+  sbr_note_arrival_order();
   if (D == 128 && n >= 4096) {
     int blocks = (int)sbr_cdiv(n, 16);                           // >= 4 rows per wave
     if (blocks > 2048) blocks = 2048;                            // 8 workgroups of 4 waves per CU
@@ -454,6 +458,8 @@ extern "C" int sbr_bag_mean_bwd(const float* dOut, long ldo, const int* in_idx, 
                                 const int* rows, float* dW, long ldw, long n, int D, void* stream) {
   if (n == 0) return SBR_OK;
   SBR_REQUIRE(dOut && tags && rows && dW, "sbr_bag_mean_bwd: null operand");
+  // (the gather form, sbr_csr_project_bwd_gather over the transposed tag matrix, is the fixed-order form of this gradient)
+  SBR_ARRIVAL_ORDER("sbr_bag_mean_bwd");
   bag_mean_bwd_kernel<<<sbr_cdiv(n, 4), 256, 0, (hipStream_t)stream>>>(dOut, ldo, in_idx, tags, T, pad, rows, dW, ldw, n, D);
   SBR_CHECK_LAUNCH("sbr_bag_mean_bwd");
   return SBR_OK;
@@ -611,6 +617,7 @@ extern "C" int sbr_csr_project_bwd(const long* indptr, const int* indices, const
                                    const int* rows, float* dWt, long ldw, long n, int C, void* stream) {
   if (n == 0) return SBR_OK;
   SBR_REQUIRE(indptr && indices && dZ && rows && dWt, "sbr_csr_project_bwd: null operand");
+  SBR_ARRIVAL_ORDER("sbr_csr_project_bwd");      // (fixed-order form: sbr_csr_project_bwd_gather)
   hipStream_t s = (hipStream_t)stream;
   const int nc = sbr_cdiv(C, 64);
   switch (nc) {
@@ -727,8 +734,8 @@ __global__ void colsum_kernel(const float* __restrict__ X, long ld, long n, int 
 
 // workspace: C doubles, zeroed by this call
 __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ X, long ld, long n, int C,
-                                                      double* __restrict__ acc) {
-  sbr_col_reduce<1>(n, C, acc, [&](long j, int cg, float4* v) { v[0] = *reinterpret_cast<const float4*>(X + j * ld + 4 * cg); });
+                                                      double* __restrict__ acc, double* __restrict__ slots) {
+  sbr_col_reduce<1>(n, C, acc, [&](long j, int cg, float4* v) { v[0] = *reinterpret_cast<const float4*>(X + j * ld + 4 * cg); }, slots);
 }
 
 __global__ void colsum_final_kernel(double* __restrict__ ws, int C, float* __restrict__ out) {
@@ -740,9 +747,19 @@ __global__ void colsum_final_kernel(double* __restrict__ ws, int C, float* __res
 extern "C" int sbr_colsum(const float* X, long ld, long n, int C, float* out, double* workspace, void* stream) {
   SBR_REQUIRE(out && workspace, "sbr_colsum: null operand");
   hipStream_t s = (hipStream_t)stream;
-  if (n > 0 && sbr_col_reduce_ok(X, ld, C)) {
-    colsum4_kernel<<<sbr_col_reduce_blocks(n, C), 256, 0, s>>>(X, ld, n, C, workspace);
+  if (n > 0 && sbr_det_on()) {   // fixed-slot form: one slot per block, folded into replica 1 in slot order
+    SBR_REQUIRE(sbr_col_reduce_ok(X, ld, C), "sbr_colsum: no deterministic form for C=%d (needs C %% 4 == 0, C <= 1024, 16-byte aligned rows)", C);
+    const int nb = sbr_col_reduce_blocks(n, C);
+    double* slots = (double*)sbr_det_scratch(SBR_SCRATCH_COLRED, (size_t)nb * C * sizeof(double), s, "sbr_colsum");
+    if (!slots) return SBR_ERR_HIP;
+    colsum4_kernel<<<nb, 256, 0, s>>>(X, ld, n, C, workspace, slots);
+    const int rc = sbr_det_fold_slots(slots, nb, C, workspace, s, "sbr_colsum");
+    if (rc) return rc;
+  } else if (n > 0 && sbr_col_reduce_ok(X, ld, C)) {
+    sbr_note_arrival_order();
+    colsum4_kernel<<<sbr_col_reduce_blocks(n, C), 256, 0, s>>>(X, ld, n, C, workspace, nullptr);
   } else if (n > 0) {          // generic path: atomics straight into replica 1
+    sbr_note_arrival_order();
     int bx = sbr_cdiv(n, 64);
     if (bx > 512) bx = 512;
     colsum_kernel<<<dim3(bx, sbr_cdiv(C, 64)), 256, 0, s>>>(X, ld, n, C, workspace + C);
@@ -1087,6 +1104,7 @@ extern "C" int sbr_bias_score_bwd(const float* g, const long* u, const long* i, 
                                   float* d_global_bias, long B, int N, void* stream) {
   if (B * N == 0) return SBR_OK;
   SBR_REQUIRE(g, "sbr_bias_score_bwd: null operand");
+  SBR_ARRIVAL_ORDER("sbr_bias_score_bwd");
   bias_score_bwd_kernel<<<sbr_cdiv(B * N, 256), 256, 0, (hipStream_t)stream>>>(g, u, i, d_user_bias, d_item_bias, d_global_bias, B, N);
   SBR_CHECK_LAUNCH("sbr_bias_score_bwd");
   return SBR_OK;

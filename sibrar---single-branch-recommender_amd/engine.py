@@ -144,6 +144,10 @@ class _EntityRun:
         pos_flat, k, counts, order, R, padded = plan
         self.padded = padded
         dev = idx.device
+        # deterministic mode: no reduction rides on another kernel's epilogue (those add into shared replicas in arrival order) —
+        # the trailing BatchNorm runs as its own kernels and the bias gradients as stand-alone fixed-slot column sums
+        det = ops.is_deterministic()
+        fuse_tail = self.fuse_tail and not det
         if pos_dev is None:
             pos_dev = to_device(torch.from_numpy(pos_flat), dev)
         seg = [0]
@@ -181,7 +185,7 @@ class _EntityRun:
         self.acts = []                                   # per layer: (input, pre-BN output | None, output, mean, rstd)
         # statistics of the trailing BatchNorm from the epilogue of the GEMM in front of it (fused tail only: nothing but the
         # statistics is needed from that pass over the output)
-        tail_stats = (self.trailing is not None and self.fuse_tail and k == 1 and not self.reg and bool(self.layers)
+        tail_stats = (self.trailing is not None and fuse_tail and k == 1 and not self.reg and bool(self.layers)
                       and self.layers[-1][1] is None and ops.lib().sbr_bn_score_supported(int(self.layers[-1][0].weight.shape[0])))
         self._stats_folded = False
         for li, (lin, bn, act) in enumerate(self.layers):
@@ -207,7 +211,7 @@ class _EntityRun:
         self.tb = None
         self.tail = None
         if self.trailing is not None:
-            if self.fuse_tail and k == 1 and not self.reg and ops.lib().sbr_bn_score_supported(int(x.shape[1])):
+            if fuse_tail and k == 1 and not self.reg and ops.lib().sbr_bn_score_supported(int(x.shape[1])):
                 # statistics only: the scorer normalises on the fly (FusedTrainStep._phase1), nothing else reads the output
                 bn, n_, D_ = self.trailing, x.shape[0], x.shape[1]
                 if self._stats_folded:
@@ -288,7 +292,8 @@ class _EntityRun:
         ent, a, st = self.ent, self.a, ops.stream()
         R, k, D = self.R, self.k, self.D
         S = R // k
-        pending = [] if self.fold else None           # folded bias-gradient column sums, completed by ONE launch at the end
+        # folded bias-gradient column sums, completed by ONE launch at the end (not in deterministic mode: see forward)
+        pending = [] if self.fold and not ops.is_deterministic() else None
         last_lin = self.layers[-1] if self.layers else None
         folded_last = False
         if tail is not None:
@@ -582,9 +587,17 @@ class FusedTrainStep:
 
     MAX_GRAPHS = 16
 
-    def __init__(self, net: SingleBranchNet, rec_loss, optimizer, use_graph: Optional[bool] = None):
+    def __init__(self, net: SingleBranchNet, rec_loss, optimizer, use_graph: Optional[bool] = None,
+                 deterministic: Optional[bool] = None):
         if not isinstance(net.item_embedding_module, SingleBranchNetEntity):
             raise NotImplementedError('FusedTrainStep needs a SingleBranchNetEntity item side')
+        # ``deterministic`` (default None: env ``SBR_DETERMINISTIC=1`` turns it on, else the current process-wide setting stays):
+        # True / False switch the library's deterministic mode (``ops.set_deterministic``). The mode is process-wide — a captured
+        # graph and the kernels behind an entry point cannot differ per object — and every step follows the CURRENT setting: with it
+        # on, the step takes the un-fused BatchNorm tail and stand-alone column sums (the epilogue reductions are arrival-order).
+        if deterministic is not None:
+            ops.set_deterministic(bool(deterministic))
+        self.deterministic = ops.is_deterministic()
         self.net, self.rec_loss, self.opt = net, rec_loss, optimizer
         dev = net.device
         self.arena = Arena(dev)
@@ -891,6 +904,12 @@ class FusedTrainStep:
         net = self.net
         if not net.training:
             raise RuntimeError('FusedTrainStep.step() needs the model in train mode')
+        det = ops.is_deterministic()
+        if det != self.deterministic:                                # switched since the last step: other kernels, other graphs
+            self.deterministic = det
+            self._graphs.clear()
+        if det and parallel.is_distributed():
+            raise NotImplementedError('FusedTrainStep: the deterministic mode covers single-GPU runs (multi-rank determinism is not checked)')
         with pin_stream():
             pb = draws if isinstance(draws, PreparedBatch) else self.prepare(u_idxs, i_idxs, labels, draws, ahead=False)
             native = getattr(pb, 'native', None)

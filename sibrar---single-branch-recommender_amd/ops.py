@@ -21,6 +21,46 @@ PARTITION_MAX_MODALITIES = 8      # sbr_partition_slots (SBR_PART_MAX in rowops.
 COLRED_WS_FACTOR = 17             # column-reduction workspaces: totals + SBR_COLRED_REP replicas (common.h)
 
 
+# ---- deterministic mode (include/sibrar_hip.h: sbr_set_deterministic; utilities/utils.py:22-27) -----------------------------------
+_DET = None                       # cached copy of the library's process-wide flag (None: not read yet)
+
+
+def is_deterministic() -> bool:
+    """True while the library's deterministic mode is on: no kernel of a training step accumulates floats in arrival order, so a
+    training repeated from the same parameters, batches, modality draws and dropout seeds gives the same bits."""
+    global _DET
+    if _DET is None:
+        if _os.environ.get('SBR_DETERMINISTIC', '0') == '1':
+            set_deterministic(True)
+        else:
+            _DET = bool(lib().sbr_get_deterministic())
+    return _DET
+
+
+def set_deterministic(flag: bool) -> bool:
+    """Switch the deterministic mode (process-wide; returns the previous setting; the env default is ``SBR_DETERMINISTIC=1``).
+    Entry points with an arrival-order float accumulation take their fixed-order form, or raise ``SibrarHipError`` ("... no
+    deterministic form") where they have none. The captured step graphs of every live ``FusedTrainStep`` are dropped: a captured
+    graph has its kernels baked in."""
+    global _DET
+    prev = bool(lib().sbr_get_deterministic())
+    lib().sbr_set_deterministic(1 if flag else 0)
+    _DET = bool(flag)
+    if prev != _DET:
+        from . import engine
+        for f in list(engine._LIVE):
+            f._graphs.clear()
+    return prev
+
+
+def nondeterministic_launches(reset: bool = False) -> int:
+    """Launches of arrival-order float accumulation the library has made since the last reset (counted in both modes)."""
+    n = int(lib().sbr_nondeterministic_launches())
+    if reset:
+        lib().sbr_reset_nondeterministic_launches()
+    return n
+
+
 def act_code(act) -> int:
     if isinstance(act, torch.nn.Module):
         act = act.__class__.__name__.lower()

@@ -197,6 +197,8 @@ class FeatureEmbedding(nn.Module):
     def _gather_pays(self, n: int, nnz: int, n_entities: int, n_cols: int, C: int) -> bool:
         if self.CSR_GATHER_FORCE is not None:
             return bool(self.CSR_GATHER_FORCE)
+        if ops.is_deterministic():
+            return True                                       # the gather form is the fixed-order one; the scatter form raises in this mode
         adds = n * (nnz / max(n_entities, 1))                 # (slot, entry) pairs of the step
         # ... and the adds that land on ONE gradient row serialise (~30 ns each, whatever C: the columns of a row go in parallel):
         # ML-1M's 18 genre tags take 5,000 adds per row at batch 4096 — 151 us in scatter form

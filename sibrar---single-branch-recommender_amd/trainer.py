@@ -51,6 +51,12 @@ class Trainer:
         self.model_path = _get(conf, 'results_path')
         self.batch_verbose = _get(_get(conf, 'run_settings'), 'batch_verbose', False)
         self.scorer = _get(conf, 'scorer', 'fp32')          # 'fp32' | 'fp16_fused' | 'fp32_fused' (evaluation.evaluate_recommender_algorithm)
+        # `conf.deterministic` (default None: leave the process-wide mode, whose env default is SBR_DETERMINISTIC): True / False switch
+        # ops.set_deterministic — bit-identical repeated trainings (utilities/utils.py:22-27), at some cost in step time
+        self.deterministic = _get(conf, 'deterministic', None)
+        if self.deterministic is not None:
+            from . import ops
+            ops.set_deterministic(bool(self.deterministic))
         self.best_value = self.best_metrics = self.best_epoch = None
         # the fused launch choreography (engine.FusedTrainStep) replaces autograd when the model is a SingleBranchNet with
         # an entity item side; `conf.fused_step = False` keeps the autograd path (same kernels, same results)
