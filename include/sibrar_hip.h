@@ -314,8 +314,8 @@ int sbr_bn_score_bwd_apply(const float* G, const float* U, const float* Z, float
  * statistics, logits / dlogits make no round trip between kernels. logits may be NULL; dlogits [B, N]; dU [B, D]; loss_out [1];
  * out3 (may be NULL) = (loss, loss, 0): the packed (total, rec, reg) scalars of a step without regularisation losses. ws: the
  * BatchNorm's workspace as for sbr_bn_score_bwd_stats (totals in ws[0 .. 2 D) afterwards, ready for sbr_bn_score_bwd_apply);
- * lws: sbr_bn_score_loss_workspace() bytes, zeroed ONCE by the caller and left zeroed by every call (calls that share it must not
- * overlap). kind / labels / scale / shift as for sbr_rec_loss_fwd_bwd. N <= D / 4 and N <= 16 (sbr_bn_score_loss_supported). */
+ * lws: sbr_bn_score_loss_workspace() bytes, zeroed ONCE by the caller; every call resets the arrival counter in its first word and
+ * overwrites the block partial sums behind it before it reads them (calls that share it must not overlap). kind / labels / scale / shift as for sbr_rec_loss_fwd_bwd. N <= D / 4 and N <= 16 (sbr_bn_score_loss_supported). */
 int sbr_bn_score_loss_supported(int D, int N);
 long sbr_bn_score_loss_workspace(void);
 int sbr_bn_score_loss_fwd_bwd(const float* Z, const float* U, const float* save_mean, const float* save_rstd, const float* weight,
@@ -346,7 +346,8 @@ int sbr_rec_loss_fwd_bwd(int kind, const float* logits, const double* labels, lo
                          double* loss_out, float* dlogits, void* stream);
 /* the same in ONE launch (new: the fused training step; sbr_rec_loss_fwd_bwd zeroes loss_out with a launch of its own and sums the
  * block partial sums with double atomics): the partial sums go through ws — sbr_rec_loss_workspace(B) bytes, zeroed ONCE by the
- * caller, left zeroed by every call; calls sharing a workspace must not overlap — and are added in block order (the same bits on
+ * caller; every call resets the arrival counter in its first word and overwrites the partial sums behind it before it reads them;
+ * calls sharing a workspace must not overlap — and are added in block order (the same bits on
  * every run). out3 (may be NULL): also writes (loss, loss, 0), the packed (total, rec, reg) scalars of a step without
  * regularisation losses (what sbr_pack_losses would produce). B >= 1. */
 long sbr_rec_loss_workspace(long B);

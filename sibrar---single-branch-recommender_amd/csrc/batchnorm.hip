@@ -30,13 +30,58 @@ __global__ void bn_stats_kernel(const float* __restrict__ X, long n, int D, doub
   }
 }
 
+// The geometry of sbr_col_reduce<2> (common.h: same row ranges per block, same replicas, same slots in deterministic mode), but the
+// squares are formed and both sums are carried in DOUBLE from the first addition: the finaliser takes var = ss / n - m * m, whose
+// cancellation multiplies every relative error of ss and of m by (mean / std)^2. With fp32 squares and fp32 per-thread sums the
+// variance of a column with mean / std = 256 was off by 5e-4 (numerical contract of the BatchNorm statistics); with
+// exact squares of fp32 values (24 + 24 bits fit a double) and double sums it is as good as the generic kernel's. The kernel
+// stays bound by its one read of X.
+__device__ __forceinline__ void bn_acc4(const float4 x, double* s, double* q) {
+  const double a = (double)x.x, b = (double)x.y, c = (double)x.z, d = (double)x.w;
+  s[0] += a; s[1] += b; s[2] += c; s[3] += d;
+  q[0] = fma(a, a, q[0]); q[1] = fma(b, b, q[1]); q[2] = fma(c, c, q[2]); q[3] = fma(d, d, q[3]);
+}
+
 __global__ __launch_bounds__(256) void bn_stats4_kernel(const float* __restrict__ X, long n, int D, double* __restrict__ ws,
                                                         double* __restrict__ slots) {
-  sbr_col_reduce<2>(n, D, ws, [&](long j, int cg, float4* v) {
-    const float4 x = *reinterpret_cast<const float4*>(X + j * D + 4 * cg);
-    v[0] = x;
-    v[1] = make_float4(x.x * x.x, x.y * x.y, x.z * x.z, x.w * x.w);
-  }, slots);
+  __shared__ double sm[2][4][256];
+  const int C4 = D >> 2, RL = 256 / C4;
+  const int t = threadIdx.x, cg = t % C4, rl = t / C4;
+  const long chunk = (n + gridDim.x - 1) / gridDim.x;
+  const long lo = blockIdx.x * chunk, hi = (lo + chunk < n) ? lo + chunk : n;
+  double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+  if (rl < RL) {
+    const float* xp = X + 4 * cg;
+    long j = lo + rl;
+    for (; j + 3L * RL < hi; j += 4L * RL) {       // four independent 16-byte loads in flight
+      const float4 x0 = *reinterpret_cast<const float4*>(xp + j * D), x1 = *reinterpret_cast<const float4*>(xp + (j + RL) * D),
+                   x2 = *reinterpret_cast<const float4*>(xp + (j + 2L * RL) * D), x3 = *reinterpret_cast<const float4*>(xp + (j + 3L * RL) * D);
+      bn_acc4(x0, s, q); bn_acc4(x1, s, q); bn_acc4(x2, s, q); bn_acc4(x3, s, q);
+    }
+    for (; j < hi; j += RL) bn_acc4(*reinterpret_cast<const float4*>(xp + j * D), s, q);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { sm[0][i][t] = s[i]; sm[1][i][t] = q[i]; }
+  __syncthreads();
+  if (t < C4) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      double o4[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        double a = 0.0;
+        for (int r = 0; r < RL; ++r) a += sm[k][i][r * C4 + t];
+        o4[i] = a;
+      }
+      if (slots) {               // deterministic mode: this block's own slot, plain stores (det.h: sbr_det_fold_slots adds the slots)
+        double* o = slots + (long)blockIdx.x * 2 * D + (long)k * D + 4 * t;
+        o[0] = o4[0]; o[1] = o4[1]; o[2] = o4[2]; o[3] = o4[3];
+        continue;
+      }
+      double* o = ws + (long)(1 + (blockIdx.x % SBR_COLRED_REP)) * 2 * D + (long)k * D + 4 * t;
+      atomicAdd(o, o4[0]); atomicAdd(o + 1, o4[1]); atomicAdd(o + 2, o4[2]); atomicAdd(o + 3, o4[3]);
+    }
+  }
 }
 
 // one thread per column: batch mean / rstd, running-stat update

@@ -112,6 +112,10 @@ static inline bool sbr_attr_stale(int* slot) {
 // Block = 256 threads = RL row lanes x (D/4) column groups (D <= 1024).
 // `slots` (deterministic mode, det.h): [gridDim.x][K*D] doubles — every block stores its sums in the slot of its own blockIdx
 // instead of adding them to a replica; nothing then depends on the order in which blocks finish.
+// batchnorm.hip: bn_stats4_kernel repeats this skeleton (row ranges, four-way unrolled loop + remainder loop, LDS fold, replica
+// choice, slot store) with DOUBLE accumulators from the first addition (its squares feed var = ss / n - m * m); a change of the
+// geometry, of the replica layout or of the slot layout here has to be made there too (sbr_col_reduce_blocks, sbr_colred_take and
+// det.h: sbr_det_fold_slots serve both).
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void sbr_f4_add(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 

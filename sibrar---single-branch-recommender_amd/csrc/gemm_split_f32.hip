@@ -194,7 +194,7 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
       if constexpr (KIND == 3) yp = g.Y + (m0 + 4 * half) * g.ldy + l31;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float ts = 0.f, tq = 0.f;
+        float ts = 0.f;
         float yv[16];
         if constexpr (KIND == 3) {
 #pragma unroll
@@ -215,7 +215,9 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
             if (FULL || lr < rows_left) ts += v;
           }
           if constexpr (EPI == 2) {
-            if (FULL || lr < rows_left) { ts += v; tq += v * v; }
+            // sums and squares in double from the first addition: the finaliser's var = sq / n - m * m multiplies their relative
+            // error by (mean / std)^2 (batchnorm.hip: bn_stats4_kernel; DESIGN.md, numerical contract of the BatchNorm statistics)
+            if (FULL || lr < rows_left) { const double dv = (double)v; cs[j] += dv; cq[j] = fma(dv, dv, cq[j]); }
           }
 #ifdef SP_ABL_NOSTORE       /* lab (timing only): the epilogue stores nothing */
           asm volatile("" ::"v"(v));
@@ -223,8 +225,7 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
           if (FULL || lr < rows_left) cp[(long)lr * g.ldc + j * 32] = v;
 #endif
         }
-        if constexpr (KIND == 3 || EPI == 2) cs[j] += (double)ts;
-        if constexpr (EPI == 2) cq[j] += (double)tq;
+        if constexpr (KIND == 3) cs[j] += (double)ts;
       }
     };
     using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>; using T2 = std::integral_constant<int, 2>;

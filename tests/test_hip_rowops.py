@@ -13,128 +13,17 @@ Conventions of this file
     its grid-stride loop twice (the caps are 4,096 blocks of 256 threads = 1,048,576 elements; 2,048 blocks x 16 rows for the
     D = 128 scatter-add; 8,192 blocks for the casts)."""
 import ctypes
-import importlib
 import math
 
 import numpy as np
 import pytest
 import torch
 
+from hip_testutil import (DEV, GUARD, NAN, U32, S, _L, _assert_bits, _assert_bound, _bits, _Buf, _dev, _i32, _i64, _orders, _p, _rand, _ulp,
+                          call, stream)
+
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
-U32 = 2.0 ** -24
-NAN = float('nan')
-GUARD = 64                                   # guard elements in front of and behind a view (a multiple of 4: keeps the alignment)
 DS = [1, 3, 4, 12, 16, 24, 64, 68, 96, 100, 128, 130, 256, 260, 300]
-
-
-def S():
-    import sibrar_amd
-    return sibrar_amd
-
-
-def _L():
-    return importlib.import_module(S().ops.__name__.rsplit('.', 1)[0] + '._lib')
-
-
-def call(name, *args):
-    _L().call(name, *args)
-    torch.cuda.synchronize()
-
-
-def stream():
-    return _L().stream()
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def _dev(t):
-    return None if t is None else t.to(DEV)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-class _Buf:
-    """A [rows, cols] fp32 view with row stride ld >= cols inside a NaN-filled flat buffer; ``off`` elements (4 bytes each) shift the
-    base pointer off the allocation's 16-byte boundary."""
-
-    def __init__(self, rows, cols, ld=None, off=0, data=None, fill=None, dtype=torch.float32):
-        self.rows, self.cols, self.ld, self.off = rows, cols, ld or cols, off
-        assert self.ld >= cols
-        self.flat = torch.full((GUARD + off + rows * self.ld + GUARD,), NAN, device=DEV, dtype=dtype)
-        self.t = self._view(self.flat)
-        assert (self.t.data_ptr() - self.flat.data_ptr()) == (GUARD + off) * self.flat.element_size()
-        if data is not None:
-            self.t.copy_(data.to(DEV))
-        elif fill is not None:
-            self.t.fill_(fill)
-
-    def _view(self, flat):
-        return flat[GUARD + self.off: GUARD + self.off + self.rows * self.ld].view(self.rows, self.ld)[:, :self.cols]
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def host(self):
-        return self.t.cpu()
-
-    def check_untouched(self, written_rows=None, what=''):
-        """every element outside [written_rows, :cols] still holds the NaN pattern; -> the view on the host"""
-        host = self.flat.cpu()
-        may = torch.zeros(host.shape, dtype=torch.bool)
-        mv = self._view(may)
-        if written_rows is None:
-            mv[:] = True
-        else:
-            mv[written_rows] = True
-        assert bool(torch.isnan(host[~may]).all()), f'{what}: {int((~torch.isnan(host[~may])).sum())} elements outside the addressed rows / columns were written'
-        return self._view(host)
-
-
-def _i32(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.int32).to(DEV)
-
-
-def _i64(x):
-    return torch.as_tensor(np.asarray(x), dtype=torch.int64).to(DEV)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _assert_bits(got, ref, what=''):
-    assert got.shape == ref.shape, what
-    bad = _bits(got) != _bits(ref)
-    assert not bool(bad.any()), f'{what}: {int(bad.sum())} of {bad.numel()} elements differ in bits'
-
-
-def _assert_bound(got, ref, bound, what=''):
-    """|got - ref| <= bound elementwise (float64); NaN anywhere fails"""
-    err = (got.double() - ref).abs()
-    bad = ~(err <= bound)
-    assert not bool(bad.any()), (f'{what}: {int(bad.sum())} of {bad.numel()} elements over the bound, worst err {float(err[bad].max()):.3e} '
-                                 f'at bound {float(bound[bad][err[bad].argmax()]):.3e}')
-
-
-def _ulp(x):
-    """spacing of fp32 at |x| (float64 tensor)"""
-    x = x.abs().double().clamp_min(2.0 ** -126)
-    return torch.exp2(torch.floor(torch.log2(x)) - 23)
-
-
-def _orders(n, n_table, seed, hot=None):
-    """index lists with heavy duplication in random, sorted and reversed order; ``hot``: one row named by > 1,000 sources (if n allows)"""
-    rng = np.random.default_rng(seed)
-    r = rng.integers(0, n_table, size=n)
-    if hot is not None and n >= 1500:
-        r[rng.choice(n, size=1200, replace=False)] = hot
-    return {'random': r, 'sorted': np.sort(r), 'reversed': np.sort(r)[::-1].copy()}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
