@@ -428,7 +428,9 @@ int sbr_merge_topk(const float* vals, const int* idxs, int W, long Bu, int k, fl
 int sbr_rank_metrics(const int* topk_idx, int kmax, const long* u_idx, const long* label_indptr, const int* label_indices,
                      long Bu, const int* ks, int n_ks, float* out, void* stream);
 /* fused scorer: fp16 MFMA  U[Bu, D] x I[I_s, D]^T  with the exclusion mask and the running per-user top-k kept on chip; the
- * [Bu, I_s] score matrix is never written (BASELINE config 5). D in {64, 128, 256}, k <= 32. Output sorted by (score desc, item
+ * [Bu, I_s] score matrix is never written (BASELINE config 5). D in {64, 128, 256}, 1 <= k <= 128 (k > 32 runs the wide
+ * instantiation of the one-pass kernel: same contract, same score bits; the two-pass route takes k <= 32 only and answers a longer
+ * list with an error). Output sorted by (score desc, item
  * index asc); indices are global (item_offset + column). u_idx: exclusion-CSR row of every scored row (NULL: identity).
  * excl_nnz: number of entries of `excl_indices` (an upper bound of the exclusions of the scored rows).
  * Exclusions reach the kernel as an EVENT STREAM built from the CSR rows (csrc/score_topk_f16_n.hip) in the caller-owned buffer
@@ -457,7 +459,8 @@ int sbr_cast_f32_to_f16(const float* X, void* Y_f16, long n, void* stream);
 /* fused scorer with fp32-class products (eval/eval.py:216-222: einsum('be,ce->bc') in fp32, -inf on the exclusions, top-k): the
  * contract of sbr_score_topk_f16 (output order, global indices, u_idx, (-inf, -1) padding, event-buffer protocol) on fp32 user rows
  * U_f32 [Bu, D] and the three bf16 planes of the item matrix (sbr_split_f32_to_bf16x3), multiplied on the bf16 matrix pipe as the six
- * leading partial products of the exact splits with fp32 accumulation (csrc/score_topk_f32s.hip). D in {64, 128}, k <= 32. The event
+ * leading partial products of the exact splits with fp32 accumulation (csrc/score_topk_f32s.hip). D in {64, 128}, 1 <= k <= 128
+ * (k > 32: the wide instantiation). The event
  * buffer has sbr_score_topk_f16_events_bytes(Bu, excl_nnz) bytes, but the stream in it is laid out for this kernel's 32-item tiles:
  * a buffer built by sbr_score_topk_f16 must not be passed with build_events = 0, nor the other way round. New (additive to ABI 4). */
 int sbr_score_topk_f32s(const float* U_f32, const void* I_bf16x3, int D, long Bu, int I, const long* u_idx,

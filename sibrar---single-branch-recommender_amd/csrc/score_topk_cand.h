@@ -72,6 +72,61 @@ __device__ __forceinline__ float s5_overflow_select(unsigned long long* b0, unsi
   return t == t ? t : -INFINITY;
 }
 
+// The same selection for the WIDE instantiations (33 <= k <= 128), where it is the steady mechanism and not a rare event: the appends'
+// threshold of a wide list is the exact k-th best score of the user's buffered entries, renewed whenever a buffer half passes the
+// limit (a user's 32 class maxima bound nothing beyond k = 32). The user's entries are read ONCE (2 x S5_EH raw entries per lane:
+// the accumulators are dead at this point of the tile loop, so the registers are there) and the search runs on registers: up to 32
+// rounds over the 32-bit score keys, and 32 more over the item words only when the k-th score is tied. Same result, same survivor
+// layout and same return value as s5_overflow_select.
+__device__ __forceinline__ float s5_overflow_select_held(unsigned long long* b0, unsigned long long* b1, int n0_any, int n1_any, int k, int lane) {
+  const int n0 = __builtin_amdgcn_readfirstlane(n0_any), n1 = __builtin_amdgcn_readfirstlane(n1_any);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");     // written and read by this wave only
+  if (n0 + n1 < k) return -INFINITY;
+  unsigned long long raw[2 * S5_EH];
+#pragma unroll
+  for (int j = 0; j < 2 * S5_EH; ++j) {
+    const int hh = j / S5_EH, q = (j % S5_EH) * 64 + lane;
+    raw[j] = q < (hh ? n1 : n0) ? (hh ? b1 : b0)[q] : 0ull;
+  }
+  unsigned int sk[2 * S5_EH];                                // score key; 0 for an empty slot (no trial value is 0)
+#pragma unroll
+  for (int j = 0; j < 2 * S5_EH; ++j) sk[j] = raw[j] ? st_f2key(__uint_as_float((unsigned int)(raw[j] >> 32))) : 0u;
+  unsigned int T = 0u;
+  int c_ge = n0 + n1;
+  for (int bit = 31; bit >= 0; --bit) {
+    const unsigned int trial = T | (1u << bit);
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 2 * S5_EH; ++j) cnt += __popcll(__ballot(sk[j] >= trial));
+    if (cnt >= k) { T = trial; c_ge = cnt; if (cnt == k) break; }
+  }
+  unsigned int Lw = 0u;                                      // ties at the k-th score keep the smallest item indices (largest ~item)
+  if (c_ge != k) {
+    int above = 0;
+#pragma unroll
+    for (int j = 0; j < 2 * S5_EH; ++j) above += __popcll(__ballot(sk[j] > T));
+    for (int bit = 31; bit >= 0; --bit) {
+      const unsigned int trial = Lw | (1u << bit);
+      int cnt = above;
+#pragma unroll
+      for (int j = 0; j < 2 * S5_EH; ++j) cnt += __popcll(__ballot(sk[j] == T && (unsigned int)raw[j] >= trial));
+      Lw = cnt >= k ? trial : Lw;
+    }
+  }
+  const int kh = k - (k >> 1);
+  int before = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * S5_EH; ++j) {                      // every entry is in registers: the survivors may land anywhere
+    const bool keep = sk[j] > T || (sk[j] == T && sk[j] != 0u && (unsigned int)raw[j] >= Lw);
+    const unsigned long long m = __ballot(keep);
+    const int p = before + (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+    if (keep && p < k) (p < kh ? b0 + p : b1 + (p - kh))[0] = raw[j];
+    before += __popcll(m);
+  }
+  const float t = st_key2f(T);
+  return t == t ? t : -INFINITY;
+}
+
 // append of one raw candidate entry at byte offset `pos` of the wave's buffer block (`block`: wave-uniform, so the descriptor is
 // four SGPRs the compiler builds once per kernel): buffer_store_dwordx2 v[ent], v[pos], s[rsrc], 0 offen
 __device__ __forceinline__ void s5_append(unsigned long long* block, int pos, u32x2 ent) {
@@ -149,10 +204,14 @@ __device__ __forceinline__ i32x4 s5_block_rsrc(const void* block) {
 // lanes of rank < k write the output. More than 64 survivors (ties at the threshold, a threshold that never rose): a bitwise binary
 // search over ballot counts (entries re-read per round: cold) finds the k-th largest composite key first and exactly k survive.
 // Empty slots (-inf, -1) behind fewer than k candidates.
+// WIDE (33 <= k <= 128): the appends' threshold is the k-th best score at the user's LAST overflow selection, so nearly everything
+// buffered since passes the filter (up to 2 x 240 entries of a full wave's user) — the staging area takes 512 survivors, the k best of
+// them are cut out by the register search and ranked two per lane.
+template <bool WIDE>
 __device__ __forceinline__ void s5_finalize(long Bu, int k, long n_full_units, int P, const int* __restrict__ cnt,
                                             const unsigned long long* __restrict__ gbuf, float* __restrict__ out_val,
                                             int* __restrict__ out_idx) {
-  constexpr int CAP = 256;                                   // survivors a wave can stage in LDS
+  constexpr int CAP = WIDE ? 512 : 256;                      // survivors a wave can stage in LDS
   __shared__ unsigned long long stage[4][CAP];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long ur = (long)blockIdx.x * 4 + w;
@@ -226,6 +285,74 @@ __device__ __forceinline__ void s5_finalize(long Bu, int k, long n_full_units, i
     for_chunks(gather);
   }
   st_wave_fence();                                           // LDS operations of a wave execute in order
+  if constexpr (WIDE) {
+    // up to CAP survivors, CAP / 64 per lane as composite keys; more than 128 of them: exactly k survive the cut at the k-th largest key
+    unsigned long long e8[CAP / 64];
+#pragma unroll
+    for (int q = 0; q < CAP / 64; ++q) e8[q] = key_of(q * 64 + lane < n ? stage[w][q * 64 + lane] : 0ull);
+    unsigned long long kcut = 0ull;
+    if (n > 128) {
+      auto count_ge = [&](unsigned long long C) {
+        int cn = 0;
+#pragma unroll
+        for (int q = 0; q < CAP / 64; ++q) cn += __popcll(__ballot(e8[q] >= C));
+        return cn;
+      };
+      unsigned int T = 0u;
+      int c_ge = 1 << 30;
+      for (int bit = 31; bit >= 0; --bit) {
+        const unsigned int trial = T | (1u << bit);
+        const int cn = count_ge((unsigned long long)trial << 32);
+        if (cn >= k) { T = trial; c_ge = cn; if (cn == k) break; }
+      }
+      kcut = (unsigned long long)T << 32;
+      if (c_ge != k) {
+        unsigned int Lw = 0u;
+        for (int bit = 31; bit >= 0; --bit) {
+          const unsigned int trial = Lw | (1u << bit);
+          Lw = count_ge(((unsigned long long)T << 32) | trial) >= k ? trial : Lw;
+        }
+        kcut |= (unsigned long long)Lw;
+      }
+    }
+    st_wave_fence();
+    n = 0;
+#pragma unroll
+    for (int q = 0; q < CAP / 64; ++q) {
+      const bool keep = e8[q] >= kcut && e8[q] != 0ull;
+      const unsigned long long m = __ballot(keep);
+      const int p = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+      if (keep && p < 128) stage[w][p] = e8[q];
+      n += __popcll(m);
+    }
+    n = n < 128 ? n : 128;
+    st_wave_fence();
+    // two survivors per lane, ranked by counting (composite keys are distinct: rank = number of larger keys)
+    const unsigned long long ea = lane < n ? stage[w][lane] : 0ull, eb = lane + 64 < n ? stage[w][lane + 64] : 0ull;
+    int ra = 0, rb = 0;
+    for (int j = 0; j < n; ++j) {
+      const unsigned long long kj = stage[w][j];             // wave-uniform address: an LDS broadcast
+      ra += kj > ea;
+      rb += kj > eb;
+    }
+    if (lane < n && ra < k) {
+      out_val[ur * k + ra] = st_key2f((unsigned int)(ea >> 32));
+      out_idx[ur * k + ra] = (int)(0xFFFFFFFFu - (unsigned int)(ea & 0xFFFFFFFFull));
+    }
+    if (lane + 64 < n && rb < k) {
+      out_val[ur * k + rb] = st_key2f((unsigned int)(eb >> 32));
+      out_idx[ur * k + rb] = (int)(0xFFFFFFFFu - (unsigned int)(eb & 0xFFFFFFFFull));
+    }
+    const int nkw = n < k ? n : k;
+#pragma unroll
+    for (int p = lane; p < 128; p += 64) {                   // fewer than k candidates: empty slots behind them, positions >= 64 included
+      if (p >= nkw && p < k) {
+        out_val[ur * k + p] = -INFINITY;
+        out_idx[ur * k + p] = -1;
+      }
+    }
+    return;
+  }
   unsigned long long e;
   if (n <= 64) {
     e = key_of(lane < n ? stage[w][lane] : 0ull);

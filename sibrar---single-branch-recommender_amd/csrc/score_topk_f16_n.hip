@@ -42,11 +42,26 @@ __global__ __launch_bounds__(1024) void score_topk_f16_n_kernel(
   st_one_pass<StF16<KS, NJ>, NS>(U, It, Bu, I, events, group_base, item_offset, k, n_pre, W, n_part, P, cnt_out, gbuf);
 }
 
+// the wide instantiation (33 <= k <= 128, st_one_pass<..., WIDE>): a kernel of its own, chosen on the host by k > 32 — the kernel above is
+// what it was before wide lists existed
+template <int KS, int NS, int NJ>
+__global__ __launch_bounds__(1024) void score_topk_wide_f16_kernel(
+    const _Float16* __restrict__ U, const _Float16* __restrict__ It, long Bu, int I, const unsigned int* __restrict__ events,
+    const int* __restrict__ group_base, int item_offset, int k, int n_pre, int W, int n_part, int P,
+    int* __restrict__ cnt_out, unsigned long long* __restrict__ gbuf) {
+  st_one_pass<StF16<KS, NJ>, NS, true>(U, It, Bu, I, events, group_base, item_offset, k, n_pre, W, n_part, P, cnt_out, gbuf);
+}
+
 // final selection of the one-pass kernels' candidate buffers (s5_finalize, score_topk_cand.h), for both routes
 __global__ __launch_bounds__(256) void score_topk_finalize_kernel(long Bu, int k, long n_full_units, int P, const int* __restrict__ cnt,
                                                                   const unsigned long long* __restrict__ gbuf, float* __restrict__ out_val,
                                                                   int* __restrict__ out_idx) {
-  s5_finalize(Bu, k, n_full_units, P, cnt, gbuf, out_val, out_idx);
+  s5_finalize<false>(Bu, k, n_full_units, P, cnt, gbuf, out_val, out_idx);
+}
+__global__ __launch_bounds__(256) void score_topk_rank_wide_kernel(long Bu, int k, long n_full_units, int P, const int* __restrict__ cnt,
+                                                                       const unsigned long long* __restrict__ gbuf, float* __restrict__ out_val,
+                                                                       int* __restrict__ out_idx) {
+  s5_finalize<true>(Bu, k, n_full_units, P, cnt, gbuf, out_val, out_idx);
 }
 
 extern "C" long sbr_score_topk_f16_events_bytes(long Bu, long excl_nnz) { return s5_event_bytes(Bu, excl_nnz); }
@@ -55,6 +70,10 @@ template <int KS, int NS, int NJ>
 static int s5_launch(const void* U, const void* It, long Bu, int I, const long* u_idx, const long* eptr, const int* eidx, long excl_nnz,
                      int item_offset, int k, float* out_val, int* out_idx, void* workspace, long workspace_bytes, void* ev_buf,
                      long ev_bytes, int build_events, hipStream_t s) {
+  if (k > 32)                                                // the wide instantiation: lists of 33 .. 128
+    return st_launch<StF16<KS, NJ>, NS, true>(score_topk_wide_f16_kernel<KS, NS, NJ>, "sbr_score_topk_f16", (const _Float16*)U,
+                                              (const _Float16*)It, Bu, I, u_idx, eptr, eidx, excl_nnz, item_offset, k, out_val, out_idx, workspace,
+                                              workspace_bytes, ev_buf, ev_bytes, build_events, s);
   return st_launch<StF16<KS, NJ>, NS>(score_topk_f16_n_kernel<KS, NS, NJ>, "sbr_score_topk_f16", (const _Float16*)U, (const _Float16*)It, Bu, I,
                                       u_idx, eptr, eidx, excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, ev_buf,
                                       ev_bytes, build_events, s);
@@ -82,7 +101,7 @@ int s2_dispatch(const void* U, const void* It, int D, long Bu, int I, const long
                 int build_events, hipStream_t s);
 
 // 0: automatic (the one-pass kernel for every shape until the two-pass scorer is the faster one), 1: always the one-pass kernel,
-// 2: two-pass (catalogues of >= 8,192 items) or an error.
+// 2: two-pass (catalogues of >= 8,192 items, k <= 32) or an error.
 // Both routes return the same lists bit for bit; the switch exists for tests and A/B timing.
 static int g_route = 0;
 extern "C" int sbr_score_topk_f16_route(int route) {
@@ -108,12 +127,13 @@ extern "C" int sbr_score_topk_f16(const void* U_f16, const void* I_f16, int D, l
                                   const long* excl_indptr, const int* excl_indices, long excl_nnz, int item_offset, int k, float* out_val,
                                   int* out_idx, void* workspace, long workspace_bytes, void* events, long events_bytes, int build_events,
                                   void* stream) {
-  SBR_REQUIRE(k >= 1 && k <= 32, "sbr_score_topk_f16: k=%d outside [1, 32] (use sbr_gemm_f32 + sbr_topk_rows)", k);
+  SBR_REQUIRE(k >= 1 && k <= 128, "sbr_score_topk_f16: k=%d outside [1, 128] (use sbr_gemm_f32 + sbr_topk_rows)", k);
   SBR_REQUIRE(I >= 1, "sbr_score_topk_f16: empty catalogue");
   if (Bu == 0) return SBR_OK;
   SBR_REQUIRE(U_f16 && I_f16 && out_val && out_idx, "sbr_score_topk_f16: null operand");
   SBR_REQUIRE((excl_indptr == nullptr) == (excl_indices == nullptr), "sbr_score_topk_f16: exclusion CSR must be given whole or not at all");
   SBR_REQUIRE(D == 64 || D == 128 || D == 256, "sbr_score_topk_f16: D=%d not supported (64, 128, 256)", D);
+  SBR_REQUIRE(g_route != 2 || k <= 32, "sbr_score_topk_f16: the two-pass route takes k <= 32 (k=%d); select route 0 or 1 for longer lists", k);
   const bool two = s2_supported(D, Bu, I, k);
   SBR_REQUIRE(g_route != 2 || two, "sbr_score_topk_f16: the two-pass route was requested for a shape it does not take (I=%d)", I);
   if (two && g_route == 2)      // (checkpoint: the automatic route stays on the one-pass kernel until the two-pass scorer is the faster one)

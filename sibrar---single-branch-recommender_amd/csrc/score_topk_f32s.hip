@@ -76,6 +76,15 @@ __global__ __launch_bounds__(512) void score_topk_f32s_kernel(
   st_one_pass<StF32s<KS>, NS>(U, It, Bu, I, events, group_base, item_offset, k, n_pre, W, n_part, P, cnt_out, gbuf);
 }
 
+// the wide instantiation (33 <= k <= 128, st_one_pass<..., WIDE>): a kernel of its own, chosen on the host by k > 32
+template <int KS, int NS>
+__global__ __launch_bounds__(512) void score_topk_wide_f32s_kernel(
+    const float* __restrict__ U, const __bf16* __restrict__ It, long Bu, int I, const unsigned int* __restrict__ events,
+    const int* __restrict__ group_base, int item_offset, int k, int n_pre, int W, int n_part, int P,
+    int* __restrict__ cnt_out, unsigned long long* __restrict__ gbuf) {
+  st_one_pass<StF32s<KS>, NS, true>(U, It, Bu, I, events, group_base, item_offset, k, n_pre, W, n_part, P, cnt_out, gbuf);
+}
+
 extern "C" long sbr_score_topk_f32s_workspace(long Bu, int I, int k) {
   (void)I; (void)k;
   return st_workspace_bytes(Bu, F3_MAXW);
@@ -88,7 +97,7 @@ extern "C" int sbr_score_topk_f32s(const float* U, const void* I_bf16x3, int D, 
                                    const long* excl_indptr, const int* excl_indices, long excl_nnz, int item_offset, int k, float* out_val,
                                    int* out_idx, void* workspace, long workspace_bytes, void* events, long events_bytes, int build_events,
                                    void* stream) {
-  SBR_REQUIRE(k >= 1 && k <= 32, "sbr_score_topk_f32s: k=%d outside [1, 32] (use sbr_gemm_f32 + sbr_topk_rows)", k);
+  SBR_REQUIRE(k >= 1 && k <= 128, "sbr_score_topk_f32s: k=%d outside [1, 128] (use sbr_gemm_f32 + sbr_topk_rows)", k);
   SBR_REQUIRE(I >= 1, "sbr_score_topk_f32s: empty catalogue");
   SBR_REQUIRE(D == 64 || D == 128, "sbr_score_topk_f32s: D=%d not supported (64, 128)", D);
   if (Bu == 0) return SBR_OK;
@@ -97,6 +106,13 @@ extern "C" int sbr_score_topk_f32s(const float* U, const void* I_bf16x3, int D, 
   SBR_REQUIRE((excl_indptr == nullptr) == (excl_indices == nullptr), "sbr_score_topk_f32s: exclusion CSR must be given whole or not at all");
   const hipStream_t s = (hipStream_t)stream;
   const __bf16* It = (const __bf16*)I_bf16x3;
+  if (k > 32) {                                              // the wide instantiations: lists of 33 .. 128
+    if (D == 64)
+      return st_launch<StF32s<4>, 12, true>(score_topk_wide_f32s_kernel<4, 12>, "sbr_score_topk_f32s", U, It, Bu, I, u_idx, excl_indptr, excl_indices,
+                                            excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, events, events_bytes, build_events, s);
+    return st_launch<StF32s<8>, 6, true>(score_topk_wide_f32s_kernel<8, 6>, "sbr_score_topk_f32s", U, It, Bu, I, u_idx, excl_indptr, excl_indices,
+                                         excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, events, events_bytes, build_events, s);
+  }
   if (D == 64)
     return st_launch<StF32s<4>, 12>(score_topk_f32s_kernel<4, 12>, "sbr_score_topk_f32s", U, It, Bu, I, u_idx, excl_indptr, excl_indices,
                                     excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, events, events_bytes, build_events, s);

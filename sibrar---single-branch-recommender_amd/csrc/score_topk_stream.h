@@ -254,7 +254,14 @@ struct StF16 {
 
 // ---- the one-pass consumer (see the header of score_topk_f16_n.hip). Lane (u, h) holds for ONE user the scores of 16 items of every
 // 32-item tile; its threshold and its byte cursor into the user's buffer half h (the thresholds of the two halves of a user are equal).
-template <class Pol, int NS>
+// WIDE (33 <= k <= 128, chosen on the host): a separate instantiation, the k <= 32 one is compiled from the same text as before.
+// A user's 32 class maxima bound the k-th best score only while k <= 32, so the wide form has no prefix pass and no class-maxima
+// refresh: its threshold is the exact k-th best score of the user's BUFFERED entries, taken whenever a buffer half passes LIMIT
+// (s5_overflow_select_held). That is k distinct, scoreable, already-seen items at or above it, all with smaller indices than any later
+// item, so the appends' rule (a > thr) stays valid. It starts at -inf: the first 2 LIMIT / 32 tiles are appended whole and the first
+// selection is the bootstrap; with a fixed threshold the k-th of n items lets k / n of the stream through, so every selection
+// multiplies the items seen by about 1 + (2 LIMIT - k) / k and a 50k catalogue takes four or five selections per user.
+template <class Pol, int NS, bool WIDE = false>
 __device__ __forceinline__ void st_one_pass(const typename Pol::UT* U, const typename Pol::IT* It, long Bu, int I, const unsigned int* events,
                                             const int* group_base, int item_offset, int k, int n_pre, int W, int n_part, int P,
                                             int* cnt_out, unsigned long long* gbuf) {
@@ -264,6 +271,8 @@ __device__ __forceinline__ void st_one_pass(const typename Pol::UT* U, const typ
   constexpr int LIMIT = S5_CAPH - 16 * NJ;                 // a tile adds at most 16 NJ entries to a (user, half) buffer
   constexpr int TILEB = Pol::PLANES * ST_TILE * D * 2;
   static_assert(LIMIT >= 32, "k <= 32 entries must fit below the compaction limit");
+  // wide lists: a half over LIMIT holds k entries by itself, and the survivors of a selection (at most 64 per half) leave a tile's room
+  static_assert(!WIDE || (LIMIT >= 128 && 64 + 16 * NJ <= LIMIT), "k <= 128: survivors split over both halves must leave room below LIMIT");
   constexpr bool CML = KS >= S5_CML_KS;                    // class maxima of the main pass in LDS instead of registers
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   lds_int* full_lds = (lds_int*)(smem + NS * TILEB);
@@ -338,7 +347,7 @@ __device__ __forceinline__ void st_one_pass(const typename Pol::UT* U, const typ
   if (un.partial) {
     for (int v = 0; v < n_pre; ++v) skip(v, v * ST_TILE);
     ev.restart();
-  } else if (n_pre > 0) {
+  } else if (!WIDE && n_pre > 0) {
     for (int v = 0; v < n_pre; ++v) {
       const int j0 = v * ST_TILE;
       f32x16 acc[NJ];
@@ -403,7 +412,9 @@ __device__ __forceinline__ void st_one_pass(const typename Pol::UT* U, const typ
         need &= need - 1ull;
         const int c0 = __builtin_amdgcn_readlane(cnt, u), c1 = __builtin_amdgcn_readlane(cnt, u + 32);
         unsigned long long* b0 = wgb + (long)u * (2 * S5_CAPH);
-        const float nt = s5_overflow_select(b0, b0 + S5_CAPH, c0, c1, k, lane);
+        float nt;
+        if constexpr (WIDE) nt = s5_overflow_select_held(b0, b0 + S5_CAPH, c0, c1, k, lane);
+        else nt = s5_overflow_select(b0, b0 + S5_CAPH, c0, c1, k, lane);
         if (c0 + c1 >= k && l31 == u) {
           thr = nt > thr ? nt : thr;
           pos = lane_base + (half ? (k >> 1) : k - (k >> 1)) * 8;
@@ -446,7 +457,7 @@ __device__ __forceinline__ void st_one_pass(const typename Pol::UT* U, const typ
       }
 #undef ST_PAIR
     }
-    if (tl >= next_rf) {
+    if (!WIDE && tl >= next_rf) {
       // every later item has a larger index than the k buffered items at or above the bound: it needs a strictly larger score
       if constexpr (CML) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's ds_max updates have been performed
@@ -474,6 +485,9 @@ __device__ __forceinline__ void st_one_pass(const typename Pol::UT* U, const typ
 // final selection of the one-pass kernels' candidate buffers (s5_finalize, score_topk_cand.h); defined in score_topk_f16_n.hip
 __global__ void score_topk_finalize_kernel(long Bu, int k, long n_full_units, int P, const int* __restrict__ cnt,
                                            const unsigned long long* __restrict__ gbuf, float* __restrict__ out_val, int* __restrict__ out_idx);
+// ... of the wide instantiations (33 <= k <= 128)
+__global__ void score_topk_rank_wide_kernel(long Bu, int k, long n_full_units, int P, const int* __restrict__ cnt,
+                                            const unsigned long long* __restrict__ gbuf, float* __restrict__ out_val, int* __restrict__ out_idx);
 
 // whole units + the last workgroup's padding + one row group per partial wave
 static long st_padded_users(long Bu, int maxw) { return sbr_cdiv(Bu, 32) * 32 + 32L * maxw + 32L * s5_n_cu(); }
@@ -485,7 +499,7 @@ static long st_workspace_bytes(long Bu, int maxw) {
 
 // kern: the route's instantiation of its one-pass kernel (the st_one_pass signature with the route's operand types); what: the C entry,
 // for messages
-template <class Pol, int NS, typename UT, typename IT>
+template <class Pol, int NS, bool WIDE = false, typename UT, typename IT>
 static int st_launch(void (*kern)(const UT*, const IT*, long, int, const unsigned int*, const int*, int, int, int, int, int, int, int*, unsigned long long*),
                      const char* what, const UT* U, const IT* It, long Bu, int I, const long* u_idx, const long* eptr, const int* eidx,
                      long excl_nnz, int item_offset, int k, float* out_val, int* out_idx, void* workspace, long workspace_bytes, void* ev_buf,
@@ -514,7 +528,7 @@ static int st_launch(void (*kern)(const UT*, const IT*, long, int, const unsigne
   // tiles (every score passes a threshold of -inf), at the price of scoring those tiles twice (fp16 route, measured on c2: 0 tiles
   // 1.76 ms, 8: 1.59, 16: 1.54, 32: 1.55, 65: 1.58)
   const int n_tiles = sbr_cdiv(I, 32 * NJ);
-  const int n_pre = n_tiles >= 6 * Pol::PRE_TILES ? Pol::PRE_TILES : 0;
+  const int n_pre = !WIDE && n_tiles >= 6 * Pol::PRE_TILES ? Pol::PRE_TILES : 0;      // (wide lists bootstrap from their first selection)
   if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     sbr_set_error("%s: cannot raise the dynamic LDS limit to %zu", what, lds);
     return SBR_ERR_HIP;
@@ -525,8 +539,8 @@ static int st_launch(void (*kern)(const UT*, const IT*, long, int, const unsigne
   SBR_CHECK_LAUNCH(what);
   char fin[64];
   snprintf(fin, sizeof fin, "%s (final selection)", what);
-  score_topk_finalize_kernel<<<(unsigned int)sbr_cdiv(Bu, 4), 256, 0, s>>>(Bu, k, plan.n_part > 0 ? (long)n_wg * W : (1L << 40), plan.P, cnt,
-                                                                            (const unsigned long long*)workspace, out_val, out_idx);
+  (WIDE ? score_topk_rank_wide_kernel : score_topk_finalize_kernel)<<<(unsigned int)sbr_cdiv(Bu, 4), 256, 0, s>>>(
+      Bu, k, plan.n_part > 0 ? (long)n_wg * W : (1L << 40), plan.P, cnt, (const unsigned long long*)workspace, out_val, out_idx);
   SBR_CHECK_LAUNCH(fin);
   return SBR_OK;
 }

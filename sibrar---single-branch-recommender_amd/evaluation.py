@@ -8,14 +8,19 @@ Here the exclusion CSR and the label CSR are resident on the device; per user ba
   * ``scorer='fp16_fused'``: the fused fp16-MFMA score+mask+top-k kernel (scores never written), or
   * ``scorer='fp32_fused'``: the same fusion with fp32-class products (fp32 user rows and the item matrix split once into three
     exact bf16 planes, six bf16-MFMA partial products per score, fp32 accumulation): the fp32 route's ranking without its score
-    matrix; k <= 32, D in {64, 128} and finite item values, anything else falls back to ``'fp32'``,
+    matrix; D in {64, 128} and finite item values, anything else falls back to ``'fp32'``,
+both fused routes for lists up to ``fused_max_k`` entries (default 32; up to 128 on request: the wide kernels), longer ones fall back,
 followed by the ranking-metric kernel (NDCG / recall / precision as defined in eval/metrics.py:4-105; ``rmet`` itself is
 absent offline, so w.r.t. ``rmet`` the metric arithmetic is parity-unpinned). ``eval_batch`` keeps the reference's
 dense-logits entry point for callers that already hold a score matrix.
+
+``gather_recommender_algorithm_results`` / ``Gatherer`` (eval/eval.py:230-333) dump the per-user top-``max(top_k)`` lists next to the
+metrics; they run the same scoring loop as the evaluation.
 """
 from __future__ import annotations
 
 import logging
+import pickle
 import re
 from collections import defaultdict
 from typing import Optional, Sequence
@@ -244,8 +249,13 @@ class FullEvaluator:
 
 
 def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, device='cuda', return_raw=False, verbose=False,
-                                   scorer: str = 'fp32', user_chunk: Optional[int] = None, shard_items: bool = False):
+                                   scorer: str = 'fp32', user_chunk: Optional[int] = None, shard_items: bool = False,
+                                   fused_max_k: int = 32):
     """eval/eval.py:171-227 (SGD branch :203-222). ``eval_loader`` only has to expose ``dataset`` and ``batch_size``.
+
+    ``fused_max_k`` (32 .. 128, anything else raises ValueError): the longest list the fused routes may serve. With the default an
+    evaluation whose largest cut-off is above 32 takes the fp32 route, as it always did; with 128 it stays on the requested fused route
+    (the wide kernels) up to a largest cut-off of 128.
 
     The users are scored in engine-sized chunks, not in the loader's batches: per-user results do not depend on the grouping,
     and the reference's default evaluation batch (256 users) leaves the GPU idle — the fused kernel assigns 448 users to a workgroup and every workgroup streams the whole catalogue, so they want >= 57k users per launch (measured on
@@ -260,6 +270,15 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
     lists are all-gathered and merged exactly (``parallel.all_gather_topk`` -> ``sbr_merge_topk``: score desc, index asc), and every
     rank feeds the merged lists to its evaluator — all ranks return the same metrics as a one-rank evaluation. Models whose item side
     is more than one matrix (biases) score unsharded on every rank."""
+    fused_max_k = ops.check_fused_max_k(fused_max_k)
+    _score_split(alg, eval_loader, evaluator, device, scorer, user_chunk, shard_items, fused_max_k, None)
+    return evaluator.get_results(return_raw_results=return_raw)
+
+
+def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, user_chunk, shard_items, fused_max_k, sink):
+    """The scoring loop of ``evaluate_recommender_algorithm`` and ``gather_recommender_algorithm_results``: every user chunk's top-k
+    lists go to the evaluator and, when given, to ``sink(first row of the chunk, u_idxs, scores [Bu, k], item positions [Bu, k])``.
+    Returns the list length k = min(max(top_k), items in the split)."""
     dataset = eval_loader.dataset
     for attr in ('items_in_split', 'users_in_split', 'exclude_data'):
         if not hasattr(dataset, attr):
@@ -305,15 +324,15 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
         bs = int(getattr(eval_loader, 'batch_size', 256) or 256)
         if scorer not in ('fp32', 'fp16_fused', 'fp32_fused'):
             raise ValueError(f'unknown scorer {scorer!r}')
-        # the fused routes: (shape the kernel takes (D, k), item operand made once per call, user operand made per chunk, call).
-        # fp16_fused keeps at most 32 candidates per user on chip and is built for D in {64, 128, 256}; fp32_fused also keeps 32 and is
-        # built for D in {64, 128} (the user planes of D = 256 do not fit its registers). Everything else — larger cut-offs (the
-        # reference's default evaluator asks for top-100), tuple item sides — takes the exact fp32 GEMM + radix-select path.
+        # the fused routes: (item operand made once per call, user operand made per chunk, call). fp16_fused is built for D in
+        # {64, 128, 256}, fp32_fused for D in {64, 128} (the user planes of D = 256 do not fit its registers); both serve lists up to
+        # fused_max_k entries (ops.score_topk_fused_supported). Everything else — larger cut-offs (the reference's default evaluator
+        # asks for top-100: fused only with fused_max_k >= 100), tuple item sides — takes the exact fp32 GEMM + radix-select path.
         fused_routes = {
-            'fp16_fused': (lambda D, k: k <= 32 and D in (64, 128, 256), ops.cast_f16, ops.cast_f16, ops.score_topk_f16),
-            'fp32_fused': (ops.score_topk_f32s_supported, ops.split_bf16x3, lambda u: u, ops.score_topk_f32s),
+            'fp16_fused': (ops.cast_f16, ops.cast_f16, ops.score_topk_f16),
+            'fp32_fused': (ops.split_bf16x3, lambda u: u, ops.score_topk_f32s),
         }
-        if scorer in fused_routes and (not plain or not fused_routes[scorer][0](int(i_repr.shape[1]), kmax)):
+        if scorer in fused_routes and (not plain or not ops.score_topk_fused_supported(scorer, int(i_repr.shape[1]), kmax, fused_max_k)):
             logging.info(f'{scorer} scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
                          f'the fused kernel, using the fp32 path')
             scorer = 'fp32'
@@ -323,7 +342,7 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
             scorer = 'fp32'
         fused = scorer in fused_routes
         if fused:
-            _, item_operand, user_operand, score_fused = fused_routes[scorer]
+            item_operand, user_operand, score_fused = fused_routes[scorer]
             i_op = item_operand(i_repr)                             # made once per call: fp16 [I, D] or three bf16 planes [3, I, D]
         if user_chunk is not None:
             bs = int(user_chunk)
@@ -347,7 +366,8 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
                 # (the key carries a fingerprint of the chunk's user ids: a split whose users_in_split changed between two evaluations
                 # must not meet the mask of the old users)
                 chunk = users[s:s + bs].astype(np.int64)
-                # (and the route: the two fused kernels lay the stream out for different tile widths)
+                # (and the route: the two fused kernels lay the stream out for different tile widths; the list length is not part of
+                # the key because a route's tile width does not depend on it: the wide kernels read the same stream)
                 holder = cache.setdefault((scorer, s, int(chunk.size), int(chunk[0]), int(chunk[-1]), int(chunk.sum()), lo, hi,
                                            int(i_op.shape[-1])), ops.ScorerExclusions())
                 val, idx = score_fused(user_operand(u_repr), i_op, kmax, u_idxs, excl[0], excl[1], item_offset=lo, exclusions=holder)
@@ -365,6 +385,84 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
             if sharded:
                 val, idx = parallel.all_gather_topk(val, idx, kmax)
             evaluator.eval_topk(u_idxs, idx)
+            if sink is not None:
+                sink(s, u_idxs, val, idx)
         if hasattr(alg, 'check_index_errors'):
             alg.check_index_errors()
-    return evaluator.get_results(return_raw_results=return_raw)
+    return kmax
+
+
+class Gatherer:
+    """eval/eval.py:230-258 — collects named results: arrays (numpy or torch) are appended per name and concatenated by ``gather``,
+    anything else is kept as the object last added under its name."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self._obj_collection = {}
+        self._collection = defaultdict(list)
+
+    def add(self, name: str, values):
+        if isinstance(values, torch.Tensor):
+            values = values.detach().cpu().numpy()
+        if isinstance(values, np.ndarray):
+            self._collection[name].append(values)
+        else:
+            self._obj_collection[name] = values
+
+    def gather(self) -> dict:
+        results = {name: np.concatenate(parts) for name, parts in self._collection.items()}
+        results.update(self._obj_collection)
+        return results
+
+    def export_pkl(self, path: str):
+        with open(path, 'wb') as fh:
+            pickle.dump(self.gather(), fh)
+
+
+def gather_recommender_algorithm_results(alg, eval_loader, evaluator: FullEvaluator, results_path: str = None, device: str = 'cuda',
+                                         verbose: bool = False, scorer: str = 'fp32', fused_max_k: int = 32,
+                                         user_chunk: Optional[int] = None):
+    """eval/eval.py:261-333 (SGD branch): the per-user top-k dump of a split. Returns (and pickles to ``results_path`` when given)
+
+      ``n_users``, ``n_items``     users / items of the split,
+      ``k``                        list length = max(top_k), capped at the items of the split (the reference's ``torch.topk`` raises there),
+      ``topk_item_indices``        int64 [n_users, k] positions in ``items_in_split``, best first (-1 behind fewer than k scoreable items),
+      ``topk_logits``              float32 [n_users, k] their scores (-inf in the empty slots),
+      ``user_indices``             int64 [n_users],
+      ``targets``                  int64 [n_labels, 2]: per LOADER batch (``eval_loader.batch_size`` consecutive users of the split, as the
+                                   reference iterates them) ``argwhere(labels)`` = (position of the user in its batch, item position),
+      ``metrics``, ``raw_metrics`` what ``evaluate_recommender_algorithm(..., return_raw=True)`` returns on the same inputs.
+
+    The one deliberate difference: the users are SCORED in engine-sized chunks (``user_chunk``; see ``evaluate_recommender_algorithm``),
+    not in the loader's batches. No result depends on that grouping — ``targets`` numbers the users by the loader's batches whatever
+    the chunk. The lists leave the device once per chunk. The scoring loop is the evaluation's own (``scorer``, ``fused_max_k`` as there):
+    the evaluator is fed from the very lists that are dumped."""
+    fused_max_k = ops.check_fused_max_k(fused_max_k)
+    dataset = eval_loader.dataset
+    gatherer = Gatherer()
+    bs = int(getattr(eval_loader, 'batch_size', 256) or 256)
+    users = np.asarray(dataset.users_in_split)
+    labels = sp.csr_matrix(dataset.user_sampling_matrix)
+
+    def sink(first, u_idxs, val, idx):
+        gatherer.add('topk_item_indices', idx.long())
+        gatherer.add('topk_logits', val.float())
+        gatherer.add('user_indices', u_idxs.long())
+        lab = sp.csr_matrix(labels[users[first:first + len(u_idxs)]][:, np.asarray(dataset.items_in_split)])
+        lab.eliminate_zeros()
+        lab.sort_indices()
+        rows = np.repeat(np.arange(first, first + lab.shape[0], dtype=np.int64), np.diff(lab.indptr))
+        gatherer.add('targets', np.stack([rows % bs, lab.indices.astype(np.int64)], axis=1))
+
+    k = _score_split(alg, eval_loader, evaluator, device, scorer, user_chunk, False, fused_max_k, sink)
+    gatherer.add('n_users', int(getattr(dataset, 'n_users_in_split', len(users))))
+    gatherer.add('n_items', int(getattr(dataset, 'n_items_in_split', len(dataset.items_in_split))))
+    gatherer.add('k', int(k))
+    metrics, raw_metrics = evaluator.get_results(return_raw_results=True)
+    gatherer.add('metrics', metrics)
+    gatherer.add('raw_metrics', raw_metrics)
+    if results_path is not None:
+        gatherer.export_pkl(results_path)
+    return gatherer.gather()

@@ -6,6 +6,7 @@ calling any op with CPU tensors raises.
 """
 from __future__ import annotations
 
+import numbers
 from typing import List, Optional, Sequence
 
 import torch
@@ -862,6 +863,8 @@ def _score_topk_fused(entry: str, route: str, u: torch.Tensor, i_op: torch.Tenso
 
 def score_topk_f16(u16: torch.Tensor, i16: torch.Tensor, k: int, u_idx=None, excl_indptr=None, excl_indices=None,
                    item_offset: int = 0, exclusions: 'ScorerExclusions' = None):
+    """The fused fp16 scorer: ``[Bu, k]`` (scores descending, ties by ascending item position; ``(-inf, -1)`` behind fewer than k
+    scoreable items). D in {64, 128, 256}, k <= 128 (k > 32 runs the wide kernels; the opt-in two-pass route takes k <= 32)."""
     _need_cuda(u16, i16)
     return _score_topk_fused('sbr_score_topk_f16', 'f16', u16, i16, i16.shape[0], k, u_idx, excl_indptr, excl_indices, item_offset,
                              exclusions)
@@ -890,10 +893,29 @@ def score_topk_f32s_supported(D: int, k: int) -> bool:
     return D in (64, 128) and 1 <= k <= 32
 
 
+FUSED_MAX_K = 128                 # longest list the one-pass fused scorers build (the wide instantiations: 33 .. 128)
+_FUSED_DIMS = {'fp16_fused': (64, 128, 256), 'fp32_fused': (64, 128)}
+
+
+def check_fused_max_k(max_k) -> int:
+    """``fused_max_k`` of the evaluator / trainer: an integer in [32, 128], anything else raises ValueError."""
+    if isinstance(max_k, bool) or not isinstance(max_k, numbers.Integral) or not 32 <= int(max_k) <= FUSED_MAX_K:
+        raise ValueError(f'fused_max_k must be an integer in [32, {FUSED_MAX_K}], got {max_k!r}')
+    return int(max_k)
+
+
+def score_topk_fused_supported(route: str, D: int, k: int, max_k: int = 32) -> bool:
+    """Whether the fused scorer ``route`` ('fp16_fused' / 'fp32_fused') takes representations of width D and lists of k entries when the
+    caller allows lists up to ``max_k`` (32: the evaluator's default, longer lists go to the fp32 route; up to 128: the wide kernels)."""
+    if route not in _FUSED_DIMS:
+        raise ValueError(f'unknown fused scorer {route!r}')
+    return int(D) in _FUSED_DIMS[route] and 1 <= int(k) <= check_fused_max_k(max_k)
+
+
 def score_topk_f32s(u32: torch.Tensor, i_planes: torch.Tensor, k: int, u_idx=None, excl_indptr=None, excl_indices=None,
                     item_offset: int = 0, exclusions: 'ScorerExclusions' = None):
     """The fused scorer with fp32-class products (eval/eval.py:216-222): fp32 user rows ``u32`` [Bu, D] against the item planes
-    ``i_planes`` = ``split_bf16x3(items)`` [3, I, D]; the output contract of ``score_topk_f16``. D in {64, 128}, k <= 32."""
+    ``i_planes`` = ``split_bf16x3(items)`` [3, I, D]; the output contract of ``score_topk_f16``. D in {64, 128}, k <= 128."""
     _need_cuda(u32, i_planes)
     u32 = _f32c(u32)
     Bu, D = u32.shape

@@ -16,7 +16,7 @@ import sys
 
 import torch
 
-from . import parallel
+from . import ops, parallel
 from .evaluation import FullEvaluator, evaluate_recommender_algorithm
 from .optim import FusedOptimizer
 
@@ -51,11 +51,12 @@ class Trainer:
         self.model_path = _get(conf, 'results_path')
         self.batch_verbose = _get(_get(conf, 'run_settings'), 'batch_verbose', False)
         self.scorer = _get(conf, 'scorer', 'fp32')          # 'fp32' | 'fp16_fused' | 'fp32_fused' (evaluation.evaluate_recommender_algorithm)
+        # longest top-k list the fused scorers may serve (32 .. 128; the default keeps longer lists on the fp32 route)
+        self.fused_max_k = ops.check_fused_max_k(_get(conf, 'fused_max_k', 32))
         # `conf.deterministic` (default None: leave the process-wide mode, whose env default is SBR_DETERMINISTIC): True / False switch
         # ops.set_deterministic — bit-identical repeated trainings (utilities/utils.py:22-27), at some cost in step time
         self.deterministic = _get(conf, 'deterministic', None)
         if self.deterministic is not None:
-            from . import ops
             ops.set_deterministic(bool(self.deterministic))
         self.best_value = self.best_metrics = self.best_epoch = None
         # the fused launch choreography (engine.FusedTrainStep) replaces autograd when the model is a SingleBranchNet with
@@ -177,7 +178,8 @@ class Trainer:
         evaluator = FullEvaluator(config=config, evaluator_name=evaluator_name, dataset=loader.dataset)
         # a data-parallel Trainer evaluates on every rank (fit() is collective): the catalogue is item-sharded over the ranks
         return evaluate_recommender_algorithm(self.pointer_to_model, loader, evaluator, self.device,
-                                              verbose=self.batch_verbose, scorer=self.scorer, shard_items=parallel.is_distributed())
+                                              verbose=self.batch_verbose, scorer=self.scorer, shard_items=parallel.is_distributed(),
+                                              fused_max_k=self.fused_max_k)
 
     def train_val(self):
         return self._eval_loader(self.train_val_loader, _get(self.full_conf, 'train_eval'), 'train')
