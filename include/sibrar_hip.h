@@ -469,6 +469,17 @@ int sbr_score_topk_f32s(const float* U_f32, const void* I_bf16x3, int D, long Bu
                         void* stream);
 /* bytes of `workspace` for sbr_score_topk_f32s (candidate buffers + fill counts of this route only; eval/eval.py:216-222) */
 long sbr_score_topk_f32s_workspace(long Bu, int I, int k);
+/* sbr_score_topk_f32s for 256-wide representations (eval/eval.py:216-222): the same operands, arithmetic, output contract and
+ * event-buffer protocol (32-item tiles: a stream built by either of the two entries for the same users, mask, item range and D may
+ * be handed to that entry again), from kernels of their own: one wave per SIMD, three consumer waves and a loader wave per workgroup
+ * (csrc/score_topk_f32s.hip). D must be 256 and k lie in [1, 128] (k > 32: the wide instantiation). New (additive to ABI 4). */
+int sbr_score_topk_f32s_d256(const float* U_f32, const void* I_bf16x3, int D, long Bu, int I, const long* u_idx,
+                             const long* excl_indptr, const int* excl_indices, long excl_nnz, int item_offset, int k, float* out_val,
+                             int* out_idx, void* workspace, long workspace_bytes, void* events, long events_bytes, int build_events,
+                             void* stream);
+/* bytes of `workspace` for sbr_score_topk_f32s_d256 (candidate buffers + fill counts of its workgroup geometry; does not depend on I
+ * or k; eval/eval.py:216-222) */
+long sbr_score_topk_f32s_d256_workspace(long Bu, int I, int k);
 /* X (fp32, n elements, contiguous) -> three bf16 planes Y[0..n), Y[n..2n), Y[2n..3n) (each plane rounded to nearest even from the
  * remainder); X = Y0 + Y1 + Y2 exactly for x = 0 and 2^-100 <= |x| <= 3.38e38 (below, the third plane underflows; above, and for inf / NaN,
  * the remainder planes are NaN: such item values are not supported): the item operand of sbr_score_topk_f32s (eval/eval.py:216-222) */

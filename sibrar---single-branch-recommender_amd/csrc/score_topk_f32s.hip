@@ -16,8 +16,8 @@
 // Geometry. The user planes do not fit the fp16 kernel's 128-register budget (four waves per SIMD), so a workgroup is 8 waves (two per
 // SIMD, up to 256 registers each): up to 7 consumer waves + 1 loader wave. Per 32-item tile a consumer wave at D = 128 issues
 // 6 x 8 = 48 MFMAs (~1,540 cycles) against three ds_read_b128 per K step; the compare / append / threshold work per tile is the fp16
-// kernel's and is a small fraction of that. D = 256 would need 192 VGPRs for the user planes alone and is not built (the host falls
-// back to the fp32 GEMM route).
+// kernel's and is a small fraction of that. D = 256 needs 192 VGPRs for the user planes alone: it does not fit this geometry and has
+// kernels of its own below (one wave per SIMD; sbr_score_topk_f32s_d256), sbr_score_topk_f32s keeps refusing it.
 //
 // Everything but the operands is the fp16 kernel's: the kernel is st_one_pass (score_topk_stream.h) with the StF32s operand policy —
 // exclusion event stream (s5_build_events, 32-item tiles), unit plan with partial waves (s5_plan with F3_MAXW slots), prefix pass and
@@ -39,10 +39,10 @@
 
 // operand policy of st_one_pass (score_topk_stream.h): fp32 user rows split in registers, three bf16 item planes per ring tile, six
 // MFMAs per K step (smallest terms first, as gemm_split_f32.hip)
-template <int KS_>
+template <int KS_, int MAXW_ = F3_MAXW>
 struct StF32s {
   static constexpr int KS = KS_, NJ = 1, PLANES = 3, NF = 3;
-  static constexpr int MAXW = F3_MAXW, NL = 1, PRE_TILES = F3_PRE_TILES;
+  static constexpr int MAXW = MAXW_, NL = 1, PRE_TILES = F3_PRE_TILES;
   static constexpr int PF = F3_PF, PF_PRE = F3_PF;
   typedef float UT;
   typedef __bf16 IT;
@@ -85,6 +85,27 @@ __global__ __launch_bounds__(512) void score_topk_wide_f32s_kernel(
   st_one_pass<StF32s<KS>, NS, true>(U, It, Bu, I, events, group_base, item_offset, k, n_pre, W, n_part, P, cnt_out, gbuf);
 }
 
+// D = 256: the user planes take 192 registers, so a workgroup is 4 waves, one per SIMD with the whole 512-entry register file each:
+// F3W_MAXW consumer waves + 1 loader wave over a ring of 3 slots of 48 KB. Kernels of their own names: the set of
+// instantiations of the two kernels above stays what it is.
+#define F3W_MAXW 3
+#define F3W_NS 3
+typedef StF32s<16, F3W_MAXW> StF32sD256;
+
+__global__ __launch_bounds__(256) void score_topk_f32s_d256_kernel(
+    const float* __restrict__ U, const __bf16* __restrict__ It, long Bu, int I, const unsigned int* __restrict__ events,
+    const int* __restrict__ group_base, int item_offset, int k, int n_pre, int W, int n_part, int P,
+    int* __restrict__ cnt_out, unsigned long long* __restrict__ gbuf) {
+  st_one_pass<StF32sD256, F3W_NS>(U, It, Bu, I, events, group_base, item_offset, k, n_pre, W, n_part, P, cnt_out, gbuf);
+}
+
+__global__ __launch_bounds__(256) void score_topk_wide_f32s_d256_kernel(
+    const float* __restrict__ U, const __bf16* __restrict__ It, long Bu, int I, const unsigned int* __restrict__ events,
+    const int* __restrict__ group_base, int item_offset, int k, int n_pre, int W, int n_part, int P,
+    int* __restrict__ cnt_out, unsigned long long* __restrict__ gbuf) {
+  st_one_pass<StF32sD256, F3W_NS, true>(U, It, Bu, I, events, group_base, item_offset, k, n_pre, W, n_part, P, cnt_out, gbuf);
+}
+
 extern "C" long sbr_score_topk_f32s_workspace(long Bu, int I, int k) {
   (void)I; (void)k;
   return st_workspace_bytes(Bu, F3_MAXW);
@@ -118,6 +139,34 @@ extern "C" int sbr_score_topk_f32s(const float* U, const void* I_bf16x3, int D, 
                                     excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, events, events_bytes, build_events, s);
   return st_launch<StF32s<8>, 6>(score_topk_f32s_kernel<8, 6>, "sbr_score_topk_f32s", U, It, Bu, I, u_idx, excl_indptr, excl_indices,
                                  excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, events, events_bytes, build_events, s);
+}
+
+extern "C" long sbr_score_topk_f32s_d256_workspace(long Bu, int I, int k) {
+  (void)I; (void)k;
+  return st_workspace_bytes(Bu, F3W_MAXW);
+}
+
+// sbr_score_topk_f32s for D = 256 (same operands, same event protocol and stream layout: 32-item tiles)
+extern "C" int sbr_score_topk_f32s_d256(const float* U, const void* I_bf16x3, int D, long Bu, int I, const long* u_idx,
+                                        const long* excl_indptr, const int* excl_indices, long excl_nnz, int item_offset, int k, float* out_val,
+                                        int* out_idx, void* workspace, long workspace_bytes, void* events, long events_bytes, int build_events,
+                                        void* stream) {
+  SBR_REQUIRE(k >= 1 && k <= 128, "sbr_score_topk_f32s_d256: k=%d outside [1, 128] (use sbr_gemm_f32 + sbr_topk_rows)", k);
+  SBR_REQUIRE(I >= 1, "sbr_score_topk_f32s_d256: empty catalogue");
+  SBR_REQUIRE(D == 256, "sbr_score_topk_f32s_d256: D=%d not supported (256; sbr_score_topk_f32s has 64 and 128)", D);
+  if (Bu == 0) return SBR_OK;
+  SBR_REQUIRE(U && I_bf16x3 && out_val && out_idx, "sbr_score_topk_f32s_d256: null operand");
+  SBR_REQUIRE(((size_t)U & 15) == 0 && ((size_t)I_bf16x3 & 15) == 0, "sbr_score_topk_f32s_d256: operands must be 16-byte aligned");
+  SBR_REQUIRE((excl_indptr == nullptr) == (excl_indices == nullptr), "sbr_score_topk_f32s_d256: exclusion CSR must be given whole or not at all");
+  const hipStream_t s = (hipStream_t)stream;
+  const __bf16* It = (const __bf16*)I_bf16x3;
+  if (k > 32)
+    return st_launch<StF32sD256, F3W_NS, true>(score_topk_wide_f32s_d256_kernel, "sbr_score_topk_f32s_d256", U, It, Bu, I, u_idx, excl_indptr,
+                                               excl_indices, excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, events,
+                                               events_bytes, build_events, s);
+  return st_launch<StF32sD256, F3W_NS>(score_topk_f32s_d256_kernel, "sbr_score_topk_f32s_d256", U, It, Bu, I, u_idx, excl_indptr, excl_indices,
+                                       excl_nnz, item_offset, k, out_val, out_idx, workspace, workspace_bytes, events, events_bytes,
+                                       build_events, s);
 }
 
 // X (fp32, n elements) -> Y = three bf16 planes of n elements each (round to nearest even per plane), X = Y[0] + Y[1] + Y[2] exactly for

@@ -8,7 +8,7 @@ Here the exclusion CSR and the label CSR are resident on the device; per user ba
   * ``scorer='fp16_fused'``: the fused fp16-MFMA score+mask+top-k kernel (scores never written), or
   * ``scorer='fp32_fused'``: the same fusion with fp32-class products (fp32 user rows and the item matrix split once into three
     exact bf16 planes, six bf16-MFMA partial products per score, fp32 accumulation): the fp32 route's ranking without its score
-    matrix; D in {64, 128} and finite item values, anything else falls back to ``'fp32'``,
+    matrix; D in {64, 128} (D = 256 with ``fused_max_d=256``) and finite item values, anything else falls back to ``'fp32'``,
 both fused routes for lists up to ``fused_max_k`` entries (default 32; up to 128 on request: the wide kernels), longer ones fall back,
 followed by the ranking-metric kernel (NDCG / recall / precision as defined in eval/metrics.py:4-105; ``rmet`` itself is
 absent offline, so w.r.t. ``rmet`` the metric arithmetic is parity-unpinned). ``eval_batch`` keeps the reference's
@@ -250,12 +250,15 @@ class FullEvaluator:
 
 def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, device='cuda', return_raw=False, verbose=False,
                                    scorer: str = 'fp32', user_chunk: Optional[int] = None, shard_items: bool = False,
-                                   fused_max_k: int = 32):
+                                   fused_max_k: int = 32, fused_max_d: int = 128):
     """eval/eval.py:171-227 (SGD branch :203-222). ``eval_loader`` only has to expose ``dataset`` and ``batch_size``.
 
     ``fused_max_k`` (32 .. 128, anything else raises ValueError): the longest list the fused routes may serve. With the default an
     evaluation whose largest cut-off is above 32 takes the fp32 route, as it always did; with 128 it stays on the requested fused route
     (the wide kernels) up to a largest cut-off of 128.
+
+    ``fused_max_d`` (128 or 256, anything else raises ValueError): the widest representation ``scorer='fp32_fused'`` may serve. With the
+    default a 256-wide model takes the fp32 route, as it always did; with 256 it is scored by ``ops.score_topk_f32s_d256``.
 
     The users are scored in engine-sized chunks, not in the loader's batches: per-user results do not depend on the grouping,
     and the reference's default evaluation batch (256 users) leaves the GPU idle — the fused kernel assigns 448 users to a workgroup and every workgroup streams the whole catalogue, so they want >= 57k users per launch (measured on
@@ -270,12 +273,12 @@ def evaluate_recommender_algorithm(alg, eval_loader, evaluator: FullEvaluator, d
     lists are all-gathered and merged exactly (``parallel.all_gather_topk`` -> ``sbr_merge_topk``: score desc, index asc), and every
     rank feeds the merged lists to its evaluator — all ranks return the same metrics as a one-rank evaluation. Models whose item side
     is more than one matrix (biases) score unsharded on every rank."""
-    fused_max_k = ops.check_fused_max_k(fused_max_k)
-    _score_split(alg, eval_loader, evaluator, device, scorer, user_chunk, shard_items, fused_max_k, None)
+    fused_max_k, fused_max_d = ops.check_fused_max_k(fused_max_k), ops.check_fused_max_d(fused_max_d)
+    _score_split(alg, eval_loader, evaluator, device, scorer, user_chunk, shard_items, fused_max_k, None, fused_max_d)
     return evaluator.get_results(return_raw_results=return_raw)
 
 
-def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, user_chunk, shard_items, fused_max_k, sink):
+def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, user_chunk, shard_items, fused_max_k, sink, fused_max_d=128):
     """The scoring loop of ``evaluate_recommender_algorithm`` and ``gather_recommender_algorithm_results``: every user chunk's top-k
     lists go to the evaluator and, when given, to ``sink(first row of the chunk, u_idxs, scores [Bu, k], item positions [Bu, k])``.
     Returns the list length k = min(max(top_k), items in the split)."""
@@ -325,14 +328,15 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
         if scorer not in ('fp32', 'fp16_fused', 'fp32_fused'):
             raise ValueError(f'unknown scorer {scorer!r}')
         # the fused routes: (item operand made once per call, user operand made per chunk, call). fp16_fused is built for D in
-        # {64, 128, 256}, fp32_fused for D in {64, 128} (the user planes of D = 256 do not fit its registers); both serve lists up to
+        # {64, 128, 256}, fp32_fused for D in {64, 128} (D = 256 has kernels of its own, used with fused_max_d = 256); both serve lists up to
         # fused_max_k entries (ops.score_topk_fused_supported). Everything else — larger cut-offs (the reference's default evaluator
         # asks for top-100: fused only with fused_max_k >= 100), tuple item sides — takes the exact fp32 GEMM + radix-select path.
         fused_routes = {
             'fp16_fused': (ops.cast_f16, ops.cast_f16, ops.score_topk_f16),
             'fp32_fused': (ops.split_bf16x3, lambda u: u, ops.score_topk_f32s),
         }
-        if scorer in fused_routes and (not plain or not ops.score_topk_fused_supported(scorer, int(i_repr.shape[1]), kmax, fused_max_k)):
+        if scorer in fused_routes and (not plain or not ops.score_topk_fused_supported(scorer, int(i_repr.shape[1]), kmax, fused_max_k,
+                                                                                       fused_max_d)):
             logging.info(f'{scorer} scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
                          f'the fused kernel, using the fp32 path')
             scorer = 'fp32'
@@ -343,6 +347,8 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
         fused = scorer in fused_routes
         if fused:
             item_operand, user_operand, score_fused = fused_routes[scorer]
+            if scorer == 'fp32_fused' and int(i_repr.shape[1]) == ops.FUSED_MAX_D:
+                score_fused = ops.score_topk_f32s_d256
             i_op = item_operand(i_repr)                             # made once per call: fp16 [I, D] or three bf16 planes [3, I, D]
         if user_chunk is not None:
             bs = int(user_chunk)
@@ -423,7 +429,7 @@ class Gatherer:
 
 def gather_recommender_algorithm_results(alg, eval_loader, evaluator: FullEvaluator, results_path: str = None, device: str = 'cuda',
                                          verbose: bool = False, scorer: str = 'fp32', fused_max_k: int = 32,
-                                         user_chunk: Optional[int] = None):
+                                         user_chunk: Optional[int] = None, fused_max_d: int = 128):
     """eval/eval.py:261-333 (SGD branch): the per-user top-k dump of a split. Returns (and pickles to ``results_path`` when given)
 
       ``n_users``, ``n_items``     users / items of the split,
@@ -437,9 +443,9 @@ def gather_recommender_algorithm_results(alg, eval_loader, evaluator: FullEvalua
 
     The one deliberate difference: the users are SCORED in engine-sized chunks (``user_chunk``; see ``evaluate_recommender_algorithm``),
     not in the loader's batches. No result depends on that grouping — ``targets`` numbers the users by the loader's batches whatever
-    the chunk. The lists leave the device once per chunk. The scoring loop is the evaluation's own (``scorer``, ``fused_max_k`` as there):
+    the chunk. The lists leave the device once per chunk. The scoring loop is the evaluation's own (``scorer``, ``fused_max_k``, ``fused_max_d`` as there):
     the evaluator is fed from the very lists that are dumped."""
-    fused_max_k = ops.check_fused_max_k(fused_max_k)
+    fused_max_k, fused_max_d = ops.check_fused_max_k(fused_max_k), ops.check_fused_max_d(fused_max_d)
     dataset = eval_loader.dataset
     gatherer = Gatherer()
     bs = int(getattr(eval_loader, 'batch_size', 256) or 256)
@@ -456,7 +462,7 @@ def gather_recommender_algorithm_results(alg, eval_loader, evaluator: FullEvalua
         rows = np.repeat(np.arange(first, first + lab.shape[0], dtype=np.int64), np.diff(lab.indptr))
         gatherer.add('targets', np.stack([rows % bs, lab.indices.astype(np.int64)], axis=1))
 
-    k = _score_split(alg, eval_loader, evaluator, device, scorer, user_chunk, False, fused_max_k, sink)
+    k = _score_split(alg, eval_loader, evaluator, device, scorer, user_chunk, False, fused_max_k, sink, fused_max_d)
     gatherer.add('n_users', int(getattr(dataset, 'n_users_in_split', len(users))))
     gatherer.add('n_items', int(getattr(dataset, 'n_items_in_split', len(dataset.items_in_split))))
     gatherer.add('k', int(k))

@@ -847,7 +847,7 @@ def score_topk_route(route: int = -1) -> int:
 def _score_topk_fused(entry: str, route: str, u: torch.Tensor, i_op: torch.Tensor, I: int, k: int, u_idx, excl_indptr, excl_indices,
                       item_offset: int, exclusions):
     """One call of a fused scorer C entry (``entry`` and ``entry + '_workspace'``): output, workspace and exclusion-event plumbing
-    shared by ``score_topk_f16`` and ``score_topk_f32s``. ``route`` keys the cached event stream (the routes lay it out for different
+    shared by ``score_topk_f16``, ``score_topk_f32s`` and ``score_topk_f32s_d256``. ``route`` keys the cached event stream (the routes lay it out for different
     tile widths)."""
     Bu, D = u.shape
     val = torch.empty(Bu, k, device=u.device, dtype=torch.float32)
@@ -904,12 +904,27 @@ def check_fused_max_k(max_k) -> int:
     return int(max_k)
 
 
-def score_topk_fused_supported(route: str, D: int, k: int, max_k: int = 32) -> bool:
+FUSED_MAX_D = 256                 # widest representation of the fp32-class fused route (score_topk_f32s_d256, on request)
+
+
+def check_fused_max_d(max_d) -> int:
+    """``fused_max_d`` of the evaluator / trainer: 128 or 256, anything else raises ValueError."""
+    if isinstance(max_d, bool) or not isinstance(max_d, numbers.Integral) or int(max_d) not in (128, FUSED_MAX_D):
+        raise ValueError(f'fused_max_d must be 128 or {FUSED_MAX_D}, got {max_d!r}')
+    return int(max_d)
+
+
+def score_topk_fused_supported(route: str, D: int, k: int, max_k: int = 32, max_d: int = 128) -> bool:
     """Whether the fused scorer ``route`` ('fp16_fused' / 'fp32_fused') takes representations of width D and lists of k entries when the
-    caller allows lists up to ``max_k`` (32: the evaluator's default, longer lists go to the fp32 route; up to 128: the wide kernels)."""
+    caller allows lists up to ``max_k`` (32: the evaluator's default, longer lists go to the fp32 route; up to 128: the wide kernels)
+    and, on 'fp32_fused', representations up to ``max_d`` wide (128: the default, D = 256 goes to the fp32 route; 256: the
+    one-wave-per-SIMD kernels of ``score_topk_f32s_d256``)."""
     if route not in _FUSED_DIMS:
         raise ValueError(f'unknown fused scorer {route!r}')
-    return int(D) in _FUSED_DIMS[route] and 1 <= int(k) <= check_fused_max_k(max_k)
+    dims = _FUSED_DIMS[route]
+    if check_fused_max_d(max_d) == FUSED_MAX_D and route == 'fp32_fused':
+        dims = dims + (FUSED_MAX_D,)
+    return int(D) in dims and 1 <= int(k) <= check_fused_max_k(max_k)
 
 
 def score_topk_f32s(u32: torch.Tensor, i_planes: torch.Tensor, k: int, u_idx=None, excl_indptr=None, excl_indices=None,
@@ -923,6 +938,22 @@ def score_topk_f32s(u32: torch.Tensor, i_planes: torch.Tensor, k: int, u_idx=Non
         raise ValueError(f'score_topk_f32s: item planes must be bfloat16 [3, I, {D}] (split_bf16x3), got {i_planes.dtype} {tuple(i_planes.shape)}')
     i_planes = i_planes.contiguous()
     return _score_topk_fused('sbr_score_topk_f32s', 'f32s', u32, i_planes, i_planes.shape[1], k, u_idx, excl_indptr, excl_indices,
+                             item_offset, exclusions)
+
+
+def score_topk_f32s_d256(u32: torch.Tensor, i_planes: torch.Tensor, k: int, u_idx=None, excl_indptr=None, excl_indices=None,
+                         item_offset: int = 0, exclusions: 'ScorerExclusions' = None):
+    """``score_topk_f32s`` for 256-wide representations (eval/eval.py:216-222): the same arithmetic and output contract from kernels
+    of their own (one wave per SIMD: the user planes take 192 registers). D = 256 only, k <= 128."""
+    _need_cuda(u32, i_planes)
+    u32 = _f32c(u32)
+    Bu, D = u32.shape
+    if D != 256:
+        raise ValueError(f'score_topk_f32s_d256: D={D} not supported (256; score_topk_f32s has 64 and 128)')
+    if i_planes.dtype != torch.bfloat16 or i_planes.dim() != 3 or i_planes.shape[0] != 3 or i_planes.shape[2] != D:
+        raise ValueError(f'score_topk_f32s_d256: item planes must be bfloat16 [3, I, {D}] (split_bf16x3), got {i_planes.dtype} {tuple(i_planes.shape)}')
+    i_planes = i_planes.contiguous()
+    return _score_topk_fused('sbr_score_topk_f32s_d256', 'f32s_d256', u32, i_planes, i_planes.shape[1], k, u_idx, excl_indptr, excl_indices,
                              item_offset, exclusions)
 
 

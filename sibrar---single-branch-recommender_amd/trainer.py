@@ -53,6 +53,8 @@ class Trainer:
         self.scorer = _get(conf, 'scorer', 'fp32')          # 'fp32' | 'fp16_fused' | 'fp32_fused' (evaluation.evaluate_recommender_algorithm)
         # longest top-k list the fused scorers may serve (32 .. 128; the default keeps longer lists on the fp32 route)
         self.fused_max_k = ops.check_fused_max_k(_get(conf, 'fused_max_k', 32))
+        # widest representation the 'fp32_fused' scorer may serve (128 | 256; the default keeps 256-wide models on the fp32 route)
+        self.fused_max_d = ops.check_fused_max_d(_get(conf, 'fused_max_d', 128))
         # `conf.deterministic` (default None: leave the process-wide mode, whose env default is SBR_DETERMINISTIC): True / False switch
         # ops.set_deterministic — bit-identical repeated trainings (utilities/utils.py:22-27), at some cost in step time
         self.deterministic = _get(conf, 'deterministic', None)
@@ -179,7 +181,7 @@ class Trainer:
         # a data-parallel Trainer evaluates on every rank (fit() is collective): the catalogue is item-sharded over the ranks
         return evaluate_recommender_algorithm(self.pointer_to_model, loader, evaluator, self.device,
                                               verbose=self.batch_verbose, scorer=self.scorer, shard_items=parallel.is_distributed(),
-                                              fused_max_k=self.fused_max_k)
+                                              fused_max_k=self.fused_max_k, fused_max_d=self.fused_max_d)
 
     def train_val(self):
         return self._eval_loader(self.train_val_loader, _get(self.full_conf, 'train_eval'), 'train')
