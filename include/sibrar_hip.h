@@ -258,6 +258,19 @@ int sbr_aggregate_bwd(const float* dOut, const unsigned char* argmax, float* dE,
 /* training scorer einsum('be,bce->bc') — algorithms/sgd_alg.py:2114 */
 int sbr_score_dot_fwd(const float* U, const float* I, float* out, long B, int N, int D, void* stream);
 int sbr_score_dot_bwd(const float* G, const float* U, const float* I, float* dU, float* dI, long B, int N, int D, void* stream);
+/* DeepMF's training scorer — algorithms/sgd_alg.py:1238-1242: nn.CosineSimilarity(dim=-1)(u[:, None, :], i) with each norm clamped
+ * at eps, then sim[sim < mu] = mu. U [B, D], I [B, N, D] -> out [B, N] (additive to ABI 4; csrc/score_cos.hip). The forward pass
+ * also writes, once, what the backward pass needs: cos_raw [B, N] (the un-floored cosine), u_stat [B, 2] and i_stat [B, N, 2] =
+ * {1 / max(|row|, eps), |row| > 0 ? 1 / |row| : 0}. Backward: a floored entry (cos_raw < mu) passes no gradient; a row at or below
+ * eps takes the gradient of torch's autograd for its clamp (finite). dU or dI may be NULL. One wavefront per batch row, no atomics:
+ * the same bits on every run. Any D >= 1, N >= 1. */
+int sbr_score_cos_fwd(const float* U, const float* I, float* out, float* cos_raw, float* u_stat, float* i_stat, long B, int N, int D,
+                      float mu, float eps, void* stream);
+int sbr_score_cos_bwd(const float* G, const float* U, const float* I, const float* cos_raw, const float* u_stat, const float* i_stat,
+                      float* dU, float* dI, long B, int N, int D, float mu, void* stream);
+/* the floor of the all-pairs evaluation form — algorithms/sgd_alg.py:1241 on the [n, n_cols] score matrix of eval/eval.py:216
+ * (row stride ld), in place: x[x < mu] = mu, NaN left alone. Applied before the exclusion mask (eval/eval.py:219-220). */
+int sbr_floor_scores(float* scores, long n, long n_cols, long ld, float mu, void* stream);
 /* SGDBaseline — algorithms/sgd_alg.py:110-119 */
 int sbr_bias_score_fwd(const float* user_bias, const float* item_bias, const float* global_bias, const long* u, const long* i,
                        float* out, long B, int N, void* stream);

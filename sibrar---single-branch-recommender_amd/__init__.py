@@ -15,6 +15,7 @@ from .sbnet import (FeatureEmbedding, ItemFeatureMatrixFactorization, SGDBasedRe
                     SGDMatrixFactorization, SingleBranchNet, SingleBranchNetEntity, UserFeatureMatrixFactorization,
                     general_weight_init)
 from .dropoutnet import DropoutNet, DropoutNetEntity                                      # noqa: F401
+from .deepmf import DeepMatrixFactorization                                                # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
                      RecSampledSoftmaxLoss, RecommenderSystemLoss, RecommenderSystemLossesEnum)
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
@@ -40,6 +41,6 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
         torch.cuda.manual_seed_all(seed)
     ops.set_deterministic(deterministic)
 
-# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf -> class (algorithms/algorithms_utils.py:14,17,36)
+# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf -> class (algorithms/algorithms_utils.py:14,17,34,36)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
-              'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet}
+              'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization}

@@ -11,37 +11,14 @@ from __future__ import annotations
 from typing import Dict
 
 import numpy as np
-import scipy.sparse as sp
 import torch
 from torch import nn
 
 from . import ops
-from ._lib import call, ptr, stream
 from .config import DropoutNetConfig, DropoutNetEntityConfig, DropoutNetSamplingStrategy
+from .features import DeviceCSR as _DeviceCSR
 from .polylinear import PolyLinear
 from .sbnet import FeatureEmbedding, SGDBasedRecommenderAlgorithm
-
-
-class _DeviceCSR(nn.Module):
-    """Interaction matrix resident in HBM (non-persistent buffers: they move with ``.to(device)``, stay out of the state_dict)."""
-
-    def __init__(self, m):
-        super().__init__()
-        m = sp.csr_matrix(m)
-        m.sort_indices()
-        self.shape = m.shape
-        self.register_buffer('indptr', torch.from_numpy(m.indptr.astype(np.int64)), persistent=False)
-        self.register_buffer('indices', torch.from_numpy(m.indices.astype(np.int32)), persistent=False)
-        data = m.data.astype(np.float32)
-        self.register_buffer('data', None if bool(np.all(data == 1)) else torch.from_numpy(data), persistent=False)
-
-    def dense_rows(self, ent: torch.Tensor) -> torch.Tensor:
-        """ent: int64 [...] entity ids, -1 = zero vector -> float32 [..., n_cols]."""
-        flat = ent.reshape(-1).long().contiguous()
-        out = torch.empty(flat.numel(), self.shape[1], device=flat.device, dtype=torch.float32)
-        call('sbr_csr_rows_to_dense', ptr(self.indptr), ptr(self.indices), ptr(self.data), ptr(flat), flat.numel(), self.shape[1],
-             ptr(out), out.stride(0), stream())
-        return out.view(*ent.shape, self.shape[1])
 
 
 class DropoutNetEntity(nn.Module):

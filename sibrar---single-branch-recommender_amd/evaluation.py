@@ -345,10 +345,20 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
             logging.info('fp32_fused scorer: non-finite item representations, using the fp32 path')
             scorer = 'fp32'
         fused = scorer in fused_routes
+        # a model whose score is not the plain dot product of its representations (DeepMF: a floored cosine) provides
+        # ``fused_score_transform() -> (items_fn, users_fn, finish_fn)``: the fused kernels only compute dot products, so the item
+        # representations pass through items_fn once, every chunk's user representations through users_fn, and every chunk's
+        # (val, idx) lists through finish_fn before they are merged / evaluated / dumped. Models without the hook are untouched.
+        transform = getattr(alg, 'fused_score_transform', None) if fused else None
+        items_fn = users_fn = finish_fn = None
+        if transform is not None:
+            items_fn, users_fn, finish_fn = transform()
         if fused:
             item_operand, user_operand, score_fused = fused_routes[scorer]
             if scorer == 'fp32_fused' and int(i_repr.shape[1]) == ops.FUSED_MAX_D:
                 score_fused = ops.score_topk_f32s_d256
+            if items_fn is not None:
+                i_repr = items_fn(i_repr)
             i_op = item_operand(i_repr)                             # made once per call: fp16 [I, D] or three bf16 planes [3, I, D]
         if user_chunk is not None:
             bs = int(user_chunk)
@@ -376,7 +386,11 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
                 # the key because a route's tile width does not depend on it: the wide kernels read the same stream)
                 holder = cache.setdefault((scorer, s, int(chunk.size), int(chunk[0]), int(chunk[-1]), int(chunk.sum()), lo, hi,
                                            int(i_op.shape[-1])), ops.ScorerExclusions())
+                if users_fn is not None:
+                    u_repr = users_fn(u_repr)
                 val, idx = score_fused(user_operand(u_repr), i_op, kmax, u_idxs, excl[0], excl[1], item_offset=lo, exclusions=holder)
+                if finish_fn is not None:
+                    val, idx = finish_fn(val, idx)
             else:
                 out = alg.combine_user_item_representations(u_repr, i_repr)
                 ops.mask_scores_(out, u_idxs, excl[0], excl[1], item_offset=lo if sharded else None)

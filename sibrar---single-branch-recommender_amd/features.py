@@ -194,3 +194,50 @@ class DeviceTable(nn.Module):
             t_data = None if self.data is None else self.data[order].contiguous()
             self._transposed = (t_indptr, t_indices, t_data)
         return self._transposed
+
+
+class DeviceCSR(nn.Module):
+    """Interaction matrix resident in HBM (non-persistent buffers: they move with ``.to(device)``, stay out of the state_dict).
+    ``l2_normalize_rows``: every row is scaled by ``1 / max(||row||_2, 1e-8)`` once, in fp32 (DeepMF's ``normalize_interactions``,
+    algorithms/sgd_alg.py:1211-1213, 1226-1228: ``vec / norm.clamp(min=1e-8)`` of the dense row)."""
+
+    def __init__(self, m, l2_normalize_rows: bool = False):
+        super().__init__()
+        m = sp.csr_matrix(m)
+        m.sort_indices()
+        self.shape = m.shape
+        self.register_buffer('indptr', torch.from_numpy(m.indptr.astype(np.int64)), persistent=False)
+        self.register_buffer('indices', torch.from_numpy(m.indices.astype(np.int32)), persistent=False)
+        data = torch.from_numpy(m.data.astype(np.float32))
+        if l2_normalize_rows:
+            counts = torch.from_numpy(np.diff(m.indptr).astype(np.int64))
+            row_of = torch.repeat_interleave(torch.arange(m.shape[0]), counts)
+            sq = torch.zeros(m.shape[0], dtype=torch.float32).index_add_(0, row_of, data * data)
+            data = data / torch.sqrt(sq).clamp(min=1e-8)[row_of]
+        self.register_buffer('data', None if bool((data == 1).all()) else data, persistent=False)
+        self._transposed = None
+        self._grad_ws = None              # [n_rows, C] per-entity gradient rows (ops.SparseLinearActFn, gather form)
+
+    def dense_rows(self, ent: torch.Tensor) -> torch.Tensor:
+        """ent: int64 [...] entity ids, -1 = zero vector -> float32 [..., n_cols]."""
+        from ._lib import call, ptr, stream
+        flat = ent.reshape(-1).long().contiguous()
+        out = torch.empty(flat.numel(), self.shape[1], device=flat.device, dtype=torch.float32)
+        call('sbr_csr_rows_to_dense', ptr(self.indptr), ptr(self.indices), ptr(self.data), ptr(flat), flat.numel(), self.shape[1],
+             ptr(out), out.stride(0), stream())
+        return out.view(*ent.shape, self.shape[1])
+
+    def transposed(self):
+        """CSR form of the transposed matrix on the matrix's device: (indptr int64 [n_cols + 1], indices int32 [nnz] = rows ascending
+        within a column, data float32 [nnz] or None). Built once per device, on first use."""
+        if self._transposed is None or self._transposed[0].device != self.indptr.device:
+            n_rows, n_cols = self.shape
+            dev = self.indptr.device
+            cols = self.indices.long()
+            t_indptr = torch.zeros(n_cols + 1, dtype=torch.int64, device=dev)
+            t_indptr[1:] = torch.cumsum(torch.bincount(cols, minlength=n_cols), 0)
+            row_of = torch.repeat_interleave(torch.arange(n_rows, device=dev), self.indptr[1:] - self.indptr[:-1])
+            order = torch.sort(cols, stable=True).indices
+            self._transposed = (t_indptr, row_of[order].to(torch.int32).contiguous(),
+                                None if self.data is None else self.data[order].contiguous())
+        return self._transposed

@@ -461,6 +461,59 @@ class LinearActFn(Function):
         return dx, dw, db, None
 
 
+class SparseLinearActFn(Function):
+    """y = act(X[rows] @ W^T + b) with X a resident CSR matrix (``features.DeviceCSR``) that is never densified — the input layer of
+    DeepMF's towers (algorithms/sgd_alg.py:1210-1215, 1225-1230: ``dataset.get_*_interaction_vectors(idx).float()`` into
+    modules/polylinear.py:51). ``rows``: int32 [n] row ids; ``weight``: [out, n_cols] stored column-major (``weight.t()`` contiguous, the
+    layout of FeatureEmbedding's CSR projector); its gradient comes back in the same layout. The weight gradient takes the gather form
+    (``sbr_csr_project_bwd_gather``: fixed summation order, no atomics on dW) when ``out % 4 == 0 and out <= 1024``, the scatter form
+    otherwise — in deterministic mode the scatter form raises "no deterministic form" instead."""
+
+    @staticmethod
+    def forward(ctx, csr, rows, weight, bias, act: int):
+        _need_cuda(rows, weight)
+        wt = weight.t()
+        if not wt.is_contiguous():
+            raise ValueError('SparseLinearActFn: the weight must be stored column-major (weight.t() contiguous)')
+        if weight.shape[1] != csr.shape[1]:
+            raise ValueError(f'SparseLinearActFn: weight has {weight.shape[1]} input columns, the matrix {csr.shape[1]}')
+        rows = rows.reshape(-1).to(torch.int32).contiguous()
+        n, C = rows.numel(), weight.shape[0]
+        y = torch.empty(n, C, device=weight.device, dtype=torch.float32)
+        call('sbr_csr_project_fwd', ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), ptr(wt), wt.stride(0), ptr(bias), ptr(rows), ptr(y),
+             y.stride(0), None, n, C, act, stream())
+        ctx.csr, ctx.act, ctx.has_bias = csr, act, bias is not None
+        ctx.save_for_backward(rows, y)
+        ctx.w_shape = tuple(weight.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        rows, y = ctx.saved_tensors
+        csr = ctx.csr
+        C, n_cols = ctx.w_shape
+        n = rows.numel()
+        dy = _f32c(dy)
+        dz = act_grad(dy, y, ctx.act) if ctx.act else dy
+        dw = None
+        if ctx.needs_input_grad[2]:
+            dwt = torch.zeros(n_cols, C, device=dz.device, dtype=torch.float32)
+            if C % 4 == 0 and C <= 1024:
+                ti, tj, tv = csr.transposed()
+                ws = csr._grad_ws
+                if ws is None or ws.shape != (csr.shape[0], C) or ws.device != dz.device:
+                    ws = csr._grad_ws = torch.empty(csr.shape[0], C, device=dz.device, dtype=torch.float32)
+                call('sbr_csr_project_bwd_gather', ptr(ti), ptr(tj), ptr(tv), ptr(dz), dz.stride(0), None, ptr(rows), n, ptr(ws), C,
+                     csr.shape[0], ptr(dwt), dwt.stride(0), n_cols, C, stream())
+            else:
+                # arrival-order float atomics: the library refuses this entry point in deterministic mode ("no deterministic form")
+                call('sbr_csr_project_bwd', ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), ptr(dz), dz.stride(0), ptr(rows), ptr(dwt),
+                     dwt.stride(0), n, C, stream())
+            dw = dwt.t()
+        db = colsum(dz) if (ctx.has_bias and ctx.needs_input_grad[3]) else None
+        return None, None, dw, db, None
+
+
 # ---- BatchNorm1d (+ activation) ---------------------------------------------------------------------------------------
 class BatchNormActFn(Function):
     """Train-mode BatchNorm1d over rows followed by an activation (polylinear.py:61-65; sgd_alg.py:1837)."""
@@ -506,15 +559,17 @@ def batch_norm_eval(x, weight, bias, running_mean, running_var, act: int):
 
 # ---- row normalisation, dropout, aggregation ---------------------------------------------------------------------------
 class L2NormalizeFn(Function):
-    """F.normalize(x, p=2, dim=-1) — sgd_alg.py:1873-1874."""
+    """F.normalize(x, p=2, dim=-1) — sgd_alg.py:1873-1874. ``eps`` (default ``NORM_EPS``): the clamp of the norm; DeepMF's
+    ``x / norm.clamp(min=1e-8)`` (sgd_alg.py:1217-1219) is the same kernel with ``eps=1e-8``."""
 
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, eps: float = NORM_EPS):
         _need_cuda(x)
         x = _f32c(x)
         y = torch.empty_like(x)
         inv = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
-        call('sbr_l2norm_fwd', ptr(x), ptr(y), ptr(inv), x.shape[0], x.shape[1], NORM_EPS, stream())
+        call('sbr_l2norm_fwd', ptr(x), ptr(y), ptr(inv), x.shape[0], x.shape[1], eps, stream())
+        ctx.eps = eps
         ctx.save_for_backward(y, inv)
         return y
 
@@ -523,8 +578,8 @@ class L2NormalizeFn(Function):
         y, inv = ctx.saved_tensors
         dy = _f32c(dy)
         dx = torch.empty_like(y)
-        call('sbr_l2norm_bwd', ptr(dy), ptr(y), ptr(inv), ptr(dx), y.shape[0], y.shape[1], NORM_EPS, stream())
-        return dx
+        call('sbr_l2norm_bwd', ptr(dy), ptr(y), ptr(inv), ptr(dx), y.shape[0], y.shape[1], ctx.eps, stream())
+        return dx, None
 
 
 class DropoutFn(Function):
@@ -595,6 +650,80 @@ class ScoreDotFn(Function):
         di = torch.empty_like(i) if ctx.needs_input_grad[1] else None
         call('sbr_score_dot_bwd', ptr(g), ptr(u), ptr(i), ptr(du), ptr(di), B, N, D, stream())
         return du, di
+
+
+COS_EPS = 1e-8                    # nn.CosineSimilarity's default eps (sgd_alg.py:1183)
+
+
+class ScoreCosFn(Function):
+    """nn.CosineSimilarity(dim=-1)(u[:, None, :], i) then ``sim[sim < mu] = mu`` — DeepMF's training scorer, sgd_alg.py:1238-1242:
+    u [B, D], i [B, N, D] -> [B, N] in one kernel each way. A floored entry passes no gradient (index assignment cuts the tape)."""
+
+    @staticmethod
+    def forward(ctx, u, i, mu: float, eps: float = COS_EPS):
+        _need_cuda(u, i)
+        u, i = _f32c(u), _f32c(i)
+        B, N, D = i.shape
+        if u.shape != (B, D):
+            raise ValueError(f'ScoreCosFn: u {tuple(u.shape)} does not match i {tuple(i.shape)}')
+        out = torch.empty(B, N, device=u.device, dtype=torch.float32)
+        raw = torch.empty(B, N, device=u.device, dtype=torch.float32)
+        u_stat = torch.empty(B, 2, device=u.device, dtype=torch.float32)
+        i_stat = torch.empty(B, N, 2, device=u.device, dtype=torch.float32)
+        call('sbr_score_cos_fwd', ptr(u), ptr(i), ptr(out), ptr(raw), ptr(u_stat), ptr(i_stat), B, N, D, mu, eps, stream())
+        ctx.mu = mu
+        ctx.save_for_backward(u, i, raw, u_stat, i_stat)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        u, i, raw, u_stat, i_stat = ctx.saved_tensors
+        g = _f32c(g)
+        B, N, D = i.shape
+        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None
+        di = torch.empty_like(i) if ctx.needs_input_grad[1] else None
+        call('sbr_score_cos_bwd', ptr(g), ptr(u), ptr(i), ptr(raw), ptr(u_stat), ptr(i_stat), ptr(du), ptr(di), B, N, D, ctx.mu, stream())
+        return du, di, None, None
+
+
+def floor_scores_(scores: torch.Tensor, mu: float) -> torch.Tensor:
+    """In place ``scores[scores < mu] = mu`` (sgd_alg.py:1241) over a 2-D score matrix with unit column stride; NaN stays."""
+    _need_cuda(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError('floor_scores_: needs a float32 [n, n_cols] matrix with unit column stride')
+    call('sbr_floor_scores', ptr(scores), scores.shape[0], scores.shape[1], scores.stride(0), mu, stream())
+    return scores
+
+
+def l2_normalize_rows(x: torch.Tensor, eps: float = COS_EPS) -> torch.Tensor:
+    """x / max(||x||_2, eps) per row, no autograd (the evaluation forms of the cosine scorer)."""
+    _need_cuda(x)
+    x = _f32c(x)
+    y = torch.empty_like(x)
+    inv = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
+    call('sbr_l2norm_fwd', ptr(x), ptr(y), ptr(inv), x.shape[0], x.shape[1], eps, stream())
+    return y
+
+
+class ScoreCosAllFn(Function):
+    """The all-pairs evaluation form of DeepMF's scorer (sgd_alg.py:1238-1242 on u [Bu, D] x i [I, D], eval/eval.py:216): both sides
+    normalised by ``sbr_l2norm_fwd`` (eps 1e-8), the all-pairs GEMM, then the floor — before the caller's exclusion mask, so excluded
+    entries stay -inf. Evaluation only: it has no backward."""
+
+    @staticmethod
+    def forward(ctx, u, i, mu: float):
+        _need_cuda(u, i)
+        out = linear_nt(l2_normalize_rows(u), l2_normalize_rows(i))
+        ctx.mark_non_differentiable(out)
+        return floor_scores_(out, mu)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise RuntimeError('ScoreCosAllFn is the evaluation form (no_grad); train through ScoreCosFn')
+
+
+def score_cos_all(u: torch.Tensor, i: torch.Tensor, mu: float) -> torch.Tensor:
+    return ScoreCosAllFn.apply(u, i, mu)
 
 
 class LookupFn(Function):

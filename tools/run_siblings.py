@@ -7,6 +7,8 @@ import numpy as np, torch
 import sibrar_amd as S
 import bench
 from oracle import model_ref, losses_ref, train_ref
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+import deepmf_ref
 
 dev = 'cuda:0'
 cores = bench.host_cores()
@@ -21,6 +23,7 @@ CONFS = {
     'dropoutnet': dict(user=dict(features=[], preference_layers=[128], common_hidden_layers=[128]),
                        item=dict(features=[dict(feature_name='text', embedding_dim=64), dict(feature_name='genres', embedding_dim=16)],
                                  preference_layers=[128], common_hidden_layers=[128]), shared_common_dim=64),
+    'dmf': dict(u_mid_layers=[128], i_mid_layers=[128], final_dimension=64),
 }
 which = [a for a in sys.argv[1:] if not a.startswith('--')] or list(CONFS)
 inter = ds.user_sampling_matrix_train
@@ -62,6 +65,8 @@ for name in which:
             elif name == 'ifeatmf':
                 logits, reg = model_ref.feature_mf_forward(sd, 'item', it_t['text'], u, i, embedding_dim=64, intermediate_layers=[128],
                                                             aggregate_for_rec=False, temperature=0.1)
+            elif name == 'dmf':
+                logits, reg = deepmf_ref.forward(sd, inter, inter_t, u, i, mu=1e-6), 0.
             else:
                 cfg = dict(CONFS['dropoutnet'])
                 logits = model_ref.dropoutnet_forward(sd, cfg, {}, it_t, inter, inter_t, u, i, rng.choice([1, 2], size=len(u)),
