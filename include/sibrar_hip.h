@@ -271,6 +271,30 @@ int sbr_score_cos_bwd(const float* G, const float* U, const float* I, const floa
 /* the floor of the all-pairs evaluation form — algorithms/sgd_alg.py:1241 on the [n, n_cols] score matrix of eval/eval.py:216
  * (row stride ld), in place: x[x < mu] = mu, NaN left alone. Applied before the exclusion mask (eval/eval.py:219-220). */
 int sbr_floor_scores(float* scores, long n, long n_cols, long ld, float mu, void* stream);
+/* ProtoMF's similarity to the prototypes — algorithms/sgd_alg.py:48-59 (compute_shifted_cosine_sim) behind the lookups of
+ * sgd_alg.py:381-382, 486-488, with the regularisers of sgd_alg.py:394-399, 505-510 (additive to ABI 4; csrc/proto_sim.hip):
+ *   e = W[rows[j], :] (rows NULL: row j; the gather is fused)      sim_out[j, p] = clamp(1 + e^ . p^, 0, 2),  x^ = x / max(|x|, 1e-12)
+ *   *proto_loss = mean_p min_j (2 - sim)      *batch_loss = mean_j min_p (2 - sim)      (device scalars, no host sync)
+ * 1 <= D <= 512, 2 <= n_proto <= 256 (anything else fails through sbr_last_error), R = 0 returns SBR_OK. Saved for the backward pass:
+ * cos_raw [R, P] (the un-clamped cosine), row_stat [R, 2] and proto_stat [P, 2] = {max(|x|, eps), |x| >= eps ? 1 : 0},
+ * row_best [R] = argmin_p, col_best_row [P] = argmin_j with col_best_val [P] its value.
+ * TIE RULE: a minimum attained more than once goes to the lowest index (lowest p for a row, lowest j for a prototype); the values
+ * compared are the fp32 distances 2 - sim.
+ * Evaluation form: cos_raw, row_stat, proto_stat may be NULL, and row_best, col_best_val, col_best_row, proto_loss, batch_loss are
+ * NULL together. workspace: sbr_proto_sim_workspace(R, D, n_proto, 0) bytes (backward: (..., 1)).
+ * Backward: G [R, P] is the upstream gradient of sim, *g_proto / *g_batch (device scalars, NULL = 0) those of the two losses; the
+ * arg-min contributions -g_proto / P and -g_batch / R are added inside the kernel, the clamp passes the gradient where
+ * 0 <= 1 + cos <= 2 (torch.clamp), a norm below eps takes torch's clamp_min gradient. dE [R, D] is the gradient of the gathered rows
+ * (scatter it with sbr_scatter_add_rows), dP [P, D] that of the prototypes; either may be NULL.
+ * One form only: per-workgroup partials folded in a fixed order, no atomics — valid in deterministic mode. */
+long sbr_proto_sim_workspace(long R, int D, int n_proto, int backward);
+int sbr_proto_sim_fwd(const float* W, long ldw, const int* rows, long R, int D, const float* P, int n_proto, float* sim_out,
+                      float* cos_raw, float* row_stat, float* proto_stat, int* row_best, float* col_best_val, int* col_best_row,
+                      float* proto_loss, float* batch_loss, void* workspace, long workspace_bytes, void* stream);
+int sbr_proto_sim_bwd(const float* G, const float* g_proto, const float* g_batch, const float* W, long ldw, const int* rows, long R,
+                      int D, const float* P, int n_proto, const float* cos_raw, const float* row_stat, const float* proto_stat,
+                      const int* row_best, const int* col_best_row, float* dE, float* dP, void* workspace, long workspace_bytes,
+                      void* stream);
 /* SGDBaseline — algorithms/sgd_alg.py:110-119 */
 int sbr_bias_score_fwd(const float* user_bias, const float* item_bias, const float* global_bias, const long* u, const long* i,
                        float* out, long B, int N, void* stream);

@@ -16,6 +16,7 @@ from .sbnet import (FeatureEmbedding, ItemFeatureMatrixFactorization, SGDBasedRe
                     general_weight_init)
 from .dropoutnet import DropoutNet, DropoutNetEntity                                      # noqa: F401
 from .deepmf import DeepMatrixFactorization                                                # noqa: F401
+from .protomf import IProtoMF, PrototypeWrapper, UIProtoMF, UProtoMF                       # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
                      RecSampledSoftmaxLoss, RecommenderSystemLoss, RecommenderSystemLossesEnum)
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
@@ -41,6 +42,8 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
         torch.cuda.manual_seed_all(seed)
     ops.set_deterministic(deterministic)
 
-# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf -> class (algorithms/algorithms_utils.py:14,17,34,36)
+# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf -> class
+# (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
-              'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization}
+              'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
+              'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF}

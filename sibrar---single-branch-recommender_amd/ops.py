@@ -752,6 +752,119 @@ class LookupFn(Function):
         return dW, None
 
 
+class GatherLinearFn(Function):
+    """nn.Linear(bias=False) on looked-up rows — UIProtoMF's projections, sgd_alg.py:575, 581: ``table[idx] @ weight^T`` with the
+    gather fused into the GEMM; the table gradient is the dense scatter-add of ``LookupFn``."""
+
+    @staticmethod
+    def forward(ctx, table, idx, weight):
+        _need_cuda(table, idx, weight)
+        if table.stride(-1) != 1:
+            table = table.contiguous()
+        w = weight if weight.stride(1) == 1 else weight.contiguous()
+        rows = idx.reshape(-1).to(torch.int32).contiguous()
+        out = linear_nt(table, w, a_idx=rows)
+        ctx.save_for_backward(table, rows, w)
+        return out.view(*idx.shape, w.shape[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        table, rows, w = ctx.saved_tensors
+        n, D = rows.numel(), table.shape[1]
+        g = _f32c(g).reshape(n, w.shape[0])
+        d_table = None
+        if ctx.needs_input_grad[0]:
+            dx = matmul_nn(g, w)
+            d_table = torch.zeros(table.shape, device=g.device, dtype=torch.float32)
+            call('sbr_scatter_add_rows', ptr(dx), D, None, ptr(rows), ptr(d_table), D, n, D, stream())
+        dw = matmul_tn(g, table, b_idx=rows) if ctx.needs_input_grad[2] else None
+        return d_table, None, dw
+
+
+# ---- ProtoMF: shifted cosine similarity to the prototypes -----------------------------------------------------------------------------
+PROTO_MAX_D, PROTO_MAX_P = 512, 256          # csrc/proto_sim.hip
+
+
+def _proto_operands(table, idx, prototypes, who):
+    if table.dim() != 2 or prototypes.dim() != 2 or table.shape[1] != prototypes.shape[1]:
+        raise ValueError(f'{who}: table {tuple(table.shape)} and prototypes {tuple(prototypes.shape)} must be matrices of one width')
+    D, P = int(table.shape[1]), int(prototypes.shape[0])
+    if not (1 <= D <= PROTO_MAX_D and 2 <= P <= PROTO_MAX_P):
+        raise ValueError(f'{who}: needs 1 <= embedding_dim <= {PROTO_MAX_D} and 2 <= n_prototypes <= {PROTO_MAX_P}, got {D} and {P}')
+    _need_cuda(table, idx, prototypes)
+    table = _f32c(table) if table.stride(-1) != 1 or table.dtype != torch.float32 else table
+    rows = None if idx is None else idx.reshape(-1).to(torch.int32).contiguous()
+    R = table.shape[0] if rows is None else rows.numel()
+    return table, rows, _f32c(prototypes), R, D, P
+
+
+def _proto_ws(device, R, D, P, backward):
+    n = int(lib().sbr_proto_sim_workspace(R, D, P, 1 if backward else 0))
+    return torch.empty(max(n, 8), device=device, dtype=torch.uint8)
+
+
+class ProtoSimFn(Function):
+    """ProtoMF's prototype side in one op — sgd_alg.py:48-59 (compute_shifted_cosine_sim) on ``table[idx]`` against ``prototypes``
+    (sgd_alg.py:381-382, 486-488) plus the two regularisers of compute_reg_losses (sgd_alg.py:394-399, 505-510):
+    ``-> (sim [*idx.shape, P], proto_loss, batch_loss)`` with proto_loss = mean_p min_j (2 - sim), batch_loss = mean_j min_p (2 - sim) as
+    device scalars. The lookup is fused (no gathered or normalised copy is written); the backward pass routes the arg-min gradients
+    inside the kernel (ties: the lowest index) and returns the dense table gradient, as ``LookupFn`` does. One fixed-order form."""
+
+    @staticmethod
+    def forward(ctx, table, idx, prototypes):
+        table, rows, protos, R, D, P = _proto_operands(table, idx, prototypes, 'ProtoSimFn')
+        dev = table.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        sim, cos = torch.empty(R, P, **f32), torch.empty(R, P, **f32)
+        row_stat, proto_stat = torch.empty(R, 2, **f32), torch.empty(P, 2, **f32)
+        row_best = torch.empty(R, device=dev, dtype=torch.int32)
+        col_val, col_row = torch.empty(P, **f32), torch.empty(P, device=dev, dtype=torch.int32)
+        proto_loss, batch_loss = torch.zeros((), **f32), torch.zeros((), **f32)
+        ws = _proto_ws(dev, R, D, P, False)
+        _timed(('proto_sim_fwd', R, D, P),
+               lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(sim), ptr(cos),
+                            ptr(row_stat), ptr(proto_stat), ptr(row_best), ptr(col_val), ptr(col_row), ptr(proto_loss), ptr(batch_loss),
+                            ptr(ws), ws.numel(), stream()))
+        ctx.save_for_backward(table, rows, protos, cos, row_stat, proto_stat, row_best, col_row)
+        shape = (R,) if idx is None else tuple(idx.shape)
+        return sim.view(*shape, P), proto_loss, batch_loss
+
+    @staticmethod
+    def backward(ctx, g_sim, g_proto, g_batch):
+        table, rows, protos, cos, row_stat, proto_stat, row_best, col_row = ctx.saved_tensors
+        (R, P), D = cos.shape, table.shape[1]
+        g_sim = _f32c(g_sim).reshape(R, P)
+        g_proto, g_batch = (None if g is None else g.reshape(1).float().contiguous() for g in (g_proto, g_batch))
+        need_t, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        dE = torch.empty(R, D, device=cos.device, dtype=torch.float32) if need_t else None
+        dP = torch.empty(P, D, device=cos.device, dtype=torch.float32) if need_p else None
+        ws = _proto_ws(cos.device, R, D, P, True) if need_p and R > 0 else None
+        _timed(('proto_sim_bwd', R, D, P),
+               lambda: call('sbr_proto_sim_bwd', ptr(g_sim), ptr(g_proto), ptr(g_batch), ptr(table), table.stride(0), ptr(rows), R, D,
+                            ptr(protos), P, ptr(cos), ptr(row_stat), ptr(proto_stat), ptr(row_best), ptr(col_row), ptr(dE), ptr(dP),
+                            ptr(ws), 0 if ws is None else ws.numel(), stream()))
+        d_table = None
+        if need_t:
+            d_table = torch.zeros(table.shape, device=cos.device, dtype=torch.float32)
+            if rows is None:
+                d_table.copy_(dE)
+            else:
+                call('sbr_scatter_add_rows', ptr(dE), D, None, ptr(rows), ptr(d_table), D, R, D, stream())
+        return d_table, None, dP
+
+
+def proto_sim(table: torch.Tensor, idx: Optional[torch.Tensor], prototypes: torch.Tensor) -> torch.Tensor:
+    """The evaluation form of ``ProtoSimFn`` (no autograd, no arg-mins): clamp(1 + cos(table[idx], prototypes), 0, 2) as
+    [*idx.shape, P]; ``idx`` None: every row of ``table``."""
+    table, rows, protos, R, D, P = _proto_operands(table.detach(), idx, prototypes.detach(), 'proto_sim')
+    sim = torch.empty(R, P, device=table.device, dtype=torch.float32)
+    ws = _proto_ws(table.device, R, D, P, False)
+    _timed(('proto_sim_fwd', R, D, P),
+           lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(sim), None, None, None,
+                        None, None, None, None, None, ptr(ws), ws.numel(), stream()))
+    return sim.view(*((R,) if idx is None else tuple(idx.shape)), P)
+
+
 class BiasScoreFn(Function):
     """out[b, n] = base[b, n] + user_bias[u[b]] + item_bias[i[b, n]] + global_bias (sgd_alg.py:186-194, 110-119); every term
     optional (None). Bias tables are 1-D float views of the [n, 1] embedding weights. u None: row b; i None: column n."""

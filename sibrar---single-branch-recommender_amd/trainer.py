@@ -97,6 +97,7 @@ class Trainer:
         self.best_value = log_dict['max_optimizing_metric'] = log_dict[self.optimizing_metric]
         self.best_epoch = log_dict['best_epoch'] = -1
         self.best_metrics = log_dict
+        log_dict.update(self._post_val(-1))
         print(f'Init - {self.optimizing_metric}={self.best_value:.4f}')
         if self.model_path:
             self.pointer_to_model.save_model_to_path(self.model_path)
@@ -112,6 +113,7 @@ class Trainer:
             if self.evaluate_train_loader:
                 epoch_losses.update(**self.train_val())
             metrics_values = self.val()
+            metrics_values.update(self._post_val(epoch))
             curr_value = metrics_values[self.optimizing_metric]
             if curr_value > self.best_value:
                 self.best_value = metrics_values['max_optimizing_metric'] = curr_value
@@ -124,6 +126,12 @@ class Trainer:
                 metrics_values['max_optimizing_metric'] = self.best_value
                 current_patience -= 1
         return self.best_metrics
+
+    def _post_val(self, epoch: int) -> dict:
+        """trainer.py:108-109, 161-162: a post-validation function that is specific to the model (ProtoMF's prototype statistics), merged
+        into the epoch's dictionary; -1 names the initial validation."""
+        post_val = getattr(self.pointer_to_model, 'post_val', None)
+        return dict(post_val(epoch)) if callable(post_val) else {}
 
     def train(self):
         return self._train()
