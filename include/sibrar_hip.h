@@ -63,7 +63,9 @@ int sbr_scatter_add_rows_det(const float* dOut, long ldo, const int* in_idx, con
  * mode 1 (NN): C[m, n] = sum_k A[ai(m), k] * B[k, n]                        autograd of nn.Linear w.r.t. its input.
  * mode 2 (TN): C[m, n] += sum_k A[ak(k), m] * B[bk(k), n]                   autograd of nn.Linear w.r.t. its weight; split
  *              over k with float atomics, so C must be zero-initialised and accumulate_atomic must be 1.
- * a_idx / b_idx / c_idx: optional int32 row maps (NULL = identity). */
+ * a_idx / b_idx / c_idx: optional int32 row maps (NULL = identity).
+ * K = 0 is an empty sum: modes 0 and 1 store act(bias[n]) (act(0) without a bias), mode 2 adds nothing and launches nothing (C keeps
+ * what it holds; valid in deterministic mode and not counted by sbr_nondeterministic_launches); sbr_gemm_tn_f32 stores zeros. M = 0 or N = 0 returns at once. */
 int sbr_gemm_f32(int mode, const float* A, long lda, const int* a_idx, const float* B, long ldb, const int* b_idx,
                  const float* bias, float* C, long ldc, const int* c_idx, int M, int N, int K, int act,
                  int accumulate_atomic, void* stream);
@@ -109,7 +111,9 @@ int sbr_splitk_reduce_multi_fin(int count, const void* const* slabs, const void*
  * mode 0 (NT): C = act(A W^T + bias) — nn.Linear forward, modules/polylinear.py:51,63-72; mode 1 (NN): C = A W — its autograd
  * w.r.t. the input. Y != NULL (mode 1): C = (A W) * act'(Y), the gradient at the pre-activation of the layer in front whose OUTPUT
  * is Y, and colsum_ws (17 * 128 doubles, contract of sbr_colsum; may be NULL) receives the pending column sums of C — that layer's
- * bias gradient, completed by sbr_colred_finish. */
+ * bias gradient, completed by sbr_colred_finish. A and W: 16-byte aligned base, leading dimension a multiple of 4; C and Y are
+ * accessed one float per lane and take any base and leading dimension (the same holds for C / Y of sbr_gemm_split_f32, and for C of
+ * sbr_gemm_split_proj_f32 and sbr_gemm_split_wide_f32). */
 int sbr_gemm_wres_supported(long M, int N, int K);
 int sbr_gemm_wres_f32(int mode, const float* A, long lda, const float* W, long ldw, const float* bias, float* C, long ldc, long M, int N,
                       int K, int act, const float* Y, long ldy, double* colsum_ws, void* stream);

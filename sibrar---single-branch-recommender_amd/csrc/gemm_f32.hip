@@ -326,6 +326,10 @@ extern "C" int sbr_gemm_f32(int mode, const float* A, long lda, const int* a_idx
   if (M == 0 || N == 0) return SBR_OK;
   SBR_REQUIRE(A && B && C, "sbr_gemm_f32: null operand");
   SBR_REQUIRE(!(accumulate_atomic && act != SBR_ACT_NONE), "sbr_gemm_f32: activation with atomic accumulate");
+  if (mode == 2 && K == 0) {                                       // an empty sum adds nothing: C keeps what it holds, nothing is launched
+    SBR_REQUIRE(accumulate_atomic, "sbr_gemm_f32: TN mode requires a zero-initialised C and accumulate_atomic=1");
+    return SBR_OK;                                                 // (and nothing is counted as, or refused for being, arrival-order work)
+  }
   if (accumulate_atomic) SBR_ARRIVAL_ORDER("sbr_gemm_f32");          // (fixed-order forms: sbr_gemm_tn_f32, sbr_gemm_nt_splitk_f32)
   hipStream_t s = (hipStream_t)stream;
   GemmArgs g;

@@ -261,7 +261,8 @@ extern "C" int sbr_gemm_wres_f32(int mode, const float* A, long lda, const float
   if (M == 0) return SBR_OK;
   SBR_REQUIRE(sbr_gemm_wres_supported(M, N, K), "sbr_gemm_wres_f32: shape %ld x %d x %d not supported (N = K = 128)", M, N, K);
   SBR_REQUIRE(A && W && C, "sbr_gemm_wres_f32: null operand");
-  SBR_REQUIRE(wr_al16(A, lda) && wr_al16(W, ldw) && (ldc & 3) == 0, "sbr_gemm_wres_f32: operands must be 16-byte aligned");
+  // A goes through the LDS DMA and W through 16-byte loads; C (and Y) are written / read one float per lane: any base and stride
+  SBR_REQUIRE(wr_al16(A, lda) && wr_al16(W, ldw), "sbr_gemm_wres_f32: operands must be 16-byte aligned");
   SBR_REQUIRE(!(Y && mode == 0) && !(colsum_ws && !Y) && !(Y && bias), "sbr_gemm_wres_f32: Y / colsum_ws belong to mode 1 without bias");
   WresArgs g;
   g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.C = C; g.ldc = ldc; g.M = M; g.act = act; g.Y = Y; g.ldy = ldy;

@@ -11,6 +11,23 @@ DEV = 'cuda'
 U32 = 2.0 ** -24
 NAN = float('nan')
 GUARD = 64                                   # guard elements in front of and behind a view (a multiple of 4: keeps the alignment)
+EXP_ULP = 4 * U32                            # allowed relative error of one expf / logf / tanhf call (2 ulp)
+SELU_A, SELU_S = 1.6732632423543772848170429916717, 1.0507009873554804934193349852946
+SELU_AF, SELU_SF = float(np.float32(SELU_A)), float(np.float32(SELU_S))
+LIP = {0: 1.0, 1: 1.0, 2: 1.0, 3: 0.25, 4: SELU_SF * SELU_AF}        # Lipschitz constants of the activations
+
+
+def ref_act(pre, act):
+    """the activation codes of include/sibrar_hip.h in the dtype of ``pre``, with the fp32 selu constants of the kernels"""
+    if act == 1:
+        return torch.relu(pre)
+    if act == 2:
+        return torch.tanh(pre)
+    if act == 3:
+        return torch.sigmoid(pre)
+    if act == 4:
+        return SELU_SF * torch.where(pre > 0, pre, SELU_AF * torch.expm1(pre))
+    return pre
 
 
 def S():

@@ -21,16 +21,13 @@ import numpy as np
 import pytest
 import torch
 
-from hip_testutil import DEV, NAN, U32, S, _L, _assert_bits, _assert_bound, _Buf, _p, _rand, call, stream
+from hip_testutil import (DEV, EXP_ULP, LIP, NAN, SELU_A, SELU_AF, SELU_S, SELU_SF, U32, S, _L, _assert_bits, _assert_bound, _Buf, _p, _rand, call,
+                          ref_act, stream)
 
 pytestmark = pytest.mark.gpu
 U64 = 2.0 ** -53
-EXP_ULP = 4 * U32                            # allowed relative error of one expf / logf / tanhf call (2 ulp)
 EPS, MOM = 1e-5, 0.1
 EPS32, MOM32 = float(np.float32(EPS)), float(np.float32(MOM))
-SELU_A, SELU_S = 1.6732632423543772848170429916717, 1.0507009873554804934193349852946
-SELU_AF, SELU_SF = float(np.float32(SELU_A)), float(np.float32(SELU_S))
-LIP = {0: 1.0, 1: 1.0, 2: 1.0, 3: 0.25, 4: SELU_SF * SELU_AF}        # Lipschitz constants of the activations
 
 
 def _dd(t):
@@ -77,18 +74,6 @@ def _err(fn, *args):
 # =================================================================================================================================
 # float64 references and bounds (imported by tests/test_tail_refs_cpu.py)
 # =================================================================================================================================
-def ref_act(pre, act):
-    if act == 1:
-        return torch.relu(pre)
-    if act == 2:
-        return torch.tanh(pre)
-    if act == 3:
-        return torch.sigmoid(pre)
-    if act == 4:
-        return SELU_SF * torch.where(pre > 0, pre, SELU_AF * torch.expm1(pre))
-    return pre
-
-
 def ref_act_grad_from_out(y, act):
     """d act / d pre-activation through the activation's OUTPUT (float64), with the fp32 selu constants of the kernels"""
     if act == 1:
