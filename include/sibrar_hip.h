@@ -299,6 +299,35 @@ int sbr_proto_sim_bwd(const float* G, const float* g_proto, const float* g_batch
                       int D, const float* P, int n_proto, const float* cos_raw, const float* row_stat, const float* proto_stat,
                       const int* row_best, const int* col_best_row, float* dE, float* dP, void* workspace, long workspace_bytes,
                       void* stream);
+/* ACF's anchor mixing — algorithms/sgd_alg.py:261-276 (ACF.get_user_representations / get_item_representations: lookup, e @ anchors^T,
+ * softmax, c @ anchors) with the two entropy regularisers of ACF.forward, sgd_alg.py:246-254, whose exclusiveness term is
+ * entropy_from_softmax, sgd_alg.py:76-85 (additive to ABI 4; csrc/anchor_mix.hip):
+ *   e = W[rows[j], :] (rows NULL: row j; the gather is fused)     s = e . A^T     c_out[j, :] = softmax(s[j, :]) (max-subtracted)
+ *   r_out[j, :] = c[j, :] . A      lse_out[j] = logsumexp_k s[j, k]
+ *   *exc_loss = mean_j H_j, H_j = -sum_k c[j, k] (s[j, k] - lse[j])       *inc_loss = log K + sum_k q_k log q_k,
+ *   q_out[k] = sum_j c[j, k] / sum_jk c[j, k]       dinc_out[k] = log q_k / sum_jk c[j, k] (d inc / d c[j, k] up to per-row constants)
+ * 1 <= D <= 512, 2 <= n_anchors <= 256 (anything else fails through sbr_last_error), R = 0 returns SBR_OK and launches nothing.
+ * Training form: every output. Evaluation / user-side form: q_out, dinc_out, exc_loss, inc_loss NULL together (no workspace needed),
+ * and any of r_out, c_out, lse_out may be NULL as long as r_out or c_out is given. The logits s are never written; log c is never
+ * taken (c underflows to exact zeros at large D and K; s - lse stays finite).
+ * NaN CONTRACT (the reference's): a column of c that is 0 in every row gives q_k == 0 and *inc_loss = NaN (0 log 0), and so are the
+ * gradients through g_inc; nothing is clamped. r, c, lse and *exc_loss do not depend on q.
+ * workspace: sbr_anchor_mix_workspace(R, D, n_anchors, 0) bytes (backward: (..., 1)); 0 for a shape outside the range.
+ * Backward: G [R, D] is the upstream gradient of r, *g_exc / *g_inc (device scalars, NULL = 0; both NULL: the user-side form, lse and
+ * dinc are not read) those of the two losses. c is not differentiable on its own. ds = softmax backward of
+ * dc = G . A^T + g_inc dinc[k], plus the exclusiveness term -g_exc / R c (s - lse + H) taken with respect to s directly (s is
+ * recomputed); the gradient through the denominator sum_jk c is a per-row constant of dc and vanishes in the softmax backward.
+ * dE [R, D] = ds . A is the gradient of the gathered rows (scatter it with sbr_scatter_add_rows), dA [K, D] = c^T . G + ds^T . e that of
+ * the anchors; either may be NULL.
+ * One form only: per-workgroup partials (column sums of c, entropy sums, dA) folded in a fixed order, no atomics; grid and split
+ * counts depend on (R, D, n_anchors) only — valid in deterministic mode. */
+long sbr_anchor_mix_workspace(long R, int D, int n_anchors, int backward);
+int sbr_anchor_mix_fwd(const float* W, long ldw, const int* rows, long R, int D, const float* A, int n_anchors, float* r_out,
+                       float* c_out, float* lse_out, float* q_out, float* dinc_out, float* exc_loss, float* inc_loss, void* workspace,
+                       long workspace_bytes, void* stream);
+int sbr_anchor_mix_bwd(const float* G, const float* g_exc, const float* g_inc, const float* W, long ldw, const int* rows, long R,
+                       int D, const float* A, int n_anchors, const float* c, const float* lse, const float* dinc, float* dE, float* dA,
+                       void* workspace, long workspace_bytes, void* stream);
 /* SGDBaseline — algorithms/sgd_alg.py:110-119 */
 int sbr_bias_score_fwd(const float* user_bias, const float* item_bias, const float* global_bias, const long* u, const long* i,
                        float* out, long B, int N, void* stream);

@@ -17,6 +17,7 @@ from .sbnet import (FeatureEmbedding, ItemFeatureMatrixFactorization, SGDBasedRe
 from .dropoutnet import DropoutNet, DropoutNetEntity                                      # noqa: F401
 from .deepmf import DeepMatrixFactorization                                                # noqa: F401
 from .protomf import IProtoMF, PrototypeWrapper, UIProtoMF, UProtoMF                       # noqa: F401
+from .acf import ACF                                                                        # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
                      RecSampledSoftmaxLoss, RecommenderSystemLoss, RecommenderSystemLossesEnum)
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
@@ -42,8 +43,8 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
         torch.cuda.manual_seed_all(seed)
     ops.set_deterministic(deterministic)
 
-# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf -> class
+# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .acf -> class
 # (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
-              'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF}
+              'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'acf': ACF}

@@ -335,12 +335,19 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
             'fp16_fused': (ops.cast_f16, ops.cast_f16, ops.score_topk_f16),
             'fp32_fused': (ops.split_bf16x3, lambda u: u, ops.score_topk_f32s),
         }
-        if scorer in fused_routes and (not plain or not ops.score_topk_fused_supported(scorer, int(i_repr.shape[1]), kmax, fused_max_k,
-                                                                                       fused_max_d)):
-            logging.info(f'{scorer} scorer: k={kmax}, item representation {"tuple" if not plain else tuple(i_repr.shape)} outside '
-                         f'the fused kernel, using the fp32 path')
+        # a tuple item side is scored by the fused kernels only if the model names the one matrix its dot-product score uses (ACF:
+        # ``fused_score_transform()[0]`` picks i_repr[0]); every other tuple model scores through its own combine on the fp32 path
+        fused_items = i_repr if plain else None
+        if not plain and scorer in fused_routes and hasattr(alg, 'fused_score_transform'):
+            pick = alg.fused_score_transform()[0]
+            picked = pick(i_repr) if pick is not None else None
+            fused_items = picked if torch.is_tensor(picked) else None
+        if scorer in fused_routes and (fused_items is None or not ops.score_topk_fused_supported(scorer, int(fused_items.shape[1]), kmax,
+                                                                                                 fused_max_k, fused_max_d)):
+            logging.info(f'{scorer} scorer: k={kmax}, item representation {"tuple" if fused_items is None else tuple(fused_items.shape)} '
+                         f'outside the fused kernel, using the fp32 path')
             scorer = 'fp32'
-        if scorer == 'fp32_fused' and not ops.split_bf16x3_supported(i_repr):
+        if scorer == 'fp32_fused' and not ops.split_bf16x3_supported(fused_items):
             # an inf / NaN (or > 3.38e38) item value splits into NaN planes: every score of that item would be NaN in the fused kernel
             logging.info('fp32_fused scorer: non-finite item representations, using the fp32 path')
             scorer = 'fp32'
@@ -355,11 +362,11 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
             items_fn, users_fn, finish_fn = transform()
         if fused:
             item_operand, user_operand, score_fused = fused_routes[scorer]
-            if scorer == 'fp32_fused' and int(i_repr.shape[1]) == ops.FUSED_MAX_D:
+            if scorer == 'fp32_fused' and int(fused_items.shape[1]) == ops.FUSED_MAX_D:
                 score_fused = ops.score_topk_f32s_d256
-            if items_fn is not None:
-                i_repr = items_fn(i_repr)
-            i_op = item_operand(i_repr)                             # made once per call: fp16 [I, D] or three bf16 planes [3, I, D]
+            if items_fn is not None and plain:                      # (a tuple side has been through items_fn above)
+                i_repr = fused_items = items_fn(i_repr)
+            i_op = item_operand(fused_items)                        # made once per call: fp16 [I, D] or three bf16 planes [3, I, D]
         if user_chunk is not None:
             bs = int(user_chunk)
         elif fused:

@@ -865,6 +865,114 @@ def proto_sim(table: torch.Tensor, idx: Optional[torch.Tensor], prototypes: torc
     return sim.view(*((R,) if idx is None else tuple(idx.shape)), P)
 
 
+def cosine_sim(table: torch.Tensor, idx: Optional[torch.Tensor], others: torch.Tensor) -> torch.Tensor:
+    """sgd_alg.py:62-73 (compute_cosine_sim): clamp(cos(table[idx], others), -1, 1) as [*idx.shape, P] — the un-clamped cosine that
+    ``sbr_proto_sim_fwd`` writes next to the shifted similarity, clamped in place. No autograd (ACF's post_val statistics)."""
+    table, rows, others, R, D, P = _proto_operands(table.detach(), idx, others.detach(), 'cosine_sim')
+    sim = torch.empty(R, P, device=table.device, dtype=torch.float32)
+    cos = torch.empty(R, P, device=table.device, dtype=torch.float32)
+    ws = _proto_ws(table.device, R, D, P, False)
+    _timed(('proto_sim_fwd', R, D, P),
+           lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(others), P, ptr(sim), ptr(cos), None, None,
+                        None, None, None, None, None, ptr(ws), ws.numel(), stream()))
+    return cos.clamp_(min=-1., max=1.).view(*((R,) if idx is None else tuple(idx.shape)), P)
+
+
+# ---- ACF: softmax mixing of the anchors ------------------------------------------------------------------------------------------------
+ANCHOR_MAX_D, ANCHOR_MAX_K = 512, 256        # csrc/anchor_mix.hip
+ANCHOR_TILE, ANCHOR_MAX_WG = 64, 1024        # rows of a workgroup's tile, grid cap of either pass (AM_T, AM_MAX_WG)
+
+
+def _anchor_operands(table, idx, anchors, who):
+    if table.dim() != 2 or anchors.dim() != 2 or table.shape[1] != anchors.shape[1]:
+        raise ValueError(f'{who}: table {tuple(table.shape)} and anchors {tuple(anchors.shape)} must be matrices of one width')
+    D, K = int(table.shape[1]), int(anchors.shape[0])
+    if not (1 <= D <= ANCHOR_MAX_D and 2 <= K <= ANCHOR_MAX_K):
+        raise ValueError(f'{who}: needs 1 <= embedding_dim <= {ANCHOR_MAX_D} and 2 <= n_anchors <= {ANCHOR_MAX_K}, got {D} and {K}')
+    _need_cuda(table, idx, anchors)
+    table = _f32c(table) if table.stride(-1) != 1 or table.dtype != torch.float32 else table
+    rows = None if idx is None else idx.reshape(-1).to(torch.int32).contiguous()
+    R = table.shape[0] if rows is None else rows.numel()
+    return table, rows, _f32c(anchors), R, D, K
+
+
+def _anchor_ws(device, R, D, K, backward):
+    n = int(lib().sbr_anchor_mix_workspace(R, D, K, 1 if backward else 0))
+    return torch.empty(max(n, 8), device=device, dtype=torch.uint8)
+
+
+class AnchorMixFn(Function):
+    """One side of ACF in one op — sgd_alg.py:261-276 on ``table[idx]`` against ``anchors`` plus, with ``with_losses``, the two entropy
+    regularisers of ACF.forward (sgd_alg.py:246-254): ``-> (r [*idx.shape, D], c [*idx.shape, K], exc_loss, inc_loss)`` with
+    c = softmax(table[idx] @ anchors^T), r = c @ anchors, exc_loss = mean entropy_from_softmax(c, logits), inc_loss = log K - H(q) as
+    device scalars (zeros without ``with_losses``). ``c`` is marked NON-DIFFERENTIABLE: gradients flow through ``r`` and the two losses
+    only, which is every use the model makes of it. The lookup is fused and the logits are never written; the backward pass recomputes
+    them and returns the dense table gradient, as ``LookupFn`` does. A column of ``c`` that is zero in every row makes ``inc_loss``
+    NaN, as in the reference. One fixed-order form (valid in deterministic mode)."""
+
+    @staticmethod
+    def forward(ctx, table, idx, anchors, with_losses: bool):
+        table, rows, anc, R, D, K = _anchor_operands(table, idx, anchors, 'AnchorMixFn')
+        dev = table.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        r, c, lse = torch.empty(R, D, **f32), torch.empty(R, K, **f32), torch.empty(R, **f32)
+        exc, inc = torch.zeros((), **f32), torch.zeros((), **f32)
+        q = dinc = ws = None
+        if with_losses and R > 0:
+            q, dinc = torch.empty(K, **f32), torch.empty(K, **f32)
+            ws = _anchor_ws(dev, R, D, K, False)
+        if R > 0:
+            _timed(('anchor_mix_fwd', R, D, K),
+                   lambda: call('sbr_anchor_mix_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(anc), K, ptr(r), ptr(c), ptr(lse),
+                                ptr(q), ptr(dinc), ptr(exc) if q is not None else None, ptr(inc) if q is not None else None, ptr(ws),
+                                0 if ws is None else ws.numel(), stream()))
+        ctx.save_for_backward(table, rows, anc, c, lse, dinc)
+        ctx.with_losses = q is not None
+        shape = (R,) if idx is None else tuple(idx.shape)
+        c_out = c.view(*shape, K)
+        ctx.mark_non_differentiable(c_out)
+        return r.view(*shape, D), c_out, exc, inc
+
+    @staticmethod
+    def backward(ctx, g_r, _g_c, g_exc, g_inc):
+        table, rows, anc, c, lse, dinc = ctx.saved_tensors
+        (R, K), D = c.shape, table.shape[1]
+        g_r = _f32c(g_r).reshape(R, D)
+        if not ctx.with_losses:
+            g_exc = g_inc = None
+        g_exc, g_inc = (None if g is None else g.reshape(1).float().contiguous() for g in (g_exc, g_inc))
+        need_t, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        dE = torch.empty(R, D, device=c.device, dtype=torch.float32) if need_t else None
+        dA = torch.empty(K, D, device=c.device, dtype=torch.float32) if need_a else None
+        ws = _anchor_ws(c.device, R, D, K, True) if need_a and R > 0 else None
+        _timed(('anchor_mix_bwd', R, D, K),
+               lambda: call('sbr_anchor_mix_bwd', ptr(g_r), ptr(g_exc), ptr(g_inc), ptr(table), table.stride(0), ptr(rows), R, D, ptr(anc),
+                            K, ptr(c), ptr(lse), ptr(dinc), ptr(dE), ptr(dA), ptr(ws), 0 if ws is None else ws.numel(), stream()))
+        d_table = None
+        if need_t:
+            d_table = torch.zeros(table.shape, device=c.device, dtype=torch.float32)
+            if rows is None:
+                d_table.copy_(dE)
+            elif R > 0:
+                call('sbr_scatter_add_rows', ptr(dE), D, None, ptr(rows), ptr(d_table), D, R, D, stream())
+        return d_table, None, dA, None
+
+
+def anchor_mix(table: torch.Tensor, idx: Optional[torch.Tensor], anchors: torch.Tensor, want: str = 'r') -> torch.Tensor:
+    """The evaluation form of ``AnchorMixFn`` (no autograd, no losses): ``want='r'`` -> softmax(table[idx] @ anchors^T) @ anchors as
+    [*idx.shape, D]; ``want='c'`` -> the softmax itself as [*idx.shape, K]. ``idx`` None: every row of ``table``."""
+    if want not in ('r', 'c'):
+        raise ValueError(f"anchor_mix: want must be 'r' or 'c', got {want!r}")
+    table, rows, anc, R, D, K = _anchor_operands(table.detach(), idx, anchors.detach(), 'anchor_mix')
+    n = D if want == 'r' else K
+    out = torch.empty(R, n, device=table.device, dtype=torch.float32)
+    if R > 0:
+        _timed(('anchor_mix_fwd', R, D, K),
+               lambda: call('sbr_anchor_mix_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(anc), K, ptr(out) if want == 'r' else None,
+                            ptr(out) if want == 'c' else None, None, None, None, None, None, None, 0, stream()))
+    return out.view(*((R,) if idx is None else tuple(idx.shape)), n)
+
+
 class BiasScoreFn(Function):
     """out[b, n] = base[b, n] + user_bias[u[b]] + item_bias[i[b, n]] + global_bias (sgd_alg.py:186-194, 110-119); every term
     optional (None). Bias tables are 1-D float views of the [n, 1] embedding weights. u None: row b; i None: column n."""

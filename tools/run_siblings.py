@@ -8,6 +8,7 @@ import sibrar_amd as S
 import bench
 from oracle import model_ref, losses_ref, train_ref
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+import acf_ref
 import deepmf_ref
 
 dev = 'cuda:0'
@@ -24,6 +25,7 @@ CONFS = {
                        item=dict(features=[dict(feature_name='text', embedding_dim=64), dict(feature_name='genres', embedding_dim=16)],
                                  preference_layers=[128], common_hidden_layers=[128]), shared_common_dim=64),
     'dmf': dict(u_mid_layers=[128], i_mid_layers=[128], final_dimension=64),
+    'acf': dict(embedding_dim=64, n_anchors=20, delta_exc=1e-1, delta_inc=1e-2),
 }
 which = [a for a in sys.argv[1:] if not a.startswith('--')] or list(CONFS)
 inter = ds.user_sampling_matrix_train
@@ -67,6 +69,9 @@ for name in which:
                                                             aggregate_for_rec=False, temperature=0.1)
             elif name == 'dmf':
                 logits, reg = deepmf_ref.forward(sd, inter, inter_t, u, i, mu=1e-6), 0.
+            elif name == 'acf':
+                logits, other = acf_ref.forward(sd, CONFS['acf'], u, i)
+                reg = other['reg_loss']
             else:
                 cfg = dict(CONFS['dropoutnet'])
                 logits = model_ref.dropoutnet_forward(sd, cfg, {}, it_t, inter, inter_t, u, i, rng.choice([1, 2], size=len(u)),
