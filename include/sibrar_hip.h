@@ -328,6 +328,37 @@ int sbr_anchor_mix_fwd(const float* W, long ldw, const int* rows, long R, int D,
 int sbr_anchor_mix_bwd(const float* G, const float* g_exc, const float* g_inc, const float* W, long ldw, const int* rows, long R,
                        int D, const float* A, int n_anchors, const float* c, const float* lse, const float* dinc, float* dE, float* dA,
                        void* workspace, long workspace_bytes, void* stream);
+/* ECF's sparse affiliation of a row to its clusters — algorithms/sgd_alg.py:1020-1037 (ECF._generate_item_representations, the item
+ * side) and sgd_alg.py:988-1009 (ECF.get_user_representations, the user side); ECF is sgd_alg.py:891-1138 (additive to ABI 4;
+ * csrc/cluster_affil.hip). Two forms of one op, selected by which operand is NULL:
+ *   cosine form (t_in NULL): the rows are the whole table W [R, D] (row stride ldw, no index list) against Cl [n_clusters, D]:
+ *     t_out[r, k] = clamp(W_r^ . Cl_k^, -1, 1),  x^ = x / max(|x|, 1e-12)      (compute_cosine_sim, sgd_alg.py:62-73)
+ *   logit form (W and Cl NULL): t = t_in [R, n_clusters] is an input (D is ignored, t_out is not written)
+ *   m = 1 at the `top` largest entries of a row      p = softmax(t / temp)      mh = p + (m - p)      x_out = sigmoid(t) * mh
+ * mh is formed in fp32 as the reference forms it: exactly 0 off the mask, fl(p + fl(1 - p)) on it.
+ * TIE RULE: equal logits at the mask boundary go to the LOWEST cluster index (-0 == +0); torch.topk leaves the order of ties
+ * unspecified, so a reference run may pick another member of a tie.
+ * 1 <= D <= 512 (cosine form), 2 <= n_clusters <= 256, 1 <= top <= n_clusters, temp > 0: anything else fails through sbr_last_error
+ * and sbr_cluster_affil_workspace returns 0. R = 0 returns SBR_OK and launches nothing.
+ * Saved for the backward pass (may both be NULL: the evaluation form): row_state [R, 4] = {max_k t / temp, sum_k exp(t / temp - max),
+ * max(|W_r|, eps), |W_r| >= eps ? 1 : 0} (16-byte aligned) and mask [R, ceil(n_clusters / 4)] bytes (bits 0 .. 3 of byte q: m of clusters
+ * 4 q .. 4 q + 3; bits 4 .. 7: the [-1, 1] clamp was active there). Everything else is recomputed from t.
+ * workspace: sbr_cluster_affil_workspace(R, D, n_clusters, 0) bytes for the cosine form (backward: (..., 1)); the logit form needs none.
+ * Backward: G [R, C] = dL/dx; the mask carries no gradient (the reference detaches m - p):
+ *   dt_k = g_k s'(t_k) mh_k + p_k (g_k s(t_k) - sum_j p_j g_j s(t_j)) / temp,   s = sigmoid
+ * logit form: t is the forward input, dt_out [R, C] is written. Cosine form: t is the saved t_out, Gt [R, C] (may be NULL) is an upstream
+ * dL/dt_out added inside the kernel (the user side's gradient into the item logits); the sum passes where the clamp was not active
+ * (torch.clamp), a norm below eps takes torch's clamp_min gradient; dW [R, D] (row stride lddw) is written directly — the rows are the
+ * table — and dCl [C, D]; either may be NULL.
+ * One form only: dCl is one partial per workgroup folded in workgroup order, no atomics; the number of workgroups depends on
+ * (R, D, n_clusters) only — valid in deterministic mode, never a non-deterministic launch. */
+long sbr_cluster_affil_workspace(long R, int D, int n_clusters, int backward);
+int sbr_cluster_affil_fwd(const float* W, long ldw, const float* Cl, const float* t_in, long R, int D, int n_clusters, int top,
+                          float temp, float* t_out, float* x_out, float* row_state, unsigned char* mask, void* workspace,
+                          long workspace_bytes, void* stream);
+int sbr_cluster_affil_bwd(const float* G, const float* Gt, const float* W, long ldw, const float* Cl, const float* t, long R, int D,
+                          int n_clusters, float temp, const float* row_state, const unsigned char* mask, float* dW, long lddw,
+                          float* dCl, float* dt_out, void* workspace, long workspace_bytes, void* stream);
 /* SGDBaseline — algorithms/sgd_alg.py:110-119 */
 int sbr_bias_score_fwd(const float* user_bias, const float* item_bias, const float* global_bias, const long* u, const long* i,
                        float* out, long B, int N, void* stream);

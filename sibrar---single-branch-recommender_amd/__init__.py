@@ -18,6 +18,7 @@ from .dropoutnet import DropoutNet, DropoutNetEntity                            
 from .deepmf import DeepMatrixFactorization                                                # noqa: F401
 from .protomf import IProtoMF, PrototypeWrapper, UIProtoMF, UProtoMF                       # noqa: F401
 from .acf import ACF                                                                        # noqa: F401
+from .ecf import ECF, ecf_tag_matrix                                                        # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
                      RecSampledSoftmaxLoss, RecommenderSystemLoss, RecommenderSystemLossesEnum)
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
@@ -43,8 +44,8 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
         torch.cuda.manual_seed_all(seed)
     ops.set_deterministic(deterministic)
 
-# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .acf -> class
+# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .acf / .ecf -> class
 # (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
-              'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'acf': ACF}
+              'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'acf': ACF, 'ecf': ECF}

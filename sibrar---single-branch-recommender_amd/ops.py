@@ -973,6 +973,132 @@ def anchor_mix(table: torch.Tensor, idx: Optional[torch.Tensor], anchors: torch.
     return out.view(*((R,) if idx is None else tuple(idx.shape)), n)
 
 
+# ---- ECF: sparse affiliation of a row to its clusters ----------------------------------------------------------------------------------
+CLUSTER_MAX_D, CLUSTER_MAX_C = 512, 256      # csrc/cluster_affil.hip
+CLUSTER_TILE = 64                            # rows of a workgroup's tile (CA_T)
+
+
+def _cluster_operands(table, clusters, logits, top, temp, who):
+    """The operand checks of either form (``logits`` None: the cosine form on ``table`` x ``clusters``; otherwise the logit form):
+    shape and range errors are ``ValueError`` before anything touches the device."""
+    cosine = logits is None
+    if cosine:
+        if table is None or clusters is None or table.dim() != 2 or clusters.dim() != 2 or table.shape[1] != clusters.shape[1]:
+            raise ValueError(f'{who}: the cosine form needs a table and clusters that are matrices of one width')
+        D, C = int(table.shape[1]), int(clusters.shape[0])
+        if not 1 <= D <= CLUSTER_MAX_D:
+            raise ValueError(f'{who}: needs 1 <= embedding_dim <= {CLUSTER_MAX_D}, got {D}')
+    else:
+        if table is not None or clusters is not None:
+            raise ValueError(f'{who}: the logit form takes the logits alone')
+        if logits.dim() != 2:
+            raise ValueError(f'{who}: the logits {tuple(logits.shape)} must be a matrix [rows, n_clusters]')
+        D, C = 0, int(logits.shape[1])
+    if not 2 <= C <= CLUSTER_MAX_C:
+        raise ValueError(f'{who}: needs 2 <= n_clusters <= {CLUSTER_MAX_C}, got {C}')
+    if not (isinstance(top, numbers.Integral) and 1 <= int(top) <= C):
+        raise ValueError(f'{who}: needs an integer 1 <= top <= n_clusters = {C}, got {top!r}')
+    if not float(temp) > 0:
+        raise ValueError(f'{who}: needs temp > 0, got {temp!r}')
+    _need_cuda(table, clusters, logits)
+    if cosine:
+        table = _f32c(table) if table.stride(-1) != 1 or table.dtype != torch.float32 else table
+        return table, _f32c(clusters), None, int(table.shape[0]), D, C
+    logits = _f32c(logits)
+    return None, None, logits, int(logits.shape[0]), D, C
+
+
+def _cluster_ws(device, R, D, C, backward):
+    n = int(lib().sbr_cluster_affil_workspace(R, D, C, 1 if backward else 0))
+    return torch.empty(max(n, 16), device=device, dtype=torch.uint8)
+
+
+def _cluster_fwd(table, clusters, logits, R, D, C, top, temp, want_state):
+    dev = (table if logits is None else logits).device
+    f32 = dict(device=dev, dtype=torch.float32)
+    t = torch.empty(R, C, **f32) if logits is None else None
+    x = torch.empty(R, C, **f32)
+    state = torch.empty(R, 4, **f32) if want_state else None
+    mask = torch.empty(R, (C + 3) // 4, device=dev, dtype=torch.uint8) if want_state else None
+    if R > 0:
+        ws = _cluster_ws(dev, R, D, C, False) if logits is None else None
+        _timed(('cluster_affil_fwd', R, D, C),
+               lambda: call('sbr_cluster_affil_fwd', ptr(table), 0 if table is None else table.stride(0), ptr(clusters), ptr(logits), R, D, C,
+                            int(top), float(temp), ptr(t), ptr(x), ptr(state), ptr(mask), ptr(ws), 0 if ws is None else ws.numel(), stream()))
+    return t, x, state, mask
+
+
+class ClusterAffilFn(Function):
+    """ECF's affiliation of a row to its ``top`` clusters in one op each way (csrc/cluster_affil.hip) — sgd_alg.py:1020-1037 and
+    988-1009: ``x = sigmoid(t) * (p + (m - p).detach())`` with m the exact top-``top`` mask of a row of t and p = softmax(t / temp).
+
+    Cosine form ``apply(table, clusters, None, top, temp) -> (t, x)``: the rows are the WHOLE table, t = clamp(cos(table, clusters), -1, 1)
+    [R, C]. ``t`` is a differentiable output: a gradient into it (ECF's user side reads the item logits) is added inside the backward
+    kernel. The table gradient is dense and written directly. Logit form ``apply(None, None, logits, top, temp) -> x``.
+    Equal logits at the mask boundary go to the lowest cluster index. One fixed-order form (valid in deterministic mode)."""
+
+    @staticmethod
+    def forward(ctx, table, clusters, logits, top, temp):
+        table, cl, lg, R, D, C = _cluster_operands(table, clusters, logits, top, temp, 'ClusterAffilFn')
+        t, x, state, mask = _cluster_fwd(table, cl, lg, R, D, C, top, temp, True)
+        ctx.cosine, ctx.temp, ctx.dims = lg is None, float(temp), (R, D, C)
+        ctx.set_materialize_grads(False)
+        if lg is None:
+            ctx.save_for_backward(table, cl, t, state, mask)
+            return t, x
+        ctx.save_for_backward(lg, state, mask)
+        return x
+
+    @staticmethod
+    def backward(ctx, *grads):
+        R, D, C = ctx.dims
+        if ctx.cosine:
+            table, cl, t, state, mask = ctx.saved_tensors
+            g_t, g_x = grads
+            dev = t.device
+            need_w, need_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            g_x = torch.zeros(R, C, device=dev, dtype=torch.float32) if g_x is None else _f32c(g_x)
+            g_t = None if g_t is None else _f32c(g_t)
+            dW = torch.empty(R, D, device=dev, dtype=torch.float32) if need_w else None
+            if R == 0:                       # no rows: nothing to launch (an empty table has no device pointer either)
+                return dW, torch.zeros(C, D, device=dev, dtype=torch.float32) if need_c else None, None, None, None
+            dC = torch.empty(C, D, device=dev, dtype=torch.float32) if need_c else None
+            ws = _cluster_ws(dev, R, D, C, True) if need_w or need_c else None
+            _timed(('cluster_affil_bwd', R, D, C),
+                   lambda: call('sbr_cluster_affil_bwd', ptr(g_x), ptr(g_t), ptr(table), table.stride(0), ptr(cl), ptr(t), R, D, C, ctx.temp,
+                                ptr(state), ptr(mask), ptr(dW), D, ptr(dC), None, ptr(ws), 0 if ws is None else ws.numel(), stream()))
+            return dW, dC, None, None, None
+        lg, state, mask = ctx.saved_tensors
+        (g_x,) = grads
+        d = None
+        if ctx.needs_input_grad[2]:
+            g_x = torch.zeros(R, C, device=lg.device, dtype=torch.float32) if g_x is None else _f32c(g_x)
+            d = torch.empty(R, C, device=lg.device, dtype=torch.float32)
+            if R > 0:
+                _timed(('cluster_affil_bwd', R, 0, C),
+                       lambda: call('sbr_cluster_affil_bwd', ptr(g_x), None, None, 0, None, ptr(lg), R, 0, C, ctx.temp, ptr(state), ptr(mask),
+                                    None, 0, None, ptr(d), None, 0, stream()))
+        return None, None, d, None, None
+
+
+def cluster_affil(table, clusters, logits, top: int, temp: float):
+    """The evaluation form of ``ClusterAffilFn`` (no autograd, nothing saved): ``(t, x)`` in the cosine form, ``x`` in the logit form."""
+    table, cl, lg, R, D, C = _cluster_operands(None if table is None else table.detach(), None if clusters is None else clusters.detach(),
+                                               None if logits is None else logits.detach(), top, temp, 'cluster_affil')
+    t, x, _, _ = _cluster_fwd(table, cl, lg, R, D, C, top, temp, False)
+    return (t, x) if lg is None else x
+
+
+def csr_rows_times_dense(csr, rows: torch.Tensor, dense: torch.Tensor) -> torch.Tensor:
+    """``X[rows] @ dense`` with X a resident ``features.DeviceCSR`` [n, n_cols] and ``dense`` [n_cols, C] contiguous — ECF's
+    ``Y[u_idxs] @ x_tildes`` (sgd_alg.py:992) and ``tag_matrix^T @ xs`` (sgd_alg.py:957, transposed). ``SparseLinearActFn`` with the dense
+    operand as its column-major weight: the gradient of ``dense`` takes the gather form (fixed order) when ``C % 4 == 0``, the scatter
+    form otherwise, which deterministic mode refuses ("no deterministic form")."""
+    if dense.dim() != 2 or not dense.is_contiguous():
+        raise ValueError('csr_rows_times_dense: the dense operand must be a contiguous matrix [n_cols, C]')
+    return SparseLinearActFn.apply(csr, rows, dense.t(), None, 0)
+
+
 class BiasScoreFn(Function):
     """out[b, n] = base[b, n] + user_bias[u[b]] + item_bias[i[b, n]] + global_bias (sgd_alg.py:186-194, 110-119); every term
     optional (None). Bias tables are 1-D float views of the [n, 1] embedding weights. u None: row b; i None: column n."""
