@@ -12,16 +12,14 @@
 // NaN contract (the reference's): a column of c that is 0 in every row gives q_k == 0 and inc = NaN (0 log 0), and so are the gradients
 // that flow through inc. Nothing is clamped. r, c, lse and exc do not depend on q and stay finite.
 //
-// Fixed order everywhere, no atomics, one form that is valid in deterministic mode: the column sums of c are kept per workgroup (double,
-// in LDS, the workgroup's tiles in order), written as one partial per workgroup and folded in workgroup order by one workgroup; the
-// entropy sum is one double per workgroup, added in workgroup order; dA is one partial [K, D] per workgroup (= row split: a workgroup
-// adds its tiles into its own partial in tile order, every element by the same thread) and the partials are folded in split order. The
-// number of workgroups / splits depends on (R, D, K) only, never on the device.
-//
-// Work-item map: a workgroup of 256 threads owns a tile of 64 rows and keeps it for every product that shares the rows. A thread holds
-// a 4 x 4 block of every 64-wide anchor tile of the [64, K] logits in registers (K <= 256: up to four blocks, the template parameter), so
-// the softmax, the entropies and the softmax backward are register arithmetic plus shuffles over the 16 lanes of a row group. Operands of
-// a K-chunk of 32 are staged in LDS K-major ([32][64 + 4 pad], one 16-byte LDS load per operand and k, as csrc/proto_sim.hip does).
+// Built on the 64 x 64 fp32 tile skeleton (csrc/tile64_f32.h; DESIGN.md has the work-item map, the LDS layout and the fixed-order rule):
+// a workgroup keeps its tile of 64 rows for every product that shares the rows, and a thread holds a 4 x 4 block of every 64-wide anchor
+// tile of the [64, K] logits in registers (K <= 256: up to four blocks, the template parameter), so the softmax, the entropies and the
+// softmax backward are register arithmetic plus shuffles over the 16 lanes of a row group. What crosses workgroups here, one form that is
+// valid in deterministic mode: the column sums of c are kept per workgroup (double, in LDS, the workgroup's tiles in order), written as
+// one partial per workgroup and folded in workgroup order by one workgroup; the entropy sum is one double per workgroup, added in
+// workgroup order; dA is one partial [K, D] per workgroup (= row split), folded in split order. The number of workgroups / splits depends
+// on (R, D, K) only, never on the device.
 //   forward   s = e A^T        the rows go from the table into LDS once (the lookup is never materialised), one staging of the row chunk
 //                              serves every anchor tile
 //             r = c A          c staged from the registers, per 64-wide tile of D
@@ -31,142 +29,30 @@
 //                                                                                               the softmax backward)
 //             dE = ds A        ds staged from the registers
 //             dA = ds^T e + c^T G   one product over the 128 "rows" [ds; c] x [e; G] per (anchor tile, D tile), added into the partial
-#include "common.h"
-#include <limits.h>
-#include <math.h>
+#include "tile64_f32.h"
 
 namespace {
 
-constexpr int AM_T = 64;            // tile edge
-constexpr int AM_KC = 32;           // K-chunk
-constexpr int AM_LD = AM_T + 4;     // LDS row stride (floats): 16-byte aligned rows, 4-bank shift per k
-constexpr int AM_MAX_D = 512, AM_MAX_K = 256;
-constexpr int AM_MAX_WG = 1024;     // workgroups of either pass = column-sum partials = dA row splits
-constexpr long AM_WS_FLOATS = 16L << 20;   // dA partials: at most 64 MiB ...
-constexpr int AM_MIN_SPLIT = 64;           // ... but never fewer than 64 splits (32 MiB at the largest K D)
+constexpr int AM_MAX_D = T64_MAX_D, AM_MAX_K = T64_MAX_N;
+constexpr int AM_MAX_WG = T64_MAX_WG;      // workgroups of either pass = column-sum partials = dA row splits
 
-static inline int am_tiles(long n) { return (int)((n + AM_T - 1) / AM_T); }
-static inline int am_fwd_wgs(long R) { const int t = am_tiles(R); return t < AM_MAX_WG ? t : AM_MAX_WG; }
-static inline int am_splits(long R, int D, int K) {
-  long s = AM_WS_FLOATS / ((long)D * K);
-  if (s < AM_MIN_SPLIT) s = AM_MIN_SPLIT;
-  if (s > AM_MAX_WG) s = AM_MAX_WG;
-  const int t = am_tiles(R);
-  return s > t ? t : (int)s;
-}
+static inline int am_fwd_wgs(long R) { return t64_wgs(R, AM_MAX_WG); }
+static inline int am_splits(long R, int D, int K) { return t64_splits(R, (long)D * K); }
 // forward workspace: [wg doubles: entropy sums][wg * K doubles: column sums of c]
 static inline size_t am_fwd_ws_bytes(long R, int K) { return (size_t)am_fwd_wgs(R) * ((size_t)K + 1) * sizeof(double); }
 // backward workspace: [splits * K * D floats: dA partials]
 static inline size_t am_bwd_ws_bytes(long R, int D, int K) { return (size_t)am_splits(R, D, K) * K * D * sizeof(float); }
 
-// acc[i][c] += sum_k As[k][4 rg + i] * Bs[k][4 cg + c] over one staged K-chunk
-__device__ __forceinline__ void am_mma(const float* __restrict__ As, const float* __restrict__ Bs, int rg, int cg, float (&acc)[4][4]) {
-#pragma unroll 8
-  for (int k = 0; k < AM_KC; ++k) {
-    const float4 a = *reinterpret_cast<const float4*>(As + k * AM_LD + 4 * rg);
-    const float4 b = *reinterpret_cast<const float4*>(Bs + k * AM_LD + 4 * cg);
-    const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[i][c] = fmaf(av[i], bv[c], acc[i][c]);
-  }
-}
-
-__device__ __forceinline__ void am_zero(float (&acc)[4][4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[i][c] = 0.f;
-}
-
-// sum / max over the 16 lanes of a row group (lane bits 0 .. 3); every lane ends with the same bits
-__device__ __forceinline__ float am_row_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float am_row_max(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// a transposed chunk of looked-up / plain rows: Xs[d - d0][row] for the 8 rows sr + 8 q of this thread, zero outside
-__device__ __forceinline__ void am_stage_rows_t(float* __restrict__ Xs, const float* const (&rp)[8], int d, int D, int sk, int sr) {
-#pragma unroll
-  for (int q = 0; q < 8; ++q) Xs[sk * AM_LD + sr + 8 * q] = (rp[q] && d < D) ? rp[q][d] : 0.f;
-}
-// a transposed chunk of the anchor tile pt: Bs[d - d0][k - 64 pt]
-__device__ __forceinline__ void am_stage_anchors_t(float* __restrict__ Bs, const float* __restrict__ A, int pt, int K, int d, int D, int sk,
-                                                   int sr) {
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const int k = pt * AM_T + sr + 8 * q;
-    Bs[sk * AM_LD + sr + 8 * q] = (k < K && d < D) ? A[(long)k * D + d] : 0.f;
-  }
-}
-// 32 anchors k0 .. k0 + 31 as stored: Bs[k - k0][d - 64 dt]
-__device__ __forceinline__ void am_stage_anchors(float* __restrict__ Bs, const float* __restrict__ A, int k0, int K, int dt, int D, int bc,
-                                                 int bk) {
-  const int d = dt * AM_T + bc;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const int k = bk + 4 * q, kk = k0 + k;
-    Bs[k * AM_LD + bc] = (kk < K && d < D) ? A[(long)kk * D + d] : 0.f;
-  }
-}
-// the half `half` (32 columns) of a thread-held [64 rows, 64 columns] block, transposed: As[column - 32 half][row]
-__device__ __forceinline__ void am_stage_regs_t(float* __restrict__ As, const float (&v)[4][4], int half, int rg, int cg) {
-  if ((cg >> 3) == half) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      *reinterpret_cast<float4*>(As + (4 * (cg & 7) + c) * AM_LD + 4 * rg) = make_float4(v[0][c], v[1][c], v[2][c], v[3][c]);
-  }
-}
-// the half `half` (32 rows) of a thread-held block as it is: As[row - 32 half][column]
-__device__ __forceinline__ void am_stage_regs(float* __restrict__ As, const float (&v)[4][4], int half, int rg, int cg) {
-  if ((rg >> 3) == half) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      *reinterpret_cast<float4*>(As + (4 * (rg & 7) + i) * AM_LD + 4 * cg) = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
-  }
-}
-
-// out[j0 + row, 64 dt + col] = sum_k v[row, k] A[k, col]: v is the thread-held [64, K] block set (zero for k >= K)
+// out[j0 + row, :] = sum_k v[row, k] A[k, :]: v is the thread-held [64, K] block set (zero for k >= K)
 template <int NPT>
 __device__ __forceinline__ void am_times_anchors(float* __restrict__ As, float* __restrict__ Bs, const float (&v)[NPT][4][4],
                                                  const float* __restrict__ A, int K, int D, long j0, long R, float* __restrict__ out,
                                                  int t) {
-  const int cg = t & 15, rg = t >> 4, bc = t & 63, bk = t >> 6;
-  const int n_dt = (D + AM_T - 1) / AM_T;
+  const int n_dt = (D + T64_T - 1) / T64_T;
   for (int dt = 0; dt < n_dt; ++dt) {
     float acc[4][4];
-    am_zero(acc);
-#pragma unroll
-    for (int pt = 0; pt < NPT; ++pt) {
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int k0 = pt * AM_T + half * AM_KC;
-        if (k0 < K) {                                   // the same for every thread
-          am_stage_regs_t(As, v[pt], half, rg, cg);
-          am_stage_anchors(Bs, A, k0, K, dt, D, bc, bk);
-          __syncthreads();
-          am_mma(As, Bs, rg, cg, acc);
-          __syncthreads();
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const long j = j0 + 4 * rg + i;
-      if (j >= R) continue;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int d = dt * AM_T + 4 * cg + c;
-        if (d < D) out[j * D + d] = acc[i][c];
-      }
-    }
+    t64_regs_times<NPT>(As, Bs, v, A, K, D, dt, t, acc);
+    t64_store_rows(out, D, acc, j0, R, dt, D, t);
   }
 }
 
@@ -175,11 +61,11 @@ __global__ __launch_bounds__(256) void am_fwd_kernel(const float* __restrict__ W
                                                      const float* __restrict__ A, int K, float* __restrict__ r_out,
                                                      float* __restrict__ c_out, float* __restrict__ lse_out, double* __restrict__ part_cs,
                                                      double* __restrict__ part_h, int n_tiles) {
-  __shared__ __align__(16) float As[AM_KC * AM_LD];
-  __shared__ __align__(16) float Bs[AM_KC * AM_LD];
+  __shared__ __align__(16) float As[T64_KC * T64_LD];
+  __shared__ __align__(16) float Bs[T64_KC * T64_LD];
   __shared__ double s_col[AM_MAX_K];
-  __shared__ float s_wc[4][AM_T];
-  __shared__ float s_h[AM_T];
+  __shared__ float s_wc[4][T64_T];
+  __shared__ float s_h[T64_T];
   const int t = threadIdx.x, cg = t & 15, rg = t >> 4, lane = t & 63, wave = t >> 6;
   const int sk = t & 31, sr = t >> 5;                 // staging of a transposed tile: k within the chunk, first of 8 rows (stride 8)
   if (LOSS) {
@@ -187,23 +73,19 @@ __global__ __launch_bounds__(256) void am_fwd_kernel(const float* __restrict__ W
   }
   double hsum = 0.0;                                  // thread 0: sum of this workgroup's row entropies, in tile order
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long j0 = (long)tile * AM_T;
+    const long j0 = (long)tile * T64_T;
     const float* rp[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const long j = j0 + sr + 8 * q;
-      rp[q] = j < R ? W + (long)(rows ? rows[j] : j) * ldw : nullptr;
-    }
+    t64_row_ptrs(rp, W, ldw, rows, j0, R, sr);
     float v[NPT][4][4];                               // s, then c
 #pragma unroll
-    for (int pt = 0; pt < NPT; ++pt) am_zero(v[pt]);
-    for (int d0 = 0; d0 < D; d0 += AM_KC) {
-      am_stage_rows_t(As, rp, d0 + sk, D, sk, sr);
+    for (int pt = 0; pt < NPT; ++pt) t64_zero(v[pt]);
+    for (int d0 = 0; d0 < D; d0 += T64_KC) {
+      t64_stage_rows_t(As, rp, d0 + sk, D, sk, sr);
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt) {
-        am_stage_anchors_t(Bs, A, pt, K, d0 + sk, D, sk, sr);
+        t64_stage_tile_t(Bs, A, pt, K, d0 + sk, D, sk, sr);
         __syncthreads();
-        am_mma(As, Bs, rg, cg, v[pt]);
+        t64_mma(As, Bs, rg, cg, v[pt]);
         __syncthreads();
       }
     }
@@ -216,22 +98,22 @@ __global__ __launch_bounds__(256) void am_fwd_kernel(const float* __restrict__ W
       for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-          if (pt * AM_T + 4 * cg + c < K) m = fmaxf(m, v[pt][i][c]);
-      m = am_row_max(m);
+          if (pt * T64_T + 4 * cg + c < K) m = fmaxf(m, v[pt][i][c]);
+      m = t64_row_max(m);
       float sum = 0.f;
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-          if (pt * AM_T + 4 * cg + c < K) sum += expf(v[pt][i][c] - m);
-      sum = am_row_sum(sum);
+          if (pt * T64_T + 4 * cg + c < K) sum += expf(v[pt][i][c] - m);
+      sum = t64_row_sum(sum);
       const float lse = m + logf(sum);
       float h = 0.f;
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int k = pt * AM_T + 4 * cg + c;
+          const int k = pt * T64_T + 4 * cg + c;
           float cv = 0.f;
           if (k < K) {
             const float s = v[pt][i][c];
@@ -242,28 +124,19 @@ __global__ __launch_bounds__(256) void am_fwd_kernel(const float* __restrict__ W
           v[pt][i][c] = cv;
         }
       if (LOSS) {
-        h = am_row_sum(h);
+        h = t64_row_sum(h);
         if (cg == 0) s_h[4 * rg + i] = j < R ? -h : 0.f;
       }
       if (lse_out && cg == 0 && j < R) lse_out[j] = lse;
     }
     if (LOSS) {
-      // column sums of c over the rows of this tile: the thread's rows, the row groups of a wave (lane bits 4, 5), the waves
+      // column sums of c over the rows of this tile
+      t64_col_sums<NPT>(s_wc, s_col, K, t, [&](int pt, int c) {
+        float cs = 0.f;
 #pragma unroll
-      for (int pt = 0; pt < NPT; ++pt) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          float cs = 0.f;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) cs += (j0 + 4 * rg + i < R) ? v[pt][i][c] : 0.f;
-          cs += __shfl_xor(cs, 16, 64);
-          cs += __shfl_xor(cs, 32, 64);
-          if (lane < 16) s_wc[wave][4 * cg + c] = cs;
-        }
-        __syncthreads();
-        if (t < AM_T && pt * AM_T + t < K) s_col[pt * AM_T + t] += (double)((s_wc[0][t] + s_wc[1][t]) + (s_wc[2][t] + s_wc[3][t]));
-        __syncthreads();
-      }
+        for (int i = 0; i < 4; ++i) cs += (j0 + 4 * rg + i < R) ? v[pt][i][c] : 0.f;
+        return cs;
+      });
       if (wave == 0) {
         const double hv = sbr_wave_sum_d((double)s_h[lane]);
         if (t == 0) hsum += hv;
@@ -325,40 +198,35 @@ __global__ __launch_bounds__(256) void am_bwd_kernel(const float* __restrict__ G
                                                      const float* __restrict__ c_in, const float* __restrict__ lse_in,
                                                      const float* __restrict__ dinc, float* __restrict__ dE, float* __restrict__ part,
                                                      int n_tiles) {
-  __shared__ __align__(16) float As[AM_KC * AM_LD];
-  __shared__ __align__(16) float Bs[AM_KC * AM_LD];
-  __shared__ __align__(16) float Gs[AM_KC * AM_LD];
+  __shared__ __align__(16) float As[T64_KC * T64_LD];
+  __shared__ __align__(16) float Bs[T64_KC * T64_LD];
+  __shared__ __align__(16) float Gs[T64_KC * T64_LD];
   const int t = threadIdx.x, cg = t & 15, rg = t >> 4;
   const int sk = t & 31, sr = t >> 5;                 // transposed staging: k within the chunk, first of 8 rows (stride 8)
-  const int bc = t & 63, bk = t >> 6;                 // staging as stored: column, first of 8 k (stride 4)
   const float w_exc = (LOSS && g_exc) ? *g_exc / (float)R : 0.f;
   const float w_inc = (LOSS && g_inc) ? *g_inc : 0.f;
-  const int n_dt = (D + AM_T - 1) / AM_T;
+  const int n_dt = (D + T64_T - 1) / T64_T;
   float* const my_part = part ? part + (long)blockIdx.x * K * D : nullptr;
   bool first = true;
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long j0 = (long)tile * AM_T;
+    const long j0 = (long)tile * T64_T;
     const float* rp[8];
     const float* gp[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const long j = j0 + sr + 8 * q;
-      rp[q] = j < R ? W + (long)(rows ? rows[j] : j) * ldw : nullptr;
-      gp[q] = j < R ? G + j * D : nullptr;
-    }
+    t64_row_ptrs(rp, W, ldw, rows, j0, R, sr);
+    t64_row_ptrs(gp, G, D, nullptr, j0, R, sr);
     float ds[NPT][4][4];                              // dc = G A^T, then ds
     float cv[NPT][4][4];                              // s = e A^T (the loss form), then c
 #pragma unroll
-    for (int pt = 0; pt < NPT; ++pt) { am_zero(ds[pt]); am_zero(cv[pt]); }
-    for (int d0 = 0; d0 < D; d0 += AM_KC) {
-      am_stage_rows_t(Gs, gp, d0 + sk, D, sk, sr);
-      if (LOSS) am_stage_rows_t(As, rp, d0 + sk, D, sk, sr);
+    for (int pt = 0; pt < NPT; ++pt) { t64_zero(ds[pt]); t64_zero(cv[pt]); }
+    for (int d0 = 0; d0 < D; d0 += T64_KC) {
+      t64_stage_rows_t(Gs, gp, d0 + sk, D, sk, sr);
+      if (LOSS) t64_stage_rows_t(As, rp, d0 + sk, D, sk, sr);
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt) {
-        am_stage_anchors_t(Bs, A, pt, K, d0 + sk, D, sk, sr);
+        t64_stage_tile_t(Bs, A, pt, K, d0 + sk, D, sk, sr);
         __syncthreads();
-        am_mma(Gs, Bs, rg, cg, ds[pt]);
-        if (LOSS) am_mma(As, Bs, rg, cg, cv[pt]);
+        t64_mma(Gs, Bs, rg, cg, ds[pt]);
+        if (LOSS) t64_mma(As, Bs, rg, cg, cv[pt]);
         __syncthreads();
       }
     }
@@ -372,7 +240,7 @@ __global__ __launch_bounds__(256) void am_bwd_kernel(const float* __restrict__ G
       for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int k = pt * AM_T + 4 * cg + c;
+          const int k = pt * T64_T + 4 * cg + c;
           float cc = 0.f, l = 0.f, dc = 0.f;
           if (k < K && j < R) {
             cc = c_in[j * K + k];
@@ -387,13 +255,13 @@ __global__ __launch_bounds__(256) void am_bwd_kernel(const float* __restrict__ G
           ds[pt][i][c] = dc;
           cv[pt][i][c] = LOSS ? l : cc;               // the loss form needs c, l and dc at once below: it reads c again (a cache hit)
         }
-      dot = am_row_sum(dot);
-      h = LOSS ? am_row_sum(h) : 0.f;                 // = -H_j
+      dot = t64_row_sum(dot);
+      h = LOSS ? t64_row_sum(h) : 0.f;                 // = -H_j
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int k = pt * AM_T + 4 * cg + c;
+          const int k = pt * T64_T + 4 * cg + c;
           float cc = 0.f, g = 0.f;
           if (k < K && j < R) {
             if (LOSS) {
@@ -412,40 +280,16 @@ __global__ __launch_bounds__(256) void am_bwd_kernel(const float* __restrict__ G
     if (my_part) {
       // dA[k, d] += sum_j ds[j, k] e[j, d] + sum_j c[j, k] G[j, d]: four chunks of 32 "rows" per output tile
       for (int dt = 0; dt < n_dt; ++dt) {
-        const int d = dt * AM_T + bc;
 #pragma unroll
         for (int pt = 0; pt < NPT; ++pt) {
           float acc[4][4];
-          am_zero(acc);
+          t64_zero(acc);
 #pragma unroll
           for (int ch = 0; ch < 4; ++ch) {
-            const int half = ch & 1;
-            am_stage_regs(As, ch < 2 ? ds[pt] : cv[pt], half, rg, cg);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-              const int rl = bk + 4 * q;
-              const long j = j0 + half * AM_KC + rl;
-              float b = 0.f;
-              if (j < R && d < D) b = ch < 2 ? W[(long)(rows ? rows[j] : j) * ldw + d] : G[j * D + d];
-              Bs[rl * AM_LD + bc] = b;
-            }
-            __syncthreads();
-            am_mma(As, Bs, rg, cg, acc);
-            __syncthreads();
+            if (ch < 2) t64_regs_t_times(As, Bs, ds[pt], ch & 1, W, ldw, rows, j0, R, dt, D, t, acc);
+            else t64_regs_t_times(As, Bs, cv[pt], ch & 1, G, D, nullptr, j0, R, dt, D, t, acc);
           }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int k = pt * AM_T + 4 * rg + i;
-            if (k >= K) continue;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const int dd = dt * AM_T + 4 * cg + c;
-              if (dd < D) {
-                float* p = my_part + (long)k * D + dd;
-                *p = first ? acc[i][c] : *p + acc[i][c];      // the same thread owns the element in every tile
-              }
-            }
-          }
+          t64_part_add(my_part, acc, pt, K, dt, D, t, first);
         }
       }
     }
@@ -454,40 +298,13 @@ __global__ __launch_bounds__(256) void am_bwd_kernel(const float* __restrict__ G
   }
 }
 
-// dA[k, d] = the splits' partials added in split order
-__global__ __launch_bounds__(256) void am_fold_kernel(const float* __restrict__ part, int n_split, long KD, float* __restrict__ dA) {
-  const long e = blockIdx.x * 256L + threadIdx.x;
-  if (e >= KD) return;
-  double s = 0.0;
-#pragma unroll 4
-  for (int sp = 0; sp < n_split; ++sp) s += (double)part[(long)sp * KD + e];
-  dA[e] = (float)s;
-}
+// dA[k, d] = the splits' partials added in split order (t64_fold_kernel)
+struct AmFoldEpi {
+  static constexpr bool kColumnSums = false;
+  __device__ __forceinline__ float operator()(long, int, float s, float) const { return s; }
+};
 
 inline bool am_shape_ok(int D, int K) { return D >= 1 && D <= AM_MAX_D && K >= 2 && K <= AM_MAX_K; }
-
-template <bool LOSS>
-void am_launch_fwd(int npt, int nb, hipStream_t s, const float* W, long ldw, const int* rows, long R, int D, const float* A, int K,
-                   float* r_out, float* c_out, float* lse_out, double* part_cs, double* part_h, int n_tiles) {
-  switch (npt) {
-    case 1: am_fwd_kernel<1, LOSS><<<nb, 256, 0, s>>>(W, ldw, rows, R, D, A, K, r_out, c_out, lse_out, part_cs, part_h, n_tiles); break;
-    case 2: am_fwd_kernel<2, LOSS><<<nb, 256, 0, s>>>(W, ldw, rows, R, D, A, K, r_out, c_out, lse_out, part_cs, part_h, n_tiles); break;
-    case 3: am_fwd_kernel<3, LOSS><<<nb, 256, 0, s>>>(W, ldw, rows, R, D, A, K, r_out, c_out, lse_out, part_cs, part_h, n_tiles); break;
-    default: am_fwd_kernel<4, LOSS><<<nb, 256, 0, s>>>(W, ldw, rows, R, D, A, K, r_out, c_out, lse_out, part_cs, part_h, n_tiles); break;
-  }
-}
-
-template <bool LOSS>
-void am_launch_bwd(int npt, int nb, hipStream_t s, const float* G, const float* g_exc, const float* g_inc, const float* W, long ldw,
-                   const int* rows, long R, int D, const float* A, int K, const float* c, const float* lse, const float* dinc, float* dE,
-                   float* part, int n_tiles) {
-  switch (npt) {
-    case 1: am_bwd_kernel<1, LOSS><<<nb, 256, 0, s>>>(G, g_exc, g_inc, W, ldw, rows, R, D, A, K, c, lse, dinc, dE, part, n_tiles); break;
-    case 2: am_bwd_kernel<2, LOSS><<<nb, 256, 0, s>>>(G, g_exc, g_inc, W, ldw, rows, R, D, A, K, c, lse, dinc, dE, part, n_tiles); break;
-    case 3: am_bwd_kernel<3, LOSS><<<nb, 256, 0, s>>>(G, g_exc, g_inc, W, ldw, rows, R, D, A, K, c, lse, dinc, dE, part, n_tiles); break;
-    default: am_bwd_kernel<4, LOSS><<<nb, 256, 0, s>>>(G, g_exc, g_inc, W, ldw, rows, R, D, A, K, c, lse, dinc, dE, part, n_tiles); break;
-  }
-}
 
 }  // namespace
 
@@ -511,14 +328,18 @@ extern "C" int sbr_anchor_mix_fwd(const float* W, long ldw, const int* rows, lon
   SBR_REQUIRE(!loss || (workspace && workspace_bytes >= (long)am_fwd_ws_bytes(R, K)), "sbr_anchor_mix_fwd: workspace of %ld bytes, needs %ld",
               workspace_bytes, (long)am_fwd_ws_bytes(R, K));
   hipStream_t s = (hipStream_t)stream;
-  const int nb = am_fwd_wgs(R), n_tiles = am_tiles(R), npt = am_tiles(K);
+  const int nb = am_fwd_wgs(R), n_tiles = t64_tiles(R), npt = t64_tiles(K);
   if (loss) {
     double* part_h = (double*)workspace;
     double* part_cs = part_h + nb;
-    am_launch_fwd<true>(npt, nb, s, W, ldw, rows, R, D, A, K, r_out, c_out, lse_out, part_cs, part_h, n_tiles);
+    t64_dispatch_npt(npt, [&](auto n) {
+      am_fwd_kernel<decltype(n)::value, true><<<nb, 256, 0, s>>>(W, ldw, rows, R, D, A, K, r_out, c_out, lse_out, part_cs, part_h, n_tiles);
+    });
     am_fin_kernel<<<1, 256, 0, s>>>(part_cs, part_h, nb, K, R, q_out, dinc_out, exc_loss, inc_loss);
   } else {
-    am_launch_fwd<false>(npt, nb, s, W, ldw, rows, R, D, A, K, r_out, c_out, lse_out, nullptr, nullptr, n_tiles);
+    t64_dispatch_npt(npt, [&](auto n) {
+      am_fwd_kernel<decltype(n)::value, false><<<nb, 256, 0, s>>>(W, ldw, rows, R, D, A, K, r_out, c_out, lse_out, nullptr, nullptr, n_tiles);
+    });
   }
   SBR_CHECK_LAUNCH("sbr_anchor_mix_fwd");
   return SBR_OK;
@@ -544,11 +365,14 @@ extern "C" int sbr_anchor_mix_bwd(const float* G, const float* g_exc, const floa
   if (!dE && !dA) return SBR_OK;
   SBR_REQUIRE(!dA || (workspace && workspace_bytes >= (long)am_bwd_ws_bytes(R, D, K)), "sbr_anchor_mix_bwd: workspace of %ld bytes, needs %ld",
               workspace_bytes, (long)am_bwd_ws_bytes(R, D, K));
-  const int n_tiles = am_tiles(R), npt = am_tiles(K), nb = am_splits(R, D, K);
+  const int n_tiles = t64_tiles(R), npt = t64_tiles(K), nb = am_splits(R, D, K);
   float* part = dA ? (float*)workspace : nullptr;
-  if (loss) am_launch_bwd<true>(npt, nb, s, G, g_exc, g_inc, W, ldw, rows, R, D, A, K, c, lse, dinc, dE, part, n_tiles);
-  else am_launch_bwd<false>(npt, nb, s, G, g_exc, g_inc, W, ldw, rows, R, D, A, K, c, lse, dinc, dE, part, n_tiles);
-  if (dA) am_fold_kernel<<<sbr_cdiv((long)K * D, 256), 256, 0, s>>>(part, nb, (long)K * D, dA);
+  t64_dispatch_npt(npt, [&](auto n) {
+    constexpr int NPT = decltype(n)::value;
+    if (loss) am_bwd_kernel<NPT, true><<<nb, 256, 0, s>>>(G, g_exc, g_inc, W, ldw, rows, R, D, A, K, c, lse, dinc, dE, part, n_tiles);
+    else am_bwd_kernel<NPT, false><<<nb, 256, 0, s>>>(G, g_exc, g_inc, W, ldw, rows, R, D, A, K, c, lse, dinc, dE, part, n_tiles);
+  });
+  if (dA) t64_fold_kernel<<<sbr_cdiv((long)K * D, 256), 256, 0, s>>>(part, nullptr, nb, K, D, AmFoldEpi{}, dA);
   SBR_CHECK_LAUNCH("sbr_anchor_mix_bwd");
   return SBR_OK;
 }

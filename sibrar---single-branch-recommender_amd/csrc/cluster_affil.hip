@@ -24,41 +24,25 @@
 // m of clusters 4 q .. 4 q + 3, bits 4 .. 7 = "the clamp was active" for the same clusters (a thread owns whole bytes: no cross-lane
 // packing).
 //
-// Work-item map (csrc/anchor_mix.hip's): a workgroup of 256 threads owns a tile of 64 rows; a thread holds a 4 x 4 block of every 64-wide
-// cluster tile of the [64, C] logits in registers (C <= 256: up to four blocks, the template parameter), so selection, softmax and their
-// backward are register arithmetic plus shuffles over the 16 lanes of a row group. GEMM operands are staged in LDS K-major
-// ([32][64 + 4 pad], one 16-byte LDS load per operand and k). fp32 FMA throughout.
+// Built on the 64 x 64 fp32 tile skeleton (csrc/tile64_f32.h; DESIGN.md has the work-item map, the LDS layout and the fixed-order rule):
+// a thread holds a 4 x 4 block of every 64-wide cluster tile of the [64, C] logits in registers (C <= 256: up to four blocks, the
+// template parameter), so selection, softmax and their backward are register arithmetic plus shuffles over the 16 lanes of a row group.
 //   forward   raw = W Cl^T      rows go from the table into LDS once, their squared norms are summed on the way in; divided by the product of
 //                               the two clamped norms afterwards
 //   backward  dW  = (dt Cl^ - flag_r W^ (dt . t)) / |W_r|          dt staged from the registers, Cl^ = Cl / |Cl| staged per chunk
 //             dCl = (dt^T W^ - flag_k Cl^ colsum_k(dt t)) / |Cl_k|
-// Fixed order, no atomics, one form that is valid in deterministic mode: dCl and the column sums are one partial per workgroup (a
-// workgroup adds its tiles into its own partial in tile order, every element by the same thread), folded in workgroup order in double by
-// ca_fold_kernel. The number of workgroups depends on (R, D, C) only, never on the device. The forward pass has no cross-workgroup sum.
-#include "common.h"
-#include <limits.h>
-#include <math.h>
+// What crosses workgroups here, one form that is valid in deterministic mode: dCl and the column sums of dt t are one partial per
+// workgroup, folded in workgroup order in double. The number of workgroups depends on (R, D, C) only, never on the device. The forward
+// pass has no cross-workgroup sum.
+#include "tile64_f32.h"
 
 namespace {
 
-constexpr int CA_T = 64;            // tile edge
-constexpr int CA_KC = 32;           // K-chunk
-constexpr int CA_LD = CA_T + 4;     // LDS row stride (floats): 16-byte aligned rows, 4-bank shift per k
-constexpr int CA_MAX_D = 512, CA_MAX_C = 256;
-constexpr int CA_MAX_WG = 1024;     // workgroups of either pass = dCl partials
-constexpr long CA_WS_FLOATS = 16L << 20;   // dCl partials: at most 64 MiB ...
-constexpr int CA_MIN_SPLIT = 64;           // ... but never fewer than 64 splits (32 MiB at the largest C D)
-constexpr float CA_EPS = 1e-12f;
+constexpr int CA_MAX_D = T64_MAX_D, CA_MAX_C = T64_MAX_N;
+constexpr int CA_MAX_WG = T64_MAX_WG;      // workgroups of either pass = dCl partials
 
-static inline int ca_tiles(long n) { return (int)((n + CA_T - 1) / CA_T); }
-static inline int ca_fwd_wgs(long R) { const int t = ca_tiles(R); return t < CA_MAX_WG ? t : CA_MAX_WG; }
-static inline int ca_splits(long R, int D, int C) {
-  long s = CA_WS_FLOATS / ((long)(D + 1) * C);
-  if (s < CA_MIN_SPLIT) s = CA_MIN_SPLIT;
-  if (s > CA_MAX_WG) s = CA_MAX_WG;
-  const int t = ca_tiles(R);
-  return s > t ? t : (int)s;
-}
+static inline int ca_fwd_wgs(long R) { return t64_wgs(R, CA_MAX_WG); }
+static inline int ca_splits(long R, int D, int C) { return t64_splits(R, (long)(D + 1) * C); }
 // workspace of either pass: [2 * CA_MAX_C floats: cluster stats {max(|Cl_k|, eps), |Cl_k| >= eps}], then, backward only,
 // [splits * C * D floats: dCl partials][splits * C floats: column sums of dt t]
 static inline size_t ca_fwd_ws_bytes() { return 2 * CA_MAX_C * sizeof(float); }
@@ -66,38 +50,7 @@ static inline size_t ca_bwd_ws_bytes(long R, int D, int C) {
   return ca_fwd_ws_bytes() + (size_t)ca_splits(R, D, C) * C * ((size_t)D + 1) * sizeof(float);
 }
 
-// acc[i][c] += sum_k As[k][4 rg + i] * Bs[k][4 cg + c] over one staged K-chunk
-__device__ __forceinline__ void ca_mma(const float* __restrict__ As, const float* __restrict__ Bs, int rg, int cg, float (&acc)[4][4]) {
-#pragma unroll 8
-  for (int k = 0; k < CA_KC; ++k) {
-    const float4 a = *reinterpret_cast<const float4*>(As + k * CA_LD + 4 * rg);
-    const float4 b = *reinterpret_cast<const float4*>(Bs + k * CA_LD + 4 * cg);
-    const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[i][c] = fmaf(av[i], bv[c], acc[i][c]);
-  }
-}
-
-__device__ __forceinline__ void ca_zero(float (&acc)[4][4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[i][c] = 0.f;
-}
-
-// sum / max over the 16 lanes of a row group (lane bits 0 .. 3); every lane ends with the same bits
-__device__ __forceinline__ float ca_row_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float ca_row_max(float v) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+// t64_row_sum of counts
 __device__ __forceinline__ unsigned ca_row_sum_u(unsigned v) {
 #pragma unroll
   for (int o = 1; o < 16; o <<= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
@@ -122,7 +75,7 @@ __device__ __forceinline__ void ca_select(const float (&v)[NPT][4][4], int C, in
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) key[pt][i][c] = (pt * CA_T + 4 * cg + c < C) ? ca_key(v[pt][i][c]) : 0u;   // candidates are >= 1
+      for (int c = 0; c < 4; ++c) key[pt][i][c] = (pt * T64_T + 4 * cg + c < C) ? ca_key(v[pt][i][c]) : 0u;   // candidates are >= 1
   unsigned pre[4] = {0u, 0u, 0u, 0u};
   const unsigned utop = (unsigned)top;
 #pragma unroll 1
@@ -174,7 +127,7 @@ __device__ __forceinline__ void ca_select(const float (&v)[NPT][4][4], int C, in
         const unsigned k = key[pt][i][c];
         bool in = k > pre[i];
         if (k == pre[i]) { in = rank < need; ++rank; }
-        if (in && pt * CA_T + 4 * cg + c < C) bits |= 1u << c;
+        if (in && pt * T64_T + 4 * cg + c < C) bits |= 1u << c;
       }
       mb[pt][i] = bits;
       before_tiles += (tot >> (8 * pt)) & 0xffu;
@@ -199,21 +152,21 @@ __device__ __forceinline__ void ca_rows_fwd(const float (&v)[NPT][4][4], const u
     for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        if (pt * CA_T + 4 * cg + c < C) m = fmaxf(m, v[pt][i][c] / temp);
-    m = ca_row_max(m);
+        if (pt * T64_T + 4 * cg + c < C) m = fmaxf(m, v[pt][i][c] / temp);
+    m = t64_row_max(m);
     float sum = 0.f;
 #pragma unroll
     for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        if (pt * CA_T + 4 * cg + c < C) sum += expf(v[pt][i][c] / temp - m);
-    sum = ca_row_sum(sum);
+        if (pt * T64_T + 4 * cg + c < C) sum += expf(v[pt][i][c] / temp - m);
+    sum = t64_row_sum(sum);
     if (j < R) {
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int k = pt * CA_T + 4 * cg + c;
+          const int k = pt * T64_T + 4 * cg + c;
           if (k < C) {
             const float t = v[pt][i][c];
             const float p = expf(t / temp - m) / sum;
@@ -244,20 +197,20 @@ __device__ __forceinline__ void ca_rows_bwd(float (&dt)[NPT][4][4], float (&tv)[
     for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const int k = pt * CA_T + 4 * cg + c;
+        const int k = pt * T64_T + 4 * cg + c;
         float t = 0.f, g = 0.f;
         if (live && k < C) { t = T[j * C + k]; g = G[j * C + k]; dot = fmaf(expf(t / temp - m) / sum, g * ca_sigmoid(t), dot); }
         tv[pt][i][c] = t;
         dt[pt][i][c] = g;
       }
-    dot = ca_row_sum(dot);
+    dot = t64_row_sum(dot);
     float r = 0.f;
 #pragma unroll
     for (int pt = 0; pt < NPT; ++pt) {
       const unsigned byte = (live && pt * 16 + cg < C4) ? mask[j * C4 + pt * 16 + cg] : 0u;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const int k = pt * CA_T + 4 * cg + c;
+        const int k = pt * T64_T + 4 * cg + c;
         float d = 0.f;
         if (live && k < C) {
           const float t = tv[pt][i][c], g = dt[pt][i][c];
@@ -273,40 +226,7 @@ __device__ __forceinline__ void ca_rows_bwd(float (&dt)[NPT][4][4], float (&tv)[
         dt[pt][i][c] = d;
       }
     }
-    rs[i] = COS ? ca_row_sum(r) : 0.f;
-  }
-}
-
-// the half `half` (32 columns) of a thread-held [64 rows, 64 columns] block, transposed: As[column - 32 half][row]
-__device__ __forceinline__ void ca_stage_regs_t(float* __restrict__ As, const float (&v)[4][4], int half, int rg, int cg) {
-  if ((cg >> 3) == half) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      *reinterpret_cast<float4*>(As + (4 * (cg & 7) + c) * CA_LD + 4 * rg) = make_float4(v[0][c], v[1][c], v[2][c], v[3][c]);
-  }
-}
-// the half `half` (32 rows) of a thread-held block as it is: As[row - 32 half][column]
-__device__ __forceinline__ void ca_stage_regs(float* __restrict__ As, const float (&v)[4][4], int half, int rg, int cg) {
-  if ((rg >> 3) == half) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      *reinterpret_cast<float4*>(As + (4 * (rg & 7) + i) * CA_LD + 4 * cg) = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
-  }
-}
-
-// {max(|Cl_k|, eps), |Cl_k| >= eps ? 1 : 0}: one wave per cluster. The norm is kept, not its reciprocal, and every normalisation is a
-// division: x / |x| is then exactly +-1 for a row of one element, as it is in the reference.
-__global__ __launch_bounds__(256) void ca_cluster_norm_kernel(const float* __restrict__ Cl, int C, int D, float* __restrict__ cstat) {
-  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (k >= C) return;
-  const int lane = threadIdx.x & 63;
-  float ss = 0.f;
-  for (int d = lane; d < D; d += 64) { const float v = Cl[(long)k * D + d]; ss = fmaf(v, v, ss); }
-  ss = sbr_wave_sum(ss);
-  if (lane == 0) {
-    const float n = sqrtf(ss);
-    cstat[2 * k] = fmaxf(n, CA_EPS);
-    cstat[2 * k + 1] = n >= CA_EPS ? 1.f : 0.f;
+    rs[i] = COS ? t64_row_sum(r) : 0.f;
   }
 }
 
@@ -315,50 +235,35 @@ __global__ __launch_bounds__(256) void ca_fwd_cos_kernel(const float* __restrict
                                                          int C, const float* __restrict__ cstat, int top, float temp,
                                                          float* __restrict__ t_out, float* __restrict__ x_out,
                                                          float* __restrict__ row_state, unsigned char* __restrict__ mask, int n_tiles) {
-  __shared__ __align__(16) float As[CA_KC * CA_LD];
-  __shared__ __align__(16) float Bs[CA_KC * CA_LD];
-  __shared__ float s_ss[CA_T];
+  __shared__ __align__(16) float As[T64_KC * T64_LD];
+  __shared__ __align__(16) float Bs[T64_KC * T64_LD];
+  __shared__ float s_ss[T64_T];
   const int t = threadIdx.x, cg = t & 15, rg = t >> 4;
   const int sk = t & 31, sr = t >> 5;                 // staging of a transposed tile: k within the chunk, first of 8 rows (stride 8)
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long j0 = (long)tile * CA_T;
+    const long j0 = (long)tile * T64_T;
     const float* rp[8];
     float ss[8];
+    t64_row_ptrs(rp, W, ldw, nullptr, j0, R, sr);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const long j = j0 + sr + 8 * q;
-      rp[q] = j < R ? W + j * ldw : nullptr;
-      ss[q] = 0.f;
-    }
+    for (int q = 0; q < 8; ++q) ss[q] = 0.f;
     float v[NPT][4][4];                               // raw dot products, then t
 #pragma unroll
-    for (int pt = 0; pt < NPT; ++pt) ca_zero(v[pt]);
-    for (int d0 = 0; d0 < D; d0 += CA_KC) {
-      const int d = d0 + sk;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float x = (rp[q] && d < D) ? rp[q][d] : 0.f;
-        ss[q] = fmaf(x, x, ss[q]);
-        As[sk * CA_LD + sr + 8 * q] = x;
-      }
+    for (int pt = 0; pt < NPT; ++pt) t64_zero(v[pt]);
+    for (int d0 = 0; d0 < D; d0 += T64_KC) {
+      t64_stage_rows_t(As, rp, d0 + sk, D, sk, sr, ss, true);
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int k = pt * CA_T + sr + 8 * q;
-          Bs[sk * CA_LD + sr + 8 * q] = (k < C && d < D) ? Cl[(long)k * D + d] : 0.f;
-        }
+        t64_stage_tile_t(Bs, Cl, pt, C, d0 + sk, D, sk, sr);
         __syncthreads();
-        ca_mma(As, Bs, rg, cg, v[pt]);
+        t64_mma(As, Bs, rg, cg, v[pt]);
         __syncthreads();
       }
     }
     // squared row norms: the 32 lanes sk of a half wave hold the chunks' columns of rows sr + 8 q
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      float s = ss[q];
-#pragma unroll
-      for (int o = 1; o < 32; o <<= 1) s += __shfl_xor(s, o, 64);
+      const float s = t64_half_sum<false>(ss[q]);
       if (sk == 0) s_ss[sr + 8 * q] = s;
     }
     __syncthreads();
@@ -367,15 +272,13 @@ __global__ __launch_bounds__(256) void ca_fwd_cos_kernel(const float* __restrict
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const long j = j0 + 4 * rg + i;
-      const float n = sqrtf(s_ss[4 * rg + i]);
-      nr[i] = fmaxf(n, CA_EPS);
-      flag[i] = n >= CA_EPS ? 1.f : 0.f;
+      t64_stats(s_ss[4 * rg + i], nr[i], flag[i]);
 #pragma unroll
       for (int pt = 0; pt < NPT; ++pt) {
         unsigned cb = 0u;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int k = pt * CA_T + 4 * cg + c;
+          const int k = pt * T64_T + 4 * cg + c;
           float tv = 0.f;
           if (k < C) {
             const float raw = v[pt][i][c] / (nr[i] * cstat[2 * k]);
@@ -399,7 +302,7 @@ __global__ __launch_bounds__(256) void ca_fwd_logit_kernel(const float* __restri
                                                            unsigned char* __restrict__ mask, int n_tiles) {
   const int t = threadIdx.x, cg = t & 15, rg = t >> 4;
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long j0 = (long)tile * CA_T;
+    const long j0 = (long)tile * T64_T;
     float v[NPT][4][4];
     unsigned clampbits[NPT][4];
     const float zero4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -411,7 +314,7 @@ __global__ __launch_bounds__(256) void ca_fwd_logit_kernel(const float* __restri
         clampbits[pt][i] = 0u;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int k = pt * CA_T + 4 * cg + c;
+          const int k = pt * T64_T + 4 * cg + c;
           v[pt][i][c] = (j < R && k < C) ? T[j * C + k] : 0.f;
         }
       }
@@ -425,7 +328,7 @@ __global__ __launch_bounds__(256) void ca_bwd_logit_kernel(const float* __restri
                                                            float* __restrict__ dt_out, int n_tiles) {
   const int t = threadIdx.x, cg = t & 15, rg = t >> 4;
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long j0 = (long)tile * CA_T;
+    const long j0 = (long)tile * T64_T;
     float dt[NPT][4][4], tv[NPT][4][4], rs[4];
     ca_rows_bwd<NPT, false>(dt, tv, rs, G, nullptr, T, C, temp, j0, R, rg, cg, row_state, mask);
 #pragma unroll
@@ -435,7 +338,7 @@ __global__ __launch_bounds__(256) void ca_bwd_logit_kernel(const float* __restri
         const long j = j0 + 4 * rg + i;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int k = pt * CA_T + 4 * cg + c;
+          const int k = pt * T64_T + 4 * cg + c;
           if (j < R && k < C) dt_out[j * C + k] = dt[pt][i][c];
         }
       }
@@ -449,37 +352,30 @@ __global__ __launch_bounds__(256) void ca_bwd_cos_kernel(const float* __restrict
                                                          const float* __restrict__ row_state, const unsigned char* __restrict__ mask,
                                                          float* __restrict__ dW, long lddw, float* __restrict__ part,
                                                          float* __restrict__ part_cs, int n_tiles) {
-  __shared__ __align__(16) float As[CA_KC * CA_LD];
-  __shared__ __align__(16) float Bs[CA_KC * CA_LD];
+  __shared__ __align__(16) float As[T64_KC * T64_LD];
+  __shared__ __align__(16) float Bs[T64_KC * T64_LD];
   __shared__ float s_col[CA_MAX_C];
-  __shared__ float s_wc[4][CA_T];
-  const int t = threadIdx.x, cg = t & 15, rg = t >> 4, lane = t & 63, wave = t >> 6;
+  __shared__ float s_wc[4][T64_T];
+  // The two products below stage their operands here and not through t64_regs_times / t64_regs_t_times (anchor_mix.hip's): the same
+  // statements behind a call cost this kernel a wave per SIMD at NPT = 1 and 16 bytes of scratch per lane at NPT = 4.
+  const int t = threadIdx.x, cg = t & 15, rg = t >> 4;
   const int bc = t & 63, bk = t >> 6;                 // staging as stored: column, first of 8 k (stride 4)
-  const int n_dt = (D + CA_T - 1) / CA_T;
+  const int n_dt = (D + T64_T - 1) / T64_T;
   float* const my_part = part ? part + (long)blockIdx.x * C * D : nullptr;
   s_col[t] = 0.f;                                     // 256 threads, CA_MAX_C entries; read after the barriers of the first tile
   bool first = true;
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long j0 = (long)tile * CA_T;
+    const long j0 = (long)tile * T64_T;
     float dt[NPT][4][4], tv[NPT][4][4], rs[4];
     ca_rows_bwd<NPT, true>(dt, tv, rs, G, Gt, T, C, temp, j0, R, rg, cg, row_state, mask);
     if (my_part) {
-      // column sums of dt t over the rows of this tile: the thread's rows, the row groups of a wave (lane bits 4, 5), the waves
+      // column sums of dt t over the rows of this tile
+      t64_col_sums<NPT>(s_wc, s_col, C, t, [&](int pt, int c) {
+        float cs = 0.f;
 #pragma unroll
-      for (int pt = 0; pt < NPT; ++pt) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          float cs = 0.f;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) cs = fmaf(dt[pt][i][c], tv[pt][i][c], cs);
-          cs += __shfl_xor(cs, 16, 64);
-          cs += __shfl_xor(cs, 32, 64);
-          if (lane < 16) s_wc[wave][4 * cg + c] = cs;
-        }
-        __syncthreads();
-        if (t < CA_T && pt * CA_T + t < C) s_col[pt * CA_T + t] += (s_wc[0][t] + s_wc[1][t]) + (s_wc[2][t] + s_wc[3][t]);
-        __syncthreads();
-      }
+        for (int i = 0; i < 4; ++i) cs = fmaf(dt[pt][i][c], tv[pt][i][c], cs);
+        return cs;
+      });
     }
     if (dW) {
       // dW[j, d] = (sum_k dt[j, k] Cl^[k, d] - flag_j W^[j, d] rs_j) / |W_j|
@@ -492,22 +388,22 @@ __global__ __launch_bounds__(256) void ca_bwd_cos_kernel(const float* __restrict
       }
       for (int dtile = 0; dtile < n_dt; ++dtile) {
         float acc[4][4];
-        ca_zero(acc);
-        const int d = dtile * CA_T + bc;
+        t64_zero(acc);
+        const int d = dtile * T64_T + bc;
 #pragma unroll
         for (int pt = 0; pt < NPT; ++pt) {
 #pragma unroll
           for (int half = 0; half < 2; ++half) {
-            const int k0 = pt * CA_T + half * CA_KC;
+            const int k0 = pt * T64_T + half * T64_KC;
             if (k0 < C) {                             // the same for every thread
-              ca_stage_regs_t(As, dt[pt], half, rg, cg);
+              t64_stage_regs_t(As, dt[pt], half, rg, cg);
 #pragma unroll
               for (int q = 0; q < 8; ++q) {
                 const int k = bk + 4 * q, kk = k0 + k;
-                Bs[k * CA_LD + bc] = (kk < C && d < D) ? Cl[(long)kk * D + d] / cstat[2 * kk] : 0.f;
+                Bs[k * T64_LD + bc] = (kk < C && d < D) ? Cl[(long)kk * D + d] / cstat[2 * kk] : 0.f;
               }
               __syncthreads();
-              ca_mma(As, Bs, rg, cg, acc);
+              t64_mma(As, Bs, rg, cg, acc);
               __syncthreads();
             }
           }
@@ -518,7 +414,7 @@ __global__ __launch_bounds__(256) void ca_bwd_cos_kernel(const float* __restrict
           if (j >= R) continue;
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
-            const int dd = dtile * CA_T + 4 * cg + c;
+            const int dd = dtile * T64_T + 4 * cg + c;
             if (dd < D) dW[j * lddw + dd] = (acc[i][c] - flag[i] * (W[j * ldw + dd] / nr[i]) * rs[i]) / nr[i];
           }
         }
@@ -527,37 +423,25 @@ __global__ __launch_bounds__(256) void ca_bwd_cos_kernel(const float* __restrict
     if (my_part) {
       // partial of sum_j dt[j, k] W^[j, d]: two chunks of 32 rows per output tile
       for (int dtile = 0; dtile < n_dt; ++dtile) {
-        const int d = dtile * CA_T + bc;
+        const int d = dtile * T64_T + bc;
 #pragma unroll
         for (int pt = 0; pt < NPT; ++pt) {
           float acc[4][4];
-          ca_zero(acc);
+          t64_zero(acc);
 #pragma unroll
           for (int half = 0; half < 2; ++half) {
-            ca_stage_regs(As, dt[pt], half, rg, cg);
+            t64_stage_regs(As, dt[pt], half, rg, cg);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
               const int rl = bk + 4 * q;
-              const long j = j0 + half * CA_KC + rl;
-              Bs[rl * CA_LD + bc] = (j < R && d < D) ? W[j * ldw + d] / row_state[4 * j + 2] : 0.f;
+              const long j = j0 + half * T64_KC + rl;
+              Bs[rl * T64_LD + bc] = (j < R && d < D) ? W[j * ldw + d] / row_state[4 * j + 2] : 0.f;
             }
             __syncthreads();
-            ca_mma(As, Bs, rg, cg, acc);
+            t64_mma(As, Bs, rg, cg, acc);
             __syncthreads();
           }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int k = pt * CA_T + 4 * rg + i;
-            if (k >= C) continue;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const int dd = dtile * CA_T + 4 * cg + c;
-              if (dd < D) {
-                float* p = my_part + (long)k * D + dd;
-                *p = first ? acc[i][c] : *p + acc[i][c];      // the same thread owns the element in every tile
-              }
-            }
-          }
+          t64_part_add(my_part, acc, pt, C, dtile, D, t, first);
         }
       }
     }
@@ -568,33 +452,19 @@ __global__ __launch_bounds__(256) void ca_bwd_cos_kernel(const float* __restrict
     for (int k = t; k < C; k += 256) part_cs[(long)blockIdx.x * C + k] = s_col[k];
 }
 
-// dCl[k, d] = (partials added in workgroup order - flag_k Cl^[k, d] (column sums added in workgroup order)) / |Cl_k|
-__global__ __launch_bounds__(256) void ca_fold_kernel(const float* __restrict__ part, const float* __restrict__ part_cs, int n_split, int C,
-                                                      int D, const float* __restrict__ Cl, const float* __restrict__ cstat,
-                                                      float* __restrict__ dCl) {
-  const long e = blockIdx.x * 256L + threadIdx.x, CD = (long)C * D;
-  if (e >= CD) return;
-  const int k = (int)(e / D);
-  double s = 0.0, cs = 0.0;
-#pragma unroll 4
-  for (int sp = 0; sp < n_split; ++sp) {
-    s += (double)part[(long)sp * CD + e];
-    cs += (double)part_cs[(long)sp * C + k];
+// dCl[k, d] = (partials added in workgroup order - flag_k Cl^[k, d] (column sums added in workgroup order)) / |Cl_k| (t64_fold_kernel)
+struct CaFoldEpi {
+  static constexpr bool kColumnSums = true;
+  const float* Cl;
+  const float* cstat;
+  __device__ __forceinline__ float operator()(long e, int k, float s, float cs) const {
+    const float nc = cstat[2 * k], flag = cstat[2 * k + 1];
+    return (s - flag * (Cl[e] / nc) * cs) / nc;
   }
-  const float nc = cstat[2 * k], flag = cstat[2 * k + 1];
-  dCl[e] = ((float)s - flag * (Cl[e] / nc) * (float)cs) / nc;
-}
+};
 
 inline bool ca_shape_ok(int C, int top, float temp) { return C >= 2 && C <= CA_MAX_C && top >= 1 && top <= C && temp > 0.f; }
 inline bool ca_dim_ok(int D) { return D >= 1 && D <= CA_MAX_D; }
-
-#define CA_DISPATCH(npt, KERNEL, ...)                                  \
-  switch (npt) {                                                       \
-    case 1: KERNEL<1><<<nb, 256, 0, s>>>(__VA_ARGS__); break;          \
-    case 2: KERNEL<2><<<nb, 256, 0, s>>>(__VA_ARGS__); break;          \
-    case 3: KERNEL<3><<<nb, 256, 0, s>>>(__VA_ARGS__); break;          \
-    default: KERNEL<4><<<nb, 256, 0, s>>>(__VA_ARGS__); break;         \
-  }
 
 }  // namespace
 
@@ -617,15 +487,19 @@ extern "C" int sbr_cluster_affil_fwd(const float* W, long ldw, const float* Cl, 
   SBR_REQUIRE(x_out, "sbr_cluster_affil_fwd: null operand");
   SBR_REQUIRE(!row_state || (((uintptr_t)row_state) & 15) == 0, "sbr_cluster_affil_fwd: row_state must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  const int nb = ca_fwd_wgs(R), n_tiles = ca_tiles(R), npt = ca_tiles(C);
+  const int nb = ca_fwd_wgs(R), n_tiles = t64_tiles(R), npt = t64_tiles(C);
   if (cosine) {
     SBR_REQUIRE(workspace && workspace_bytes >= (long)ca_fwd_ws_bytes(), "sbr_cluster_affil_fwd: workspace of %ld bytes, needs %ld",
                 workspace_bytes, (long)ca_fwd_ws_bytes());
     float* cstat = (float*)workspace;
-    ca_cluster_norm_kernel<<<sbr_cdiv(C, 4), 256, 0, s>>>(Cl, C, D, cstat);
-    CA_DISPATCH(npt, ca_fwd_cos_kernel, W, ldw, R, D, Cl, C, cstat, top, temp, t_out, x_out, row_state, mask, n_tiles)
+    t64_norm_kernel<<<sbr_cdiv(C, 4), 256, 0, s>>>(Cl, C, D, cstat, nullptr);
+    t64_dispatch_npt(npt, [&](auto n) {
+      ca_fwd_cos_kernel<decltype(n)::value><<<nb, 256, 0, s>>>(W, ldw, R, D, Cl, C, cstat, top, temp, t_out, x_out, row_state, mask, n_tiles);
+    });
   } else {
-    CA_DISPATCH(npt, ca_fwd_logit_kernel, t_in, R, C, top, temp, x_out, row_state, mask, n_tiles)
+    t64_dispatch_npt(npt, [&](auto n) {
+      ca_fwd_logit_kernel<decltype(n)::value><<<nb, 256, 0, s>>>(t_in, R, C, top, temp, x_out, row_state, mask, n_tiles);
+    });
   }
   SBR_CHECK_LAUNCH("sbr_cluster_affil_fwd");
   return SBR_OK;
@@ -653,11 +527,13 @@ extern "C" int sbr_cluster_affil_bwd(const float* G, const float* Gt, const floa
   SBR_REQUIRE(R > 0 && R < INT_MAX && (!cosine || (ldw >= D && (!dW || lddw >= D))),
               "sbr_cluster_affil_bwd: needs 0 <= R < 2^31, ldw >= D and lddw >= D");
   SBR_REQUIRE(G && t && row_state && mask, "sbr_cluster_affil_bwd: null operand");
-  const int n_tiles = ca_tiles(R), npt = ca_tiles(C);
+  const int n_tiles = t64_tiles(R), npt = t64_tiles(C);
   if (!cosine) {
     if (!dt_out) return SBR_OK;
     const int nb = ca_fwd_wgs(R);
-    CA_DISPATCH(npt, ca_bwd_logit_kernel, G, t, R, C, temp, row_state, mask, dt_out, n_tiles)
+    t64_dispatch_npt(npt, [&](auto n) {
+      ca_bwd_logit_kernel<decltype(n)::value><<<nb, 256, 0, s>>>(G, t, R, C, temp, row_state, mask, dt_out, n_tiles);
+    });
     SBR_CHECK_LAUNCH("sbr_cluster_affil_bwd");
     return SBR_OK;
   }
@@ -668,9 +544,12 @@ extern "C" int sbr_cluster_affil_bwd(const float* G, const float* Gt, const floa
   float* cstat = (float*)workspace;
   float* part = dCl ? cstat + 2 * CA_MAX_C : nullptr;
   float* part_cs = dCl ? part + (long)nb * C * D : nullptr;
-  ca_cluster_norm_kernel<<<sbr_cdiv(C, 4), 256, 0, s>>>(Cl, C, D, cstat);
-  CA_DISPATCH(npt, ca_bwd_cos_kernel, G, Gt, W, ldw, R, D, Cl, C, cstat, t, temp, row_state, mask, dW, lddw, part, part_cs, n_tiles)
-  if (dCl) ca_fold_kernel<<<sbr_cdiv((long)C * D, 256), 256, 0, s>>>(part, part_cs, nb, C, D, Cl, cstat, dCl);
+  t64_norm_kernel<<<sbr_cdiv(C, 4), 256, 0, s>>>(Cl, C, D, cstat, nullptr);
+  t64_dispatch_npt(npt, [&](auto n) {
+    ca_bwd_cos_kernel<decltype(n)::value><<<nb, 256, 0, s>>>(G, Gt, W, ldw, R, D, Cl, C, cstat, t, temp, row_state, mask, dW, lddw, part,
+                                                             part_cs, n_tiles);
+  });
+  if (dCl) t64_fold_kernel<<<sbr_cdiv((long)C * D, 256), 256, 0, s>>>(part, part_cs, nb, C, D, CaFoldEpi{Cl, cstat}, dCl);
   SBR_CHECK_LAUNCH("sbr_cluster_affil_bwd");
   return SBR_OK;
 }

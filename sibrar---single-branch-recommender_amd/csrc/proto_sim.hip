@@ -11,15 +11,11 @@
 // column minimum. The compared values are the fp32 distances 2 - sim themselves (the subtraction rounds for sim < 1, so two different
 // similarities may tie as distances, as they do in the reference).
 //
-// Fixed order everywhere, so the entry points have one form that is valid in deterministic mode: the column minimum is taken per
-// workgroup over its own rows (in LDS), written as one partial per workgroup, and picked over the partials in workgroup order by one
-// workgroup; the row-minimum sum is one double per workgroup, added in workgroup order; dP is written as one partial [P, D] per row
-// split and folded in split order. No atomics. The number of workgroups / splits depends on (R, D, P) only, never on the device.
-//
-// Work-item map (all three products are small-K or small-N GEMMs in fp32): a workgroup of 256 threads owns a 64 x 64 output tile, a
-// thread a 4 x 4 block of it; both operands of a K-chunk of 32 are staged in LDS K-major ([32][64 + 4 pad]), so that a thread reads its
-// four rows and its four columns as one 16-byte LDS load each per k. Padding rows / columns of a tile are zero-filled, so the default
-// shape D = 100, P = 20 runs the same code as the round ones.
+// Built on the 64 x 64 fp32 tile skeleton (csrc/tile64_f32.h; DESIGN.md has the work-item map, the LDS layout and the fixed-order rule).
+// What crosses workgroups here: the column minimum is taken per workgroup over its own rows (in LDS), written as one partial per
+// workgroup, and picked over the partials in workgroup order by one workgroup; the row-minimum sum is one double per workgroup, added
+// in workgroup order; dP is written as one partial [P, D] per row split and folded in split order. The number of workgroups / splits
+// depends on (R, D, P) only, never on the device. Unlike its two siblings this file keeps one 4 x 4 block per thread and walks the tiles:
 //   forward   C[j, p] = sum_d e[j, d] P[p, d]      rows gathered straight from the table into LDS (the lookup is never materialised);
 //                                                  the squared row norms are summed on the way in. P > 64: the prototype tiles are
 //                                                  walked inside the row tile, the row tile comes back through the cache.
@@ -27,25 +23,18 @@
 //   dP        C[p, d] = sum_j g'[j, p] e^[j, d]    split over row ranges, partials folded in order
 // followed by the projection terms of F.normalize's gradient ( - x^ (x^ . g) / |x| ), which need the row sums sum_p g' cos and the column
 // sums sum_j g' cos: both are summed while g' is staged.
-#include "common.h"
-#include <limits.h>
-#include <math.h>
+#include "tile64_f32.h"
 
 namespace {
 
-constexpr int PS_T = 64;            // output tile edge
-constexpr int PS_KC = 32;           // K-chunk
-constexpr int PS_LD = PS_T + 4;     // LDS row stride (floats): 16-byte aligned rows, 4-bank shift per k
-constexpr int PS_MAX_D = 512, PS_MAX_P = 256;
+constexpr int PS_MAX_D = T64_MAX_D, PS_MAX_P = T64_MAX_N;
 constexpr int PS_MAX_WG = 256;      // forward workgroups = column-minimum partials
 constexpr int PS_MAX_SPLIT = 256;   // dP row splits (times D tiles times P tiles workgroups)
-constexpr float PS_EPS = 1e-12f;
 
-static inline int ps_tiles(long n) { return (int)((n + PS_T - 1) / PS_T); }
-static inline int ps_fwd_wgs(long R) { const int t = ps_tiles(R); return t < PS_MAX_WG ? t : PS_MAX_WG; }
+static inline int ps_fwd_wgs(long R) { return t64_wgs(R, PS_MAX_WG); }
 static inline int ps_splits(long R, int D, int NP) {
-  int s = PS_MAX_SPLIT / (ps_tiles(D) * ps_tiles(NP));
-  const int t = ps_tiles(R);
+  int s = PS_MAX_SPLIT / (t64_tiles(D) * t64_tiles(NP));
+  const int t = t64_tiles(R);
   if (s > t) s = t;
   return s < 1 ? 1 : s;
 }
@@ -60,48 +49,9 @@ static inline size_t ps_bwd_ws_bytes(long R, int D, int NP) {
   return (size_t)ps_splits(R, D, NP) * NP * ((size_t)D + 1) * sizeof(float);
 }
 
-// acc[i][c] += sum_k As[k][4 rg + i] * Bs[k][4 cg + c] over one staged K-chunk
-__device__ __forceinline__ void ps_mma(const float* __restrict__ As, const float* __restrict__ Bs, int rg, int cg, float (&acc)[4][4]) {
-#pragma unroll 8
-  for (int k = 0; k < PS_KC; ++k) {
-    const float4 a = *reinterpret_cast<const float4*>(As + k * PS_LD + 4 * rg);
-    const float4 b = *reinterpret_cast<const float4*>(Bs + k * PS_LD + 4 * cg);
-    const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[i][c] = fmaf(av[i], bv[c], acc[i][c]);
-  }
-}
-
 // (v, i) <- the smaller of (v, i) and (v2, i2); equal values: the lower index
 __device__ __forceinline__ void ps_take_min(float& v, int& i, float v2, int i2) {
   if (v2 < v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-}
-
-// stats rows: [2] = {max(|x|, eps), |x| >= eps ? 1 : 0}: the flag switches the projection term of the gradient off where the clamp of
-// the norm is active (torch: clamp_min passes no gradient below its bound). The norms are kept, not their reciprocals, and every
-// normalisation is a division: x / |x| is then exactly +-1 for a row of one element, as it is in the reference.
-__device__ __forceinline__ void ps_stats(float ss, float& nc, float& flag) {
-  const float n = sqrtf(ss);
-  nc = fmaxf(n, PS_EPS);
-  flag = n >= PS_EPS ? 1.f : 0.f;
-}
-
-__global__ __launch_bounds__(256) void ps_proto_norm_kernel(const float* __restrict__ P, int NP, int D, float* __restrict__ ws_stat,
-                                                            float* __restrict__ out_stat) {
-  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= NP) return;
-  const int lane = threadIdx.x & 63;
-  float ss = 0.f;
-  for (int c = lane; c < D; c += 64) { const float v = P[(long)p * D + c]; ss = fmaf(v, v, ss); }
-  ss = sbr_wave_sum(ss);
-  float nc, flag;
-  ps_stats(ss, nc, flag);
-  if (lane == 0) {
-    ws_stat[2 * p] = nc; ws_stat[2 * p + 1] = flag;
-    if (out_stat) { out_stat[2 * p] = nc; out_stat[2 * p + 1] = flag; }
-  }
 }
 
 template <bool STATS>
@@ -110,29 +60,25 @@ __global__ __launch_bounds__(256) void ps_fwd_kernel(const float* __restrict__ W
                                                      float* __restrict__ sim_out, float* __restrict__ cos_raw, float* __restrict__ row_stat,
                                                      int* __restrict__ row_best, float* __restrict__ part_cv, int* __restrict__ part_cj,
                                                      double* __restrict__ part_rs, int n_tiles) {
-  __shared__ __align__(16) float As[PS_KC * PS_LD];
-  __shared__ __align__(16) float Bs[PS_KC * PS_LD];
-  __shared__ float s_rnc[PS_T];
+  __shared__ __align__(16) float As[T64_KC * T64_LD];
+  __shared__ __align__(16) float Bs[T64_KC * T64_LD];
+  __shared__ float s_rnc[T64_T];
   __shared__ float s_colv[PS_MAX_P];
   __shared__ int s_colj[PS_MAX_P];
-  __shared__ float s_wv[4][PS_T];
-  __shared__ int s_wj[4][PS_T];
-  __shared__ float s_rowdis[PS_T];
+  __shared__ float s_wv[4][T64_T];
+  __shared__ int s_wj[4][T64_T];
+  __shared__ float s_rowdis[T64_T];
   const int t = threadIdx.x, cg = t & 15, rg = t >> 4, lane = t & 63, wave = t >> 6;
   const int sk = t & 31, sr = t >> 5;                 // staging of a transposed tile: k within the chunk, first of 8 rows (stride 8)
   if (STATS) {
     for (int p = t; p < PS_MAX_P; p += 256) { s_colv[p] = INFINITY; s_colj[p] = INT_MAX; }
   }
   double rowsum = 0.0;                                // thread 0: sum of this workgroup's row minima, in tile order
-  const int n_pt = (NP + PS_T - 1) / PS_T;
+  const int n_pt = (NP + T64_T - 1) / T64_T;
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long j0 = (long)tile * PS_T;
+    const long j0 = (long)tile * T64_T;
     const float* rp[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const long j = j0 + sr + 8 * q;
-      rp[q] = j < R ? W + (long)(rows ? rows[j] : j) * ldw : nullptr;
-    }
+    t64_row_ptrs(rp, W, ldw, rows, j0, R, sr);
     float ss[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) ss[q] = 0.f;
@@ -142,37 +88,22 @@ __global__ __launch_bounds__(256) void ps_fwd_kernel(const float* __restrict__ W
     for (int i = 0; i < 4; ++i) { rbv[i] = INFINITY; rbp[i] = INT_MAX; }
     for (int pt = 0; pt < n_pt; ++pt) {
       float acc[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[i][c] = 0.f;
-      for (int d0 = 0; d0 < D; d0 += PS_KC) {
-        const int d = d0 + sk;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const float v = (rp[q] && d < D) ? rp[q][d] : 0.f;
-          As[sk * PS_LD + sr + 8 * q] = v;
-          if (pt == 0) ss[q] = fmaf(v, v, ss[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int p = pt * PS_T + sr + 8 * q;
-          Bs[sk * PS_LD + sr + 8 * q] = (p < NP && d < D) ? P[(long)p * D + d] : 0.f;
-        }
+      t64_zero(acc);
+      for (int d0 = 0; d0 < D; d0 += T64_KC) {
+        t64_stage_rows_t(As, rp, d0 + sk, D, sk, sr, ss, pt == 0);
+        t64_stage_tile_t(Bs, P, pt, NP, d0 + sk, D, sk, sr);
         __syncthreads();
-        ps_mma(As, Bs, rg, cg, acc);
+        t64_mma(As, Bs, rg, cg, acc);
         __syncthreads();
       }
       if (pt == 0) {
         // the 32 lanes that share sr hold the squared norm of rows sr + 8 q in 32 pieces
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          float v = ss[q];
-#pragma unroll
-          for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+          const float v = t64_half_sum<true>(ss[q]);
           if (sk == 0) {
             float nc, flag;
-            ps_stats(v, nc, flag);
+            t64_stats(v, nc, flag);
             s_rnc[sr + 8 * q] = nc;
             const long j = j0 + sr + 8 * q;
             if (row_stat && j < R) { row_stat[2 * j] = nc; row_stat[2 * j + 1] = flag; }
@@ -183,7 +114,7 @@ __global__ __launch_bounds__(256) void ps_fwd_kernel(const float* __restrict__ W
       float pnc[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const int p = pt * PS_T + 4 * cg + c;
+        const int p = pt * T64_T + 4 * cg + c;
         pnc[c] = p < NP ? pstat[2 * p] : 1.f;
       }
       float cbv[4];
@@ -196,7 +127,7 @@ __global__ __launch_bounds__(256) void ps_fwd_kernel(const float* __restrict__ W
         const float enc = s_rnc[4 * rg + i];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int p = pt * PS_T + 4 * cg + c;
+          const int p = pt * T64_T + 4 * cg + c;
           if (j < R && p < NP) {
             const float cs = acc[i][c] / (enc * pnc[c]);          // both factors >= 1e-12: the product is a normal number
             const float x = 1.f + cs;
@@ -224,8 +155,8 @@ __global__ __launch_bounds__(256) void ps_fwd_kernel(const float* __restrict__ W
           if (lane < 16) { s_wv[wave][4 * cg + c] = cbv[c]; s_wj[wave][4 * cg + c] = cbj[c]; }
         }
         __syncthreads();
-        if (t < PS_T) {
-          const int p = pt * PS_T + t;
+        if (t < T64_T) {
+          const int p = pt * T64_T + t;
           if (p < NP) {
             float v = s_colv[p];
             int j = s_colj[p];
@@ -334,26 +265,23 @@ __global__ __launch_bounds__(256) void ps_bwd_de_kernel(const float* __restrict_
                                                         const float* __restrict__ cos_raw, const float* __restrict__ row_stat,
                                                         const float* __restrict__ pstat, const int* __restrict__ row_best,
                                                         const int* __restrict__ col_best_row, float* __restrict__ dE, int n_tiles) {
-  __shared__ __align__(16) float As[PS_KC * PS_LD];
-  __shared__ __align__(16) float Bs[PS_KC * PS_LD];
-  __shared__ float s_S[PS_T];
+  __shared__ __align__(16) float As[T64_KC * T64_LD];
+  __shared__ __align__(16) float Bs[T64_KC * T64_LD];
+  __shared__ float s_S[T64_T];
   const int t = threadIdx.x, cg = t & 15, rg = t >> 4;
   const int sk = t & 31, sr = t >> 5;                 // g' tile, transposed: prototype within the chunk, first of 8 rows
   const int bc = t & 63, bk = t >> 6;                 // prototype tile, as stored: column, first of 8 k (stride 4)
   const PsGrad gr = ps_grad(G, g_proto, g_batch, cos_raw, row_best, col_best_row, R, NP);
-  const int n_dt = (D + PS_T - 1) / PS_T;
+  const int n_dt = (D + T64_T - 1) / T64_T;
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long j0 = (long)tile * PS_T;
+    const long j0 = (long)tile * T64_T;
     for (int dt = 0; dt < n_dt; ++dt) {
       float acc[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[i][c] = 0.f;
+      t64_zero(acc);
       float S[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) S[q] = 0.f;
-      for (int p0 = 0; p0 < NP; p0 += PS_KC) {
+      for (int p0 = 0; p0 < NP; p0 += T64_KC) {
         const int p = p0 + sk;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -364,24 +292,17 @@ __global__ __launch_bounds__(256) void ps_bwd_de_kernel(const float* __restrict_
             v = gr.at(j, p, cs);
             S[q] = fmaf(v, cs, S[q]);
           }
-          As[sk * PS_LD + sr + 8 * q] = v;
+          As[sk * T64_LD + sr + 8 * q] = v;
         }
-        const int d = dt * PS_T + bc;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int k = bk + 4 * q, pp = p0 + k;
-          Bs[k * PS_LD + bc] = (pp < NP && d < D) ? P[(long)pp * D + d] / pstat[2 * pp] : 0.f;
-        }
+        t64_stage_chunk<true>(Bs, P, pstat, p0, NP, dt, D, bc, bk);
         __syncthreads();
-        ps_mma(As, Bs, rg, cg, acc);
+        t64_mma(As, Bs, rg, cg, acc);
         __syncthreads();
       }
       if (dt == 0) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          float v = S[q];
-#pragma unroll
-          for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+          const float v = t64_half_sum<true>(S[q]);
           if (sk == 0) s_S[sr + 8 * q] = v;
         }
         __syncthreads();
@@ -395,7 +316,7 @@ __global__ __launch_bounds__(256) void ps_bwd_de_kernel(const float* __restrict_
         const float* erow = W + (long)(rows ? rows[j] : j) * ldw;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const int d = dt * PS_T + 4 * cg + c;
+          const int d = dt * T64_T + 4 * cg + c;
           if (d < D) dE[j * D + d] = fmaf(-(flag * (erow[d] / nc)), Sj, acc[i][c]) / nc;
         }
       }
@@ -411,25 +332,22 @@ __global__ __launch_bounds__(256) void ps_bwd_dp_kernel(const float* __restrict_
                                                         const float* __restrict__ cos_raw, const float* __restrict__ row_stat,
                                                         const int* __restrict__ row_best, const int* __restrict__ col_best_row,
                                                         float* __restrict__ part, float* __restrict__ part_t, int n_tiles) {
-  __shared__ __align__(16) float As[PS_KC * PS_LD];
-  __shared__ __align__(16) float Bs[PS_KC * PS_LD];
-  __shared__ float s_T[4][PS_T];
+  __shared__ __align__(16) float As[T64_KC * T64_LD];
+  __shared__ __align__(16) float Bs[T64_KC * T64_LD];
+  __shared__ float s_T[4][T64_T];
   const int t = threadIdx.x, cg = t & 15, rg = t >> 4;
   const int bc = t & 63, bk = t >> 6;                 // both operands as stored: column, first of 8 k (stride 4)
   const PsGrad gr = ps_grad(G, g_proto, g_batch, cos_raw, row_best, col_best_row, R, NP);
   const int split = blockIdx.x, dt = blockIdx.y, pt = blockIdx.z;
   const int per = (n_tiles + gridDim.x - 1) / gridDim.x;
-  const long jlo = (long)split * per * PS_T;
-  long jhi = jlo + (long)per * PS_T;
+  const long jlo = (long)split * per * T64_T;
+  long jhi = jlo + (long)per * T64_T;
   if (jhi > R) jhi = R;
-  const int p = pt * PS_T + bc, d = dt * PS_T + bc;
+  const int p = pt * T64_T + bc, d = dt * T64_T + bc;
   float acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[i][c] = 0.f;
+  t64_zero(acc);
   float T = 0.f;
-  for (long jc = jlo; jc < jhi; jc += PS_KC) {
+  for (long jc = jlo; jc < jhi; jc += T64_KC) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int k = bk + 4 * q;
@@ -444,46 +362,40 @@ __global__ __launch_bounds__(256) void ps_bwd_dp_kernel(const float* __restrict_
         }
         if (d < D) b = W[(long)(rows ? rows[j] : j) * ldw + d] / row_stat[2 * j];
       }
-      As[k * PS_LD + bc] = a;
-      Bs[k * PS_LD + bc] = b;
+      As[k * T64_LD + bc] = a;
+      Bs[k * T64_LD + bc] = b;
     }
     __syncthreads();
-    ps_mma(As, Bs, rg, cg, acc);
+    t64_mma(As, Bs, rg, cg, acc);
     __syncthreads();
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int pp = pt * PS_T + 4 * rg + i;
+    const int pp = pt * T64_T + 4 * rg + i;
     if (pp >= NP) continue;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const int dd = dt * PS_T + 4 * cg + c;
+      const int dd = dt * T64_T + 4 * cg + c;
       if (dd < D) part[((long)split * NP + pp) * D + dd] = acc[i][c];
     }
   }
   if (dt == 0) {
     s_T[bk][bc] = T;
     __syncthreads();
-    if (t < PS_T && p < NP) part_t[(long)split * NP + p] = (s_T[0][t] + s_T[1][t]) + (s_T[2][t] + s_T[3][t]);
+    if (t < T64_T && p < NP) part_t[(long)split * NP + p] = (s_T[0][t] + s_T[1][t]) + (s_T[2][t] + s_T[3][t]);
   }
 }
 
-// dP[p, d] = (sum over splits - [|P[p]| >= eps] P^[p, d] sum_j g' cos) / max(|P[p]|, eps), the splits added in order
-__global__ __launch_bounds__(256) void ps_bwd_fold_kernel(const float* __restrict__ part, const float* __restrict__ part_t, int n_split,
-                                                          const float* __restrict__ P, const float* __restrict__ pstat, int NP, int D,
-                                                          float* __restrict__ dP) {
-  const long e = blockIdx.x * 256L + threadIdx.x;
-  if (e >= (long)NP * D) return;
-  const int p = (int)(e / D);
-  double s = 0.0, tt = 0.0;
-#pragma unroll 4
-  for (int sp = 0; sp < n_split; ++sp) {
-    s += (double)part[(long)sp * NP * D + e];
-    tt += (double)part_t[(long)sp * NP + p];
+// dP[p, d] = (sum over splits - [|P[p]| >= eps] P^[p, d] sum_j g' cos) / max(|P[p]|, eps), the splits added in order (t64_fold_kernel)
+struct PsFoldEpi {
+  static constexpr bool kColumnSums = true;
+  const float* P;
+  const float* pstat;
+  __device__ __forceinline__ float operator()(long e, int p, float s, float tt) const {
+    const float nc = pstat[2 * p], flag = pstat[2 * p + 1];
+    return fmaf(-(flag * (P[e] / nc)), tt, s) / nc;
   }
-  const float nc = pstat[2 * p], flag = pstat[2 * p + 1];
-  dP[e] = fmaf(-(flag * (P[e] / nc)), (float)tt, (float)s) / nc;
-}
+};
 
 inline bool ps_shape_ok(int D, int NP) { return D >= 1 && D <= PS_MAX_D && NP >= 2 && NP <= PS_MAX_P; }
 
@@ -509,12 +421,12 @@ extern "C" int sbr_proto_sim_fwd(const float* W, long ldw, const int* rows, long
   SBR_REQUIRE(workspace_bytes >= (long)ps_fwd_ws_bytes(R, n_proto), "sbr_proto_sim_fwd: workspace of %ld bytes, needs %ld", workspace_bytes,
               (long)ps_fwd_ws_bytes(R, n_proto));
   hipStream_t s = (hipStream_t)stream;
-  const int nb = ps_fwd_wgs(R), n_tiles = ps_tiles(R);
+  const int nb = ps_fwd_wgs(R), n_tiles = t64_tiles(R);
   double* part_rs = (double*)workspace;
   float* pstat = (float*)(part_rs + nb);
   float* part_cv = pstat + 2 * PS_MAX_P;
   int* part_cj = (int*)(part_cv + (size_t)nb * n_proto);
-  ps_proto_norm_kernel<<<sbr_cdiv(n_proto, 4), 256, 0, s>>>(P, n_proto, D, pstat, proto_stat);
+  t64_norm_kernel<<<sbr_cdiv(n_proto, 4), 256, 0, s>>>(P, n_proto, D, pstat, proto_stat);
   if (stats) {
     ps_fwd_kernel<true><<<nb, 256, 0, s>>>(W, ldw, rows, R, D, P, n_proto, pstat, sim_out, cos_raw, row_stat, row_best, part_cv, part_cj,
                                            part_rs, n_tiles);
@@ -543,7 +455,7 @@ extern "C" int sbr_proto_sim_bwd(const float* G, const float* g_proto, const flo
   }
   SBR_REQUIRE(R > 0 && R < INT_MAX && ldw >= D, "sbr_proto_sim_bwd: needs 0 <= R < 2^31 and ldw >= D");
   SBR_REQUIRE(G && W && P && cos_raw && row_stat && proto_stat && row_best && col_best_row, "sbr_proto_sim_bwd: null operand");
-  const int n_tiles = ps_tiles(R);
+  const int n_tiles = t64_tiles(R);
   if (dE) {
     const int nb = n_tiles < 8192 ? n_tiles : 8192;
     ps_bwd_de_kernel<<<nb, 256, 0, s>>>(G, g_proto, g_batch, W, ldw, rows, R, D, P, n_proto, cos_raw, row_stat, proto_stat, row_best,
@@ -555,10 +467,10 @@ extern "C" int sbr_proto_sim_bwd(const float* G, const float* g_proto, const flo
     const int n_split = ps_splits(R, D, n_proto);
     float* part = (float*)workspace;
     float* part_t = part + (size_t)n_split * n_proto * D;
-    const dim3 grid(n_split, ps_tiles(D), ps_tiles(n_proto));
+    const dim3 grid(n_split, t64_tiles(D), t64_tiles(n_proto));
     ps_bwd_dp_kernel<<<grid, 256, 0, s>>>(G, g_proto, g_batch, W, ldw, rows, R, D, n_proto, cos_raw, row_stat, row_best, col_best_row, part,
                                           part_t, n_tiles);
-    ps_bwd_fold_kernel<<<sbr_cdiv((long)n_proto * D, 256), 256, 0, s>>>(part, part_t, n_split, P, proto_stat, n_proto, D, dP);
+    t64_fold_kernel<<<sbr_cdiv((long)n_proto * D, 256), 256, 0, s>>>(part, part_t, n_split, n_proto, D, PsFoldEpi{P, proto_stat}, dP);
   }
   SBR_CHECK_LAUNCH("sbr_proto_sim_bwd");
   return SBR_OK;

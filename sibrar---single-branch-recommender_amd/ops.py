@@ -781,26 +781,45 @@ class GatherLinearFn(Function):
         return d_table, None, dw
 
 
+# ---- the three fused model ops on the 64 x 64 fp32 tile skeleton (csrc/tile64_f32.h): shared operand checks, workspaces, table gradient ----
+def _tile_operands(table, idx, matrix, who, noun, count, max_d, max_n):
+    """``table[idx]`` against the rows of ``matrix`` (``noun``: 'prototypes' / 'anchors', counted as ``count``): shape and range errors
+    are ``ValueError`` before anything touches the device. -> (table, rows, matrix, R, D, N)"""
+    if table.dim() != 2 or matrix.dim() != 2 or table.shape[1] != matrix.shape[1]:
+        raise ValueError(f'{who}: table {tuple(table.shape)} and {noun} {tuple(matrix.shape)} must be matrices of one width')
+    D, N = int(table.shape[1]), int(matrix.shape[0])
+    if not (1 <= D <= max_d and 2 <= N <= max_n):
+        raise ValueError(f'{who}: needs 1 <= embedding_dim <= {max_d} and 2 <= {count} <= {max_n}, got {D} and {N}')
+    _need_cuda(table, idx, matrix)
+    table = _f32c(table) if table.stride(-1) != 1 or table.dtype != torch.float32 else table
+    rows = None if idx is None else idx.reshape(-1).to(torch.int32).contiguous()
+    R = table.shape[0] if rows is None else rows.numel()
+    return table, rows, _f32c(matrix), R, D, N
+
+
+def _tile_ws(entry, device, R, D, N, backward, min_bytes=8):
+    """the workspace that ``entry`` (a ``*_workspace`` entry point) asks for, never empty"""
+    n = int(getattr(lib(), entry)(R, D, N, 1 if backward else 0))
+    return torch.empty(max(n, min_bytes), device=device, dtype=torch.uint8)
+
+
+def _table_grad(table, rows, dE):
+    """the dense table gradient from dE [R, D] = d / d table[rows] (``rows`` None: the rows are the table), as ``LookupFn`` returns it"""
+    d_table = torch.zeros(table.shape, device=dE.device, dtype=torch.float32)
+    if rows is None:
+        d_table.copy_(dE)
+    elif rows.numel() > 0:
+        D = table.shape[1]
+        call('sbr_scatter_add_rows', ptr(dE), D, None, ptr(rows), ptr(d_table), D, rows.numel(), D, stream())
+    return d_table
+
+
 # ---- ProtoMF: shifted cosine similarity to the prototypes -----------------------------------------------------------------------------
 PROTO_MAX_D, PROTO_MAX_P = 512, 256          # csrc/proto_sim.hip
 
 
 def _proto_operands(table, idx, prototypes, who):
-    if table.dim() != 2 or prototypes.dim() != 2 or table.shape[1] != prototypes.shape[1]:
-        raise ValueError(f'{who}: table {tuple(table.shape)} and prototypes {tuple(prototypes.shape)} must be matrices of one width')
-    D, P = int(table.shape[1]), int(prototypes.shape[0])
-    if not (1 <= D <= PROTO_MAX_D and 2 <= P <= PROTO_MAX_P):
-        raise ValueError(f'{who}: needs 1 <= embedding_dim <= {PROTO_MAX_D} and 2 <= n_prototypes <= {PROTO_MAX_P}, got {D} and {P}')
-    _need_cuda(table, idx, prototypes)
-    table = _f32c(table) if table.stride(-1) != 1 or table.dtype != torch.float32 else table
-    rows = None if idx is None else idx.reshape(-1).to(torch.int32).contiguous()
-    R = table.shape[0] if rows is None else rows.numel()
-    return table, rows, _f32c(prototypes), R, D, P
-
-
-def _proto_ws(device, R, D, P, backward):
-    n = int(lib().sbr_proto_sim_workspace(R, D, P, 1 if backward else 0))
-    return torch.empty(max(n, 8), device=device, dtype=torch.uint8)
+    return _tile_operands(table, idx, prototypes, who, 'prototypes', 'n_prototypes', PROTO_MAX_D, PROTO_MAX_P)
 
 
 class ProtoSimFn(Function):
@@ -820,7 +839,7 @@ class ProtoSimFn(Function):
         row_best = torch.empty(R, device=dev, dtype=torch.int32)
         col_val, col_row = torch.empty(P, **f32), torch.empty(P, device=dev, dtype=torch.int32)
         proto_loss, batch_loss = torch.zeros((), **f32), torch.zeros((), **f32)
-        ws = _proto_ws(dev, R, D, P, False)
+        ws = _tile_ws('sbr_proto_sim_workspace', dev, R, D, P, False)
         _timed(('proto_sim_fwd', R, D, P),
                lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(sim), ptr(cos),
                             ptr(row_stat), ptr(proto_stat), ptr(row_best), ptr(col_val), ptr(col_row), ptr(proto_loss), ptr(batch_loss),
@@ -838,19 +857,12 @@ class ProtoSimFn(Function):
         need_t, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
         dE = torch.empty(R, D, device=cos.device, dtype=torch.float32) if need_t else None
         dP = torch.empty(P, D, device=cos.device, dtype=torch.float32) if need_p else None
-        ws = _proto_ws(cos.device, R, D, P, True) if need_p and R > 0 else None
+        ws = _tile_ws('sbr_proto_sim_workspace', cos.device, R, D, P, True) if need_p and R > 0 else None
         _timed(('proto_sim_bwd', R, D, P),
                lambda: call('sbr_proto_sim_bwd', ptr(g_sim), ptr(g_proto), ptr(g_batch), ptr(table), table.stride(0), ptr(rows), R, D,
                             ptr(protos), P, ptr(cos), ptr(row_stat), ptr(proto_stat), ptr(row_best), ptr(col_row), ptr(dE), ptr(dP),
                             ptr(ws), 0 if ws is None else ws.numel(), stream()))
-        d_table = None
-        if need_t:
-            d_table = torch.zeros(table.shape, device=cos.device, dtype=torch.float32)
-            if rows is None:
-                d_table.copy_(dE)
-            else:
-                call('sbr_scatter_add_rows', ptr(dE), D, None, ptr(rows), ptr(d_table), D, R, D, stream())
-        return d_table, None, dP
+        return _table_grad(table, rows, dE) if need_t else None, None, dP
 
 
 def proto_sim(table: torch.Tensor, idx: Optional[torch.Tensor], prototypes: torch.Tensor) -> torch.Tensor:
@@ -858,7 +870,7 @@ def proto_sim(table: torch.Tensor, idx: Optional[torch.Tensor], prototypes: torc
     [*idx.shape, P]; ``idx`` None: every row of ``table``."""
     table, rows, protos, R, D, P = _proto_operands(table.detach(), idx, prototypes.detach(), 'proto_sim')
     sim = torch.empty(R, P, device=table.device, dtype=torch.float32)
-    ws = _proto_ws(table.device, R, D, P, False)
+    ws = _tile_ws('sbr_proto_sim_workspace', table.device, R, D, P, False)
     _timed(('proto_sim_fwd', R, D, P),
            lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(sim), None, None, None,
                         None, None, None, None, None, ptr(ws), ws.numel(), stream()))
@@ -871,7 +883,7 @@ def cosine_sim(table: torch.Tensor, idx: Optional[torch.Tensor], others: torch.T
     table, rows, others, R, D, P = _proto_operands(table.detach(), idx, others.detach(), 'cosine_sim')
     sim = torch.empty(R, P, device=table.device, dtype=torch.float32)
     cos = torch.empty(R, P, device=table.device, dtype=torch.float32)
-    ws = _proto_ws(table.device, R, D, P, False)
+    ws = _tile_ws('sbr_proto_sim_workspace', table.device, R, D, P, False)
     _timed(('proto_sim_fwd', R, D, P),
            lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(others), P, ptr(sim), ptr(cos), None, None,
                         None, None, None, None, None, ptr(ws), ws.numel(), stream()))
@@ -884,21 +896,7 @@ ANCHOR_TILE, ANCHOR_MAX_WG = 64, 1024        # rows of a workgroup's tile, grid 
 
 
 def _anchor_operands(table, idx, anchors, who):
-    if table.dim() != 2 or anchors.dim() != 2 or table.shape[1] != anchors.shape[1]:
-        raise ValueError(f'{who}: table {tuple(table.shape)} and anchors {tuple(anchors.shape)} must be matrices of one width')
-    D, K = int(table.shape[1]), int(anchors.shape[0])
-    if not (1 <= D <= ANCHOR_MAX_D and 2 <= K <= ANCHOR_MAX_K):
-        raise ValueError(f'{who}: needs 1 <= embedding_dim <= {ANCHOR_MAX_D} and 2 <= n_anchors <= {ANCHOR_MAX_K}, got {D} and {K}')
-    _need_cuda(table, idx, anchors)
-    table = _f32c(table) if table.stride(-1) != 1 or table.dtype != torch.float32 else table
-    rows = None if idx is None else idx.reshape(-1).to(torch.int32).contiguous()
-    R = table.shape[0] if rows is None else rows.numel()
-    return table, rows, _f32c(anchors), R, D, K
-
-
-def _anchor_ws(device, R, D, K, backward):
-    n = int(lib().sbr_anchor_mix_workspace(R, D, K, 1 if backward else 0))
-    return torch.empty(max(n, 8), device=device, dtype=torch.uint8)
+    return _tile_operands(table, idx, anchors, who, 'anchors', 'n_anchors', ANCHOR_MAX_D, ANCHOR_MAX_K)
 
 
 class AnchorMixFn(Function):
@@ -920,7 +918,7 @@ class AnchorMixFn(Function):
         q = dinc = ws = None
         if with_losses and R > 0:
             q, dinc = torch.empty(K, **f32), torch.empty(K, **f32)
-            ws = _anchor_ws(dev, R, D, K, False)
+            ws = _tile_ws('sbr_anchor_mix_workspace', dev, R, D, K, False)
         if R > 0:
             _timed(('anchor_mix_fwd', R, D, K),
                    lambda: call('sbr_anchor_mix_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(anc), K, ptr(r), ptr(c), ptr(lse),
@@ -944,18 +942,11 @@ class AnchorMixFn(Function):
         need_t, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
         dE = torch.empty(R, D, device=c.device, dtype=torch.float32) if need_t else None
         dA = torch.empty(K, D, device=c.device, dtype=torch.float32) if need_a else None
-        ws = _anchor_ws(c.device, R, D, K, True) if need_a and R > 0 else None
+        ws = _tile_ws('sbr_anchor_mix_workspace', c.device, R, D, K, True) if need_a and R > 0 else None
         _timed(('anchor_mix_bwd', R, D, K),
                lambda: call('sbr_anchor_mix_bwd', ptr(g_r), ptr(g_exc), ptr(g_inc), ptr(table), table.stride(0), ptr(rows), R, D, ptr(anc),
                             K, ptr(c), ptr(lse), ptr(dinc), ptr(dE), ptr(dA), ptr(ws), 0 if ws is None else ws.numel(), stream()))
-        d_table = None
-        if need_t:
-            d_table = torch.zeros(table.shape, device=c.device, dtype=torch.float32)
-            if rows is None:
-                d_table.copy_(dE)
-            elif R > 0:
-                call('sbr_scatter_add_rows', ptr(dE), D, None, ptr(rows), ptr(d_table), D, R, D, stream())
-        return d_table, None, dA, None
+        return _table_grad(table, rows, dE) if need_t else None, None, dA, None
 
 
 def anchor_mix(table: torch.Tensor, idx: Optional[torch.Tensor], anchors: torch.Tensor, want: str = 'r') -> torch.Tensor:
@@ -1008,11 +999,6 @@ def _cluster_operands(table, clusters, logits, top, temp, who):
     return None, None, logits, int(logits.shape[0]), D, C
 
 
-def _cluster_ws(device, R, D, C, backward):
-    n = int(lib().sbr_cluster_affil_workspace(R, D, C, 1 if backward else 0))
-    return torch.empty(max(n, 16), device=device, dtype=torch.uint8)
-
-
 def _cluster_fwd(table, clusters, logits, R, D, C, top, temp, want_state):
     dev = (table if logits is None else logits).device
     f32 = dict(device=dev, dtype=torch.float32)
@@ -1021,7 +1007,7 @@ def _cluster_fwd(table, clusters, logits, R, D, C, top, temp, want_state):
     state = torch.empty(R, 4, **f32) if want_state else None
     mask = torch.empty(R, (C + 3) // 4, device=dev, dtype=torch.uint8) if want_state else None
     if R > 0:
-        ws = _cluster_ws(dev, R, D, C, False) if logits is None else None
+        ws = _tile_ws('sbr_cluster_affil_workspace', dev, R, D, C, False, 16) if logits is None else None
         _timed(('cluster_affil_fwd', R, D, C),
                lambda: call('sbr_cluster_affil_fwd', ptr(table), 0 if table is None else table.stride(0), ptr(clusters), ptr(logits), R, D, C,
                             int(top), float(temp), ptr(t), ptr(x), ptr(state), ptr(mask), ptr(ws), 0 if ws is None else ws.numel(), stream()))
@@ -1063,7 +1049,7 @@ class ClusterAffilFn(Function):
             if R == 0:                       # no rows: nothing to launch (an empty table has no device pointer either)
                 return dW, torch.zeros(C, D, device=dev, dtype=torch.float32) if need_c else None, None, None, None
             dC = torch.empty(C, D, device=dev, dtype=torch.float32) if need_c else None
-            ws = _cluster_ws(dev, R, D, C, True) if need_w or need_c else None
+            ws = _tile_ws('sbr_cluster_affil_workspace', dev, R, D, C, True, 16) if need_w or need_c else None
             _timed(('cluster_affil_bwd', R, D, C),
                    lambda: call('sbr_cluster_affil_bwd', ptr(g_x), ptr(g_t), ptr(table), table.stride(0), ptr(cl), ptr(t), R, D, C, ctx.temp,
                                 ptr(state), ptr(mask), ptr(dW), D, ptr(dC), None, ptr(ws), 0 if ws is None else ws.numel(), stream()))

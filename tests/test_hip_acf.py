@@ -172,7 +172,7 @@ def _row_cap_rows():
     return ops.ANCHOR_MAX_WG * ops.ANCHOR_TILE + 1 + 5
 
 
-@pytest.mark.parametrize('R,D,K', [(37, 100, 20), (2048, 64, 130), (512, 512, 256), (3, 1, 2), ('row_cap', 5, 3)])
+@pytest.mark.parametrize('R,D,K', [(37, 100, 20), (130, 33, 70), (2048, 64, 130), (512, 512, 256), (3, 1, 2), ('row_cap', 5, 3)])
 def test_anchor_mix_kernels_against_float64(R, D, K):
     """r, c, both losses, dE and dA of ops.AnchorMixFn against torch autograd in float64. The rows are a permutation of the table, so the
     table gradient is dE read back through the lookup. (512, 512, 256): c has exact zeros in fp32 (asserted): a backward pass that took

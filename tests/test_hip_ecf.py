@@ -86,7 +86,7 @@ def test_g20_ecf_on_hip_kernels(case):
 
 
 # ---- 2. the kernels against float64 -------------------------------------------------------------------------------------------------
-SHAPES = [(200, 8, 6, 2), (1000, 100, 64, 20), (515, 512, 256, 20), (257, 33, 65, 64), (2048, 128, 256, 128), (130, 2, 2, 1)]
+SHAPES = [(200, 8, 6, 2), (1000, 100, 64, 20), (515, 512, 256, 20), (257, 33, 65, 64), (2048, 128, 256, 128), (130, 2, 2, 1), (130, 33, 130, 20)]
 TEMP = 2.0
 
 
