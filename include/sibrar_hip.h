@@ -299,6 +299,33 @@ int sbr_proto_sim_bwd(const float* G, const float* g_proto, const float* g_batch
                       int D, const float* P, int n_proto, const float* cos_raw, const float* row_stat, const float* proto_stat,
                       const int* row_best, const int* col_best_row, float* dE, float* dP, void* workspace, long workspace_bytes,
                       void* stream);
+/* The simplified ProtoMF family's prototype side — algorithms/sgd_alg.py:62-73 (compute_cosine_sim) behind the lookups of
+ * sgd_alg.py:677-678, 742-744, with the ReLU of sgd_alg.py:683, 739, 808, 814 on the other entity's weights and the dot over the
+ * prototypes of sgd_alg.py:687, 750, 823-824 (additive to ABI 4; csrc/proto_score.hip). Two forms of one op, selected by Wt:
+ *   e = W[rows[j], :] (rows NULL: row j; the gather is fused)      cos[j, p] = clamp(e^ . P^_p, -1, 1),  x^ = x / max(|x|, 1e-12)
+ *   cosine form (Wt NULL; out, widx NULL; fan ignored but >= 1): cos_out [R, P] is written
+ *   score form: every row j carries fan >= 1 weight rows w[j, f, :] = Wt[widx[j fan + f], :] (widx NULL: row j fan + f; row stride
+ *     ldwt >= n_proto):  out[j, f] = sum_p cos[j, p] max(w[j, f, p], 0); cos_out may be NULL. The gathered, relu'd weights are never
+ *     written; for n_proto > 64 the partial dots of the 64-wide prototype tiles are added in tile order.
+ * A NaN stays a NaN (torch.clamp). 1 <= D <= 512, 2 <= n_proto <= 256, 1 <= fan, R fan < 2^31 (anything else fails through
+ * sbr_last_error; sbr_proto_score_workspace returns 0), R = 0 returns SBR_OK. Saved for the backward pass (what sbr_proto_sim_fwd
+ * keeps): cos_raw [R, P] (the un-clamped cosine), row_stat [R, 2] and proto_stat [P, 2] = {max(|x|, eps), |x| >= eps ? 1 : 0}; any may
+ * be NULL in the evaluation form. workspace: sbr_proto_score_workspace(R, D, n_proto, 0) bytes (backward: (..., 1)).
+ * Backward: G is the upstream gradient — of cos, [R, P], in the cosine form; of out, [R, fan], in the score form, where
+ * dcos[j, p] = sum_f G[j, f] max(w[j, f, p], 0) is formed inside the kernels. The clamp passes the gradient where -1 <= cos <= 1
+ * (torch.clamp), a norm below eps takes torch's clamp_min gradient. dE [R, D] is the gradient of the gathered rows (scatter it with
+ * sbr_scatter_add_rows), dP [P, D] that of the prototypes, dWrows [R fan, P] (score form) that of the gathered weight rows:
+ * G[j, f] cos[j, p] where w > 0, else 0 (torch's ReLU: 0 at w == 0); each may be NULL. R = 0 zeroes dP.
+ * One form only: dP is one partial per row split folded in split order, no atomics; the split count depends on (R, D, n_proto) only —
+ * valid in deterministic mode, never a non-deterministic launch. */
+long sbr_proto_score_workspace(long R, int D, int n_proto, int backward);
+int sbr_proto_score_fwd(const float* W, long ldw, const int* rows, long R, int D, const float* P, int n_proto, const float* Wt,
+                        long ldwt, const int* widx, int fan, float* cos_out, float* out, float* cos_raw, float* row_stat,
+                        float* proto_stat, void* workspace, long workspace_bytes, void* stream);
+int sbr_proto_score_bwd(const float* G, const float* W, long ldw, const int* rows, long R, int D, const float* P, int n_proto,
+                        const float* Wt, long ldwt, const int* widx, int fan, const float* cos_raw, const float* row_stat,
+                        const float* proto_stat, float* dE, float* dP, float* dWrows, void* workspace, long workspace_bytes,
+                        void* stream);
 /* ACF's anchor mixing — algorithms/sgd_alg.py:261-276 (ACF.get_user_representations / get_item_representations: lookup, e @ anchors^T,
  * softmax, c @ anchors) with the two entropy regularisers of ACF.forward, sgd_alg.py:246-254, whose exclusiveness term is
  * entropy_from_softmax, sgd_alg.py:76-85 (additive to ABI 4; csrc/anchor_mix.hip):

@@ -17,6 +17,7 @@ from .sbnet import (FeatureEmbedding, ItemFeatureMatrixFactorization, SGDBasedRe
 from .dropoutnet import DropoutNet, DropoutNetEntity                                      # noqa: F401
 from .deepmf import DeepMatrixFactorization                                                # noqa: F401
 from .protomf import IProtoMF, PrototypeWrapper, UIProtoMF, UProtoMF                       # noqa: F401
+from .protomfs import IProtoMFs, UIProtoMFs, UIProtoMFsCombine, UProtoMFs                   # noqa: F401
 from .acf import ACF                                                                        # noqa: F401
 from .ecf import ECF, ecf_tag_matrix                                                        # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
@@ -44,8 +45,10 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
         torch.cuda.manual_seed_all(seed)
     ops.set_deterministic(deterministic)
 
-# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .acf / .ecf -> class
+# the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
+# .uiprotomfs / .acf / .ecf -> class
 # (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
-              'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'acf': ACF, 'ecf': ECF}
+              'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
+              'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF}

@@ -890,6 +890,95 @@ def cosine_sim(table: torch.Tensor, idx: Optional[torch.Tensor], others: torch.T
     return cos.clamp_(min=-1., max=1.).view(*((R,) if idx is None else tuple(idx.shape)), P)
 
 
+# ---- ProtoMFs: plain cosine similarity to the prototypes, and its dot with the relu'd weights of the other entity -------------------------
+class ProtoCosFn(Function):
+    """sgd_alg.py:62-73 (compute_cosine_sim) on ``table[idx]`` against ``prototypes`` (sgd_alg.py:677-678, 742-746), differentiable:
+    ``-> clamp(cos, -1, 1) [*idx.shape, P]`` (``idx`` None: every row of ``table``). The lookup is fused; the backward pass returns the
+    dense table gradient, as ``LookupFn`` does, and the prototype gradient. One fixed-order form (csrc/proto_score.hip)."""
+
+    @staticmethod
+    def forward(ctx, table, idx, prototypes):
+        table, rows, protos, R, D, P = _proto_operands(table, idx, prototypes, 'ProtoCosFn')
+        f32 = dict(device=table.device, dtype=torch.float32)
+        cos, raw = torch.empty(R, P, **f32), torch.empty(R, P, **f32)
+        row_stat, proto_stat = torch.empty(R, 2, **f32), torch.empty(P, 2, **f32)
+        ws = _tile_ws('sbr_proto_score_workspace', table.device, R, D, P, False)
+        _timed(('proto_score_fwd', R, D, P, 0),
+               lambda: call('sbr_proto_score_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, None, 0, None, 1, ptr(cos),
+                            None, ptr(raw), ptr(row_stat), ptr(proto_stat), ptr(ws), ws.numel(), stream()))
+        ctx.save_for_backward(table, rows, protos, raw, row_stat, proto_stat)
+        return cos.view(*((R,) if idx is None else tuple(idx.shape)), P)
+
+    @staticmethod
+    def backward(ctx, g):
+        table, rows, protos, raw, row_stat, proto_stat = ctx.saved_tensors
+        (R, P), D = raw.shape, table.shape[1]
+        g = _f32c(g).reshape(R, P)
+        need_t, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        dE = torch.empty(R, D, device=raw.device, dtype=torch.float32) if need_t else None
+        dP = torch.empty(P, D, device=raw.device, dtype=torch.float32) if need_p else None
+        ws = _tile_ws('sbr_proto_score_workspace', raw.device, R, D, P, True) if need_p and R > 0 else None
+        _timed(('proto_score_bwd', R, D, P, 0),
+               lambda: call('sbr_proto_score_bwd', ptr(g), ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, None, 0, None, 1,
+                            ptr(raw), ptr(row_stat), ptr(proto_stat), ptr(dE), ptr(dP), None, ptr(ws), 0 if ws is None else ws.numel(),
+                            stream()))
+        return _table_grad(table, rows, dE) if need_t else None, None, dP
+
+
+class ProtoScoreFn(Function):
+    """The training logit of the simplified ProtoMF family in one op — sgd_alg.py:676-688, 738-751, 806-826:
+    ``out[j, f] = sum_p clamp(cos(table[idx[j]], prototypes[p]), -1, 1) * relu(weights[widx[j * fan + f], p]) -> [R, fan]``, R =
+    idx.numel(). ``widx`` None: ``weights`` holds the R * fan weight rows themselves, in order. Neither the cosines' lookup nor the
+    relu'd weight gather is written. The backward pass returns the dense table gradient, the prototype gradient and the weight
+    gradient: dense (scattered over ``widx``) when ``widx`` is given, the row gradient itself when it is None; zero where
+    ``weights <= 0``, as torch's ReLU. One fixed-order form (csrc/proto_score.hip)."""
+
+    @staticmethod
+    def forward(ctx, table, idx, prototypes, weights, widx, fan):
+        fan = int(fan)
+        if weights.dim() != 2 or prototypes.dim() != 2 or weights.shape[1] != prototypes.shape[0]:
+            raise ValueError(f'ProtoScoreFn: weights {tuple(weights.shape)} must be a matrix as wide as the n_prototypes of prototypes '
+                             f'{tuple(prototypes.shape)}')
+        R = int(table.shape[0] if idx is None else idx.numel()) if table.dim() == 2 else 0
+        n_w = int(weights.shape[0] if widx is None else widx.numel())
+        if fan < 1 or n_w != R * fan or R * fan >= 2 ** 31:
+            raise ValueError(f'ProtoScoreFn: needs 1 <= fan, R * fan < 2^31 and R * fan weight rows ({"weights" if widx is None else "widx"}), '
+                             f'got R = {R}, fan = {fan} and {n_w}')
+        table, rows, protos, R, D, P = _proto_operands(table, idx, prototypes, 'ProtoScoreFn')
+        _need_cuda(weights, widx)
+        wt = _f32c(weights) if weights.stride(-1) != 1 or weights.dtype != torch.float32 else weights
+        wrows = None if widx is None else widx.reshape(-1).to(torch.int32).contiguous()
+        f32 = dict(device=table.device, dtype=torch.float32)
+        out, raw = torch.empty(R, fan, **f32), torch.empty(R, P, **f32)
+        row_stat, proto_stat = torch.empty(R, 2, **f32), torch.empty(P, 2, **f32)
+        ws = _tile_ws('sbr_proto_score_workspace', table.device, R, D, P, False)
+        _timed(('proto_score_fwd', R, D, P, fan),
+               lambda: call('sbr_proto_score_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(wt), wt.stride(0),
+                            ptr(wrows), fan, None, ptr(out), ptr(raw), ptr(row_stat), ptr(proto_stat), ptr(ws), ws.numel(), stream()))
+        ctx.save_for_backward(table, rows, protos, wt, wrows, raw, row_stat, proto_stat)
+        ctx.fan = fan
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        table, rows, protos, wt, wrows, raw, row_stat, proto_stat = ctx.saved_tensors
+        (R, P), D, fan = raw.shape, table.shape[1], ctx.fan
+        g = _f32c(g).reshape(R, fan)
+        need_t, need_p, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        f32 = dict(device=raw.device, dtype=torch.float32)
+        dE = torch.empty(R, D, **f32) if need_t else None
+        dP = torch.empty(P, D, **f32) if need_p else None
+        dW = torch.empty(R * fan, P, **f32) if need_w else None
+        ws = _tile_ws('sbr_proto_score_workspace', raw.device, R, D, P, True) if need_p and R > 0 else None
+        _timed(('proto_score_bwd', R, D, P, fan),
+               lambda: call('sbr_proto_score_bwd', ptr(g), ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(wt),
+                            wt.stride(0), ptr(wrows), fan, ptr(raw), ptr(row_stat), ptr(proto_stat), ptr(dE), ptr(dP), ptr(dW), ptr(ws),
+                            0 if ws is None else ws.numel(), stream()))
+        if need_w and wrows is not None:
+            dW = _table_grad(wt, wrows, dW)
+        return _table_grad(table, rows, dE) if need_t else None, None, dP, dW, None, None
+
+
 # ---- ACF: softmax mixing of the anchors ------------------------------------------------------------------------------------------------
 ANCHOR_MAX_D, ANCHOR_MAX_K = 512, 256        # csrc/anchor_mix.hip
 ANCHOR_TILE, ANCHOR_MAX_WG = 64, 1024        # rows of a workgroup's tile, grid cap of either pass (AM_T, AM_MAX_WG)
