@@ -517,7 +517,10 @@ int sbr_adam_step_zero_grad(int kind, float* p, float* g, float* m, float* v, lo
 /* copy_n (0 .. 256) doubles copy_src -> copy_dst ride on the same launch: the loss scalars of a captured step, whose buffer the
  * next replay overwrites (copy_n = 0: no copy). */
 /* The same dense-optimizer semantics for a [n_rows, D] lookup table, deferred row by row (train/trainer.py:62-68 updates every row
- * every step; a row without gradient can take its zero-gradient updates later, in order, bit-identically). mode 0: bring the rows
+ * every step; a row without gradient can take its zero-gradient updates later, in order, bit-identically — for every eps the
+ * caller passes: the replay's short cut for rows whose first moment is exactly zero is taken only when eps > 0 (as rounded to fp32),
+ * where the dense step's denominator is positive; with eps = 0 such a row is replayed through the full step and, like the dense
+ * kernel and torch.optim.AdamW, ends with NaN parameters where its second moment is zero). mode 0: bring the rows
  * named by ids (int64 or int32, optionally through rowmap) up to step - 1 (before the forward pass reads them); mode 1: the same,
  * then apply `step` with their gradient rows, zero those gradient rows, record the step's scalars in sched[step]; mode 2: flush
  * every row to `step` (before any other reader). claim, last: int32 [n_rows * ceil(D / 64)] (one entry per 64-element sub-row, the

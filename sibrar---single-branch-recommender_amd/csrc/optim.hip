@@ -89,11 +89,15 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
 // records the entry of its own step replays that step for the rows of its sweep
 // A zero-gradient step of an element whose first moment is exactly zero — a row that has never received a gradient, or one idle for
 // ~900 steps (0.9^n underflows) — is `v *= beta2; p *= 1 - lr wd` bit for bit under AdamW: lerp(m, 0) = +0, v * beta2 + 0 = v * beta2,
-// and p - step * (+0 / denom) = p for any finite v (a NaN / inf second moment takes the general path). When that holds for the whole
+// and p - step * (+0 / denom) = p for any finite v AS LONG AS denom > 0, which eps > 0 guarantees (a NaN / inf second moment takes
+// the general path). With eps == 0 it does not hold: a row that never received a gradient has v = 0, the dense step divides +0 by
+// sqrt(0) / sqrt(bc2) + 0 and its parameter becomes NaN (torch.optim.AdamW does the same), and a tiny v can reach 0 under `v *= beta2`
+// in the middle of a run of idle steps — so eps == 0 (as rounded to fp32) never takes the short cut. The condition is uniform over
+// the launch. When the short cut holds for the whole
 // wave the replay skips the square root and the two divisions: 2 vector instructions per element-step instead of ~60. The sweep of a
 // cold table (c4: a row is touched every ~4,000 steps) and of the rows a short run never reaches costs next to nothing then.
 __device__ __forceinline__ bool adam_wave_is_idle(float me, float ve, const AdamHyper& h) {
-  return h.decoupled && __all(me == 0.f && ve <= 3.4028234663852886e38f);
+  return h.decoupled && h.eps > 0.f && __all(me == 0.f && ve <= 3.4028234663852886e38f);
 }
 __device__ __forceinline__ void adam_idle_step(float& pe, float& me, float& ve, const AdamHyper& h) {
 #pragma clang fp contract(off)
