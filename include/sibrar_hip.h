@@ -549,11 +549,15 @@ int sbr_mask_scores(float* scores, long ld, const long* u_idx, const long* excl_
 /* the same when `scores` holds the item columns [item_offset, item_offset + n_cols) only (new: item-sharded evaluation) */
 int sbr_mask_scores_shard(float* scores, long ld, const long* u_idx, const long* excl_indptr, const int* excl_indices, long Bu,
                           int item_offset, int n_cols, void* stream);
-/* exact per-row top-k, sorted by (score desc, index asc) — torch.topk at eval/eval.py:320 and inside rmet.calculate */
+/* exact per-row top-k, sorted by (score desc, index asc) — torch.topk at eval/eval.py:320 and inside rmet.calculate. The list is the
+ * first k of the stable descending order of the row (torch.sort(descending=True, stable=True)): every NaN, whatever its sign bit,
+ * ranks ahead of +inf; -0.0 and +0.0 are the same score; equal scores (NaNs among themselves, the two zeros) go in ascending index.
+ * A NaN is returned as a NaN (not necessarily the same bits), a zero as +0.0, every other value bit for bit. 1 <= k <= min(I, 256). */
 int sbr_topk_rows(const float* scores, long ld, long Bu, int I, int k, float* out_val, int* out_idx, void* stream);
 /* exact merge of W per-shard top-k lists of an item-sharded evaluation (new: the reference has no multi-GPU path):
  * vals / idxs: [W, Bu, k] (all-gathered; idx < 0 = empty slot, idx = global item index), W * k <= 256 -> [Bu, k] sorted by
- * (score desc, index asc). */
+ * (score desc, index asc) under the rule of sbr_topk_rows (NaN first, -0.0 == +0.0, ties by ascending item index). An empty slot
+ * ranks behind every real entry — a real entry whose score is -inf keeps its index and precedes it — and comes out as (-inf, -1). */
 int sbr_merge_topk(const float* vals, const int* idxs, int W, long Bu, int k, float* out_val, int* out_idx, void* stream);
 /* NDCG / recall / precision @ ks from top-k indices and CSR labels — eval/metrics.py:4-105. out: [3, n_ks, Bu]. */
 int sbr_rank_metrics(const int* topk_idx, int kmax, const long* u_idx, const long* label_indptr, const int* label_indices,

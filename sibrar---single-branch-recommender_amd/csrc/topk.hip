@@ -3,7 +3,7 @@
 //   sbr_topk_rows     exact top-k of every score row, sorted by (score desc, index asc)  (torch.topk, eval.py:320)
 //   sbr_rank_metrics  NDCG / recall / precision @k from the top-k indices and the CSR labels (eval/metrics.py:4-105)
 // Integer / ordering work: results are exact (no tolerance); the only freedom is the order of exactly tied scores,
-// which torch.topk leaves unspecified and which is fixed here to "lower index first".
+// which torch.topk leaves unspecified and which is fixed here to "lower index first" (NaN first, -0 == +0: the rule at f2key).
 #include "common.h"
 
 __global__ void mask_scores_kernel(float* __restrict__ S, long ld, const long* __restrict__ u_idx,
@@ -36,9 +36,20 @@ extern "C" int sbr_mask_scores_shard(float* scores, long ld, const long* u_idx, 
   return SBR_OK;
 }
 
-// order-preserving map float -> uint32 (larger float <=> larger key; -inf is the smallest non-NaN key)
+// The ordering rule of sbr_topk_rows and sbr_merge_topk: a list is the first k of the STABLE DESCENDING order of the row, as
+// torch.sort(descending=True, stable=True) gives it —
+//   * every NaN, whatever its sign bit or payload, ranks ahead of +inf (torch.topk at eval/eval.py:320 ranks NaN first);
+//   * -0.0 and +0.0 are the same score;
+//   * equal scores (the NaNs among themselves, the two zeros) go in ascending index.
+// f2key is the order-preserving map float -> uint32 of that rule (larger float <=> larger key; -inf is the smallest key). It is
+// canonical: all NaNs share the top key 0xFFFFFFFF and -0.0 has the key of +0.0, so that the composite (key, ~index) breaks those
+// ties by index like any other. key2f therefore returns a canonical NaN (0x7FFFFFFF) for a NaN and +0.0 for either zero; every
+// other value comes back bit for bit. No key is 0, which the composites below use for "empty".
 __device__ __forceinline__ unsigned int f2key(float f) {
-  const unsigned int u = __float_as_uint(f);
+  unsigned int u = __float_as_uint(f);
+  const unsigned int mag = u & 0x7FFFFFFFu;
+  u = mag > 0x7F800000u ? 0x7FFFFFFFu : u;      // NaN of either sign -> the largest positive pattern
+  u = mag == 0u ? 0u : u;                       // -0.0 -> +0.0
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float key2f(unsigned int k) {
@@ -286,7 +297,8 @@ extern "C" int sbr_topk_rows(const float* scores, long ld, long Bu, int I, int k
 // ---------------------------------------------------------------------------------------------------------------
 // Exact merge of W per-shard top-k lists (item-sharded scoring, SURVEY 8(e): every rank scores its item shard, the lists are
 // all-gathered): out[b] = the k best of the W * k entries (score desc, item index asc — the rule every top-k kernel here
-// uses; idx < 0 marks an empty slot). One wave per user; every entry is ranked against all others by counting over
+// uses, with f2key's NaN-first and -0 == +0; idx < 0 marks an empty slot, which ranks behind every real entry, a real entry
+// with score -inf included). One wave per user; every entry is ranked against all others by counting over
 // v_readlane broadcasts (W * k <= 256: up to four entries per lane), the entry of rank j writes output position j.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void merge_topk_kernel(const float* __restrict__ vals, const int* __restrict__ idxs, int W,
