@@ -620,6 +620,36 @@ long sbr_score_topk_f32s_d256_workspace(long Bu, int I, int k);
  * the remainder planes are NaN: such item values are not supported): the item operand of sbr_score_topk_f32s (eval/eval.py:216-222) */
 int sbr_split_f32_to_bf16x3(const float* X, void* Y_bf16x3, long n, void* stream);
 
+/* ---- neighbourhood models on 0/1 data (csrc/knn.hip) ---------------------------------------------------------------------------
+ * compute_similarity_top_k + compute_*_sim_mtx — utilities/similarities.py:18-130 (called from algorithms/knn_algs.py:94, :114).
+ * X [n, m]: binary CSR (indptr int64 [n + 1], indices int32 sorted ascending within a row, unique; no values: every entry is 1),
+ * X^T [m, n] in the same form (t_indptr, t_indices); m <= 2^24. For every row i of [r0, r1) the candidates are the rows j != i with
+ * c = |row i & row j| > 0; with ni, nj the entry counts of the two rows, all in fp32, one correctly rounded operation per step, no
+ * contraction, integers converted once (they are exact):
+ *   sim 0 cosine             v = c / (sqrtf(ni) * sqrtf(nj))
+ *   sim 1 jaccard            v = c / float(ni + nj - c)
+ *   sim 2 asymmetric_cosine  v = c / (powf(ni, alpha) * powf(nj, 1.f - alpha))
+ *   sim 3 sorensen_dice      v = (2.f * c) / float(ni + nj)
+ *   sim 4 tversky            v = c / ((c + alpha * float(ni - c)) + beta * float(nj - c))
+ *   value = v * (c / (c + shrinkage))
+ * The list of row i is the first min(k, candidates) of them by (value descending, index ascending), the rule of sbr_topk_rows:
+ * nbr_idx int32 [n, k], nbr_val fp32 [n, k], nbr_len int32 [n]; the slots behind nbr_len[i] hold (-1, 0). Only the rows of [r0, r1)
+ * are written. 1 <= k <= 256; alpha, beta, shrinkage >= 0. tile_cols: entity columns per tile of LDS counters (4 bytes each);
+ * 0 = min(max(n, 64), 32768); a request over 160 KiB of LDS is an error. Integer LDS atomics only: the same bits on every run,
+ * valid in deterministic mode. New (additive to ABI 4). */
+int sbr_knn_topk(const long* indptr, const int* indices, const long* t_indptr, const int* t_indices, int n, int m, int r0, int r1,
+                 int sim, float alpha, float beta, float shrinkage, int k, int tile_cols, int* nbr_idx, float* nbr_val, int* nbr_len,
+                 void* stream);
+/* out[b, 0 .. n_cols) = X[rows[b]] . Y as dense fp32 rows with leading dimension ld (rows NULL: row b) — both predictions:
+ * `matrix @ sim_mtx.T` (algorithms/knn_algs.py:116: X = interactions, Y = S^T) and `sim_mtx @ matrix` (knn_algs.py:96: X = S,
+ * Y = interactions). X and Y are CSR (indptr int64, indices int32 sorted ascending and unique within a row); x_data / y_data fp32 or
+ * NULL = ones. An element starts at +0 and receives its terms in ascending order of X's column as acc = fmaf(x, y, acc): one owner, one
+ * rounding per term, no atomics, the same bits on every run. Every element of the addressed rows' [0, n_cols) is written (zeros
+ * included), nothing else. tile_cols: columns per workgroup (0 = min(n_cols, 8192); at most 16384). New (additive to ABI 4). */
+int sbr_csr_rows_times_csr(const long* x_indptr, const int* x_indices, const float* x_data, const long* rows, long B,
+                           const long* y_indptr, const int* y_indices, const float* y_data, int n_cols, int tile_cols, float* out,
+                           long ld, void* stream);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

@@ -1,0 +1,368 @@
+// Neighbourhood models on 0/1 interaction data (algorithms/knn_algs.py: UserKNN, ItemKNN).
+//   sbr_knn_topk            the k most similar rows of every row of a binary CSR matrix: co-occurrence counts, similarity value and
+//                           top-k selection of one row inside one workgroup (utilities/similarities.py:18-130)
+//   sbr_csr_rows_times_csr  dense rows of a CSR x CSR product: both predictions (knn_algs.py:96, :116)
+// Nothing of size n x n or block x n exists: a workgroup owns one row of the similarity matrix from the first count to the sorted list.
+// No float atomics anywhere: the counts are integers (LDS integer atomics: exact, order-free), every float has one owner and a fixed
+// operation order, so both entries give the same bits on every run and are valid in deterministic mode.
+#include "common.h"
+
+#define KNN_THREADS 1024
+#define KNN_WAVES (KNN_THREADS / 64)
+#define KNN_K_MAX 256                // the limit of sbr_topk_rows
+#define KNN_TILE_DEFAULT 32768       // u32 counters of one tile: 128 KiB
+#define KNN_LDS_MAX 163840           // 160 KiB per CU, all of which one workgroup may use
+#define KNN_M_MAX (1 << 24)          // counts and row sizes are converted to fp32 exactly
+
+#define KNN_COSINE 0
+#define KNN_JACCARD 1
+#define KNN_ASYMMETRIC_COSINE 2
+#define KNN_SORENSEN_DICE 3
+#define KNN_TVERSKY 4
+
+// The similarity of two rows with c > 0 common features, ni and nj features each. Every operation is one correctly rounded fp32
+// operation in exactly this order (no contraction of a product and a sum into an fma); the integer sums are exact and are converted
+// once. include/sibrar_hip.h states the same order, tests/knn_ref.py derives its bound from it.
+__device__ __forceinline__ float knn_value(int sim, unsigned int c, int ni, int nj, float alpha, float beta, float shrinkage) {
+#pragma clang fp contract(off)
+  const float cf = (float)c;
+  float v;
+  switch (sim) {
+    case KNN_COSINE: {
+      const float d = sqrtf((float)ni) * sqrtf((float)nj);
+      v = cf / d;
+      break;
+    }
+    case KNN_JACCARD:
+      v = cf / (float)(ni + nj - (int)c);
+      break;
+    case KNN_ASYMMETRIC_COSINE: {
+      const float oma = 1.f - alpha;
+      const float d = powf((float)ni, alpha) * powf((float)nj, oma);
+      v = cf / d;
+      break;
+    }
+    case KNN_SORENSEN_DICE:
+      v = (2.f * cf) / (float)(ni + nj);
+      break;
+    default: {    // KNN_TVERSKY
+      const float a = alpha * (float)(ni - (int)c), b = beta * (float)(nj - (int)c);
+      const float d = (cf + a) + b;
+      v = cf / d;
+      break;
+    }
+  }
+  const float s = cf / (cf + shrinkage);
+  return v * s;
+}
+
+// One histogram add. Similarities crowd into a few exponents, so in the leading radix passes most lanes of a wave name the same
+// bin: when they all do, one lane adds the wave's count instead of up to 64 adds queueing on one address. Called by whole waves.
+__device__ __forceinline__ void knn_hist_add(unsigned int* hist, bool active, unsigned int digit) {
+  const unsigned long long act = __ballot(active);
+  if (act == 0ull) return;
+  const int src = __ffsll((long long)act) - 1;
+  const unsigned int first = (unsigned int)__shfl((int)digit, src, 64);
+  if (__ballot(active && digit == first) == act) {
+    if ((int)(threadIdx.x & 63) == src) atomicAdd(&hist[first], (unsigned int)__popcll(act));
+  } else if (active) {
+    atomicAdd(&hist[digit], 1u);
+  }
+}
+
+// The radix step of wave 0: the bin d (from 255 down) at which the running count reaches `need`; -> true in the lane that holds it,
+// with the count of the bins above it and the bin's own count. Lane l owns the bins 255 - 4 l ... 252 - 4 l. total: all bins.
+__device__ __forceinline__ bool knn_find_bin(const unsigned int* hist, unsigned int need, int lane, int& d, unsigned int& above,
+                                             unsigned int& own, unsigned int& total) {
+  unsigned int h[4], s = 0u;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { h[q] = hist[255 - 4 * lane - q]; s += h[q]; }
+  unsigned int incl = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned int up = (unsigned int)__shfl_up((int)incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  total = (unsigned int)__shfl((int)incl, 63, 64);
+  unsigned int a = incl - s;
+  bool found = false;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (!found && a + h[q] >= need) { found = true; d = 255 - 4 * lane - q; above = a; own = h[q]; }
+    a += h[q];
+  }
+  const unsigned long long f = __ballot(found);
+  return found && lane == __ffsll((long long)f) - 1;
+}
+
+// One workgroup per row i of X. The entity columns are covered by tiles of `tw` u32 counters in LDS. Per tile:
+//   count    wave w takes the features w, w + 16, ... of row i and walks X^T's row of each (entered at the tile's start by a lower
+//            bound), adding 1 to cnt[j - t0];
+//   value    every counter c > 0 with j != i is replaced in place by the bits of its similarity (> 0, so the bits order like the
+//            values), everything else by 0;
+//   select   the k largest composites (value bits << 32 | 0xFFFFFFFF - j: value descending, index ascending) among the list carried
+//            from the earlier tiles and this tile's entries, by radix select on the composite (4 passes on the value; 4 more on the
+//            index only when equal values straddle the k-th place), then compaction into the second list buffer.
+// After the last tile the list is sorted (bitonic) and written with its length and the (-1, 0) padding.
+__global__ __launch_bounds__(KNN_THREADS) void knn_topk_kernel(const long* __restrict__ indptr, const int* __restrict__ indices,
+                                                                const long* __restrict__ t_indptr, const int* __restrict__ t_indices,
+                                                                int n, int r0, int sim, float alpha, float beta, float shrinkage, int k,
+                                                                int kpad, int tw, int* __restrict__ nbr_idx, float* __restrict__ nbr_val,
+                                                                int* __restrict__ nbr_len) {
+  extern __shared__ unsigned int cnt[];
+  __shared__ unsigned long long lists[2][KNN_K_MAX];
+  __shared__ unsigned int hist[256];
+  __shared__ unsigned int s_prefix_hi, s_prefix_lo, s_need, s_take_all, s_done, s_cnt;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int i = r0 + (int)blockIdx.x;
+  const long f_beg = indptr[i], f_end = indptr[i + 1];
+  const int ni = (int)(f_end - f_beg);
+  int cur = 0;                 // lists[cur]: the list carried so far, n_list entries, unsorted
+  unsigned int n_list = 0;
+
+  for (int t0 = 0; t0 < n && ni > 0; t0 += tw) {
+    const int t1 = t0 + tw < n ? t0 + tw : n, width = t1 - t0;
+    for (int x = t; x < width; x += KNN_THREADS) cnt[x] = 0u;
+    __syncthreads();
+    // ---- count
+    for (long p = f_beg + w; p < f_end; p += KNN_WAVES) {
+      const int f = indices[p];
+      long lo = t_indptr[f];
+      const long end = t_indptr[f + 1];
+      if (t0 > 0) {            // first entry with entity id >= t0
+        long hi = end;
+        while (lo < hi) {
+          const long mid = (lo + hi) >> 1;
+          if (t_indices[mid] < t0) lo = mid + 1; else hi = mid;
+        }
+      }
+      for (long q = lo + lane; q < end; q += 64) {
+        const unsigned int x = (unsigned int)(t_indices[q] - t0);
+        if (x >= (unsigned int)width) break;            // sorted: everything behind it lies in a later tile
+        atomicAdd(&cnt[x], 1u);
+      }
+    }
+    __syncthreads();
+    // ---- value, in place
+    for (int x = t; x < width; x += KNN_THREADS) {
+      const unsigned int c = cnt[x];
+      const int j = t0 + x;
+      if (c != 0u) cnt[x] = j == i ? 0u : __float_as_uint(knn_value(sim, c, ni, (int)(indptr[j + 1] - indptr[j]), alpha, beta, shrinkage));
+    }
+    if (t == 0) { s_take_all = 0u; s_done = 0u; }
+    __syncthreads();
+    // ---- select: the composite of the k-th largest entry of (carried list, tile)
+    unsigned int pre_hi = 0u, pre_lo = 0u, need = (unsigned int)k;
+    for (int pass = 0; pass < 8; ++pass) {
+      const int shift = 24 - 8 * (pass & 3);
+      const bool on_index = pass >= 4;
+      const unsigned int hi_mask = (pass & 3) == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
+      if (t < 256) hist[t] = 0u;
+      __syncthreads();
+      for (int x = t; x < (int)n_list; x += KNN_THREADS) {
+        const unsigned long long e = lists[cur][x];
+        const unsigned int vb = (unsigned int)(e >> 32), ib = (unsigned int)e;
+        const bool in = on_index ? (vb == pre_hi && (ib & hi_mask) == pre_lo) : ((vb & hi_mask) == pre_hi);
+        if (in) atomicAdd(&hist[((on_index ? ib : vb) >> shift) & 255u], 1u);
+      }
+      for (int x0 = 0; x0 < width; x0 += KNN_THREADS) {
+        const int x = x0 + t;
+        const unsigned int vb = x < width ? cnt[x] : 0u, ib = 0xFFFFFFFFu - (unsigned int)(t0 + x);
+        const bool in = vb != 0u && (on_index ? (vb == pre_hi && (ib & hi_mask) == pre_lo) : ((vb & hi_mask) == pre_hi));
+        knn_hist_add(hist, in, ((on_index ? ib : vb) >> shift) & 255u);
+      }
+      __syncthreads();
+      if (w == 0) {
+        int d = 0;
+        unsigned int above = 0u, own = 0u, total = 0u;
+        const bool mine = knn_find_bin(hist, need, lane, d, above, own, total);
+        if (pass == 0 && total <= (unsigned int)k) {
+          if (lane == 0) s_take_all = 1u;                           // everything fits: no threshold
+        } else if (mine) {                                          // (a bin is always found: the prefix group holds >= need entries)
+          if (on_index) s_prefix_lo = pre_lo | ((unsigned int)d << shift);
+          else { s_prefix_hi = pre_hi | ((unsigned int)d << shift); s_prefix_lo = 0u; }
+          s_need = need - above;
+          // the value is fixed after pass 3: if every entry that has it is needed, the index does not matter
+          if (pass == 3 && own == need - above) s_done = 1u;
+        }
+      }
+      __syncthreads();
+      pre_hi = s_prefix_hi;
+      pre_lo = s_prefix_lo;
+      need = s_need;
+      if (s_take_all || s_done) break;             // uniform: read behind the barrier, written before it
+    }
+    const unsigned long long thr = s_take_all ? 1ull : (((unsigned long long)pre_hi << 32) | (unsigned long long)pre_lo);
+    // ---- compaction of every composite >= thr into the other buffer (the order is fixed by the final sort)
+    if (t == 0) s_cnt = 0u;
+    __syncthreads();
+    const int nxt = cur ^ 1;
+    for (int x = t; x < (int)n_list; x += KNN_THREADS) {
+      const unsigned long long e = lists[cur][x];
+      if (e >= thr) {
+        const unsigned int pos = atomicAdd(&s_cnt, 1u);
+        if (pos < (unsigned int)k) lists[nxt][pos] = e;
+      }
+    }
+    for (int x = t; x < width; x += KNN_THREADS) {
+      const unsigned int vb = cnt[x];
+      if (vb != 0u) {
+        const unsigned long long e = ((unsigned long long)vb << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned int)(t0 + x));
+        if (e >= thr) {
+          const unsigned int pos = atomicAdd(&s_cnt, 1u);
+          if (pos < (unsigned int)k) lists[nxt][pos] = e;             // (pos < k always: the guard keeps a wrong count inside the buffer)
+        }
+      }
+    }
+    __syncthreads();
+    n_list = s_cnt < (unsigned int)k ? s_cnt : (unsigned int)k;
+    cur = nxt;
+    __syncthreads();
+  }
+
+  // ---- sort (descending composites; the zero padding sorts last) and write
+  for (int x = (int)n_list + t; x < kpad; x += KNN_THREADS) lists[cur][x] = 0ull;
+  __syncthreads();
+  for (int size = 2; size <= kpad; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (t < kpad) {
+        const int j = t ^ stride;
+        if (j > t) {
+          const bool desc = (t & size) == 0;
+          const unsigned long long a = lists[cur][t], b = lists[cur][j];
+          if ((a < b) == desc) { lists[cur][t] = b; lists[cur][j] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (t < k) {
+    const unsigned long long e = lists[cur][t];
+    const bool real = t < (int)n_list;
+    nbr_idx[(long)i * k + t] = real ? (int)(0xFFFFFFFFu - (unsigned int)(e & 0xFFFFFFFFull)) : -1;
+    nbr_val[(long)i * k + t] = real ? __uint_as_float((unsigned int)(e >> 32)) : 0.f;
+  }
+  if (t == 0) nbr_len[i] = (int)n_list;
+}
+
+extern "C" int sbr_knn_topk(const long* indptr, const int* indices, const long* t_indptr, const int* t_indices, int n, int m, int r0,
+                            int r1, int sim, float alpha, float beta, float shrinkage, int k, int tile_cols, int* nbr_idx,
+                            float* nbr_val, int* nbr_len, void* stream) {
+  SBR_REQUIRE(k >= 1 && k <= KNN_K_MAX, "sbr_knn_topk: k=%d outside [1, %d]", k, KNN_K_MAX);
+  SBR_REQUIRE(sim >= KNN_COSINE && sim <= KNN_TVERSKY, "sbr_knn_topk: unknown similarity code %d", sim);
+  SBR_REQUIRE(shrinkage >= 0.f, "sbr_knn_topk: negative shrinkage %g", (double)shrinkage);
+  SBR_REQUIRE(alpha >= 0.f && beta >= 0.f, "sbr_knn_topk: negative alpha / beta (%g, %g)", (double)alpha, (double)beta);
+  SBR_REQUIRE(n >= 0 && m >= 0 && m <= KNN_M_MAX, "sbr_knn_topk: shape [%d, %d] outside [0, 2^31) x [0, 2^24]", n, m);
+  SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= n, "sbr_knn_topk: row range [%d, %d) outside [0, %d]", r0, r1, n);
+  SBR_REQUIRE(tile_cols >= 0, "sbr_knn_topk: negative tile_cols %d", tile_cols);
+  const long fixed = 2L * KNN_K_MAX * 8 + 256 * 4 + 64;         // the kernel's static LDS: two lists, the histogram, the scalars
+  int tw = tile_cols > 0 ? tile_cols : (n < KNN_TILE_DEFAULT ? (n > 64 ? n : 64) : KNN_TILE_DEFAULT);
+  const long lds = 4L * tw;
+  SBR_REQUIRE(lds + fixed <= KNN_LDS_MAX, "sbr_knn_topk: tile_cols=%d asks for %ld bytes of LDS, over 160 KiB", tw, lds + fixed);
+  if (r1 == r0) return SBR_OK;
+  SBR_REQUIRE(indptr && indices && t_indptr && t_indices && nbr_idx && nbr_val && nbr_len, "sbr_knn_topk: null operand");
+  static int attr_dev = -1;
+  if (sbr_attr_stale(&attr_dev)) {
+    if (hipFuncSetAttribute((const void*)knn_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KNN_LDS_MAX - fixed)) != hipSuccess) {
+      attr_dev = -1;
+      sbr_set_error("sbr_knn_topk: cannot raise the dynamic LDS limit");
+      return SBR_ERR_HIP;
+    }
+  }
+  int kpad = 2;
+  while (kpad < k) kpad <<= 1;
+  knn_topk_kernel<<<(unsigned)(r1 - r0), KNN_THREADS, (size_t)lds, (hipStream_t)stream>>>(indptr, indices, t_indptr, t_indices, n, r0, sim, alpha,
+                                                                                   beta, shrinkage, k, kpad, tw, nbr_idx, nbr_val, nbr_len);
+  SBR_CHECK_LAUNCH("sbr_knn_topk");
+  return SBR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// out[b, c] = sum over the entries p of X's row rows[b], in ascending column of X, of x[p] * Y[col(p), c]      (0 <= c < n_cols)
+// A wave owns (row b, `sub` consecutive columns) with its accumulators in its own slice of LDS; four waves share a workgroup and
+// nothing else. The wave loads 64 entries of X's row at a time (column, value, the bounds of Y's row) and then takes them one after
+// the other: its lanes cover Y's row, whose columns are distinct, so no two lanes meet on an accumulator, and an accumulator sees
+// its terms in the order of X's entries: acc = fmaf(x, y, acc), one rounding per term. Short rows of Y are scanned from their start
+// (two loads cover 128 entries), longer ones are entered at the slice's first column by a lower bound.
+// ---------------------------------------------------------------------------------------------------------------
+#define CXC_WAVES 4
+#define CXC_TILE_DEFAULT 8192        // columns per workgroup: 32 KiB of accumulators, five workgroups (20 waves) per CU
+#define CXC_SCAN_MAX 128
+
+__global__ __launch_bounds__(64 * CXC_WAVES) void csr_rows_times_csr_kernel(const long* __restrict__ x_indptr, const int* __restrict__ x_indices,
+                                                                            const float* __restrict__ x_data, const long* __restrict__ rows,
+                                                                            const long* __restrict__ y_indptr, const int* __restrict__ y_indices,
+                                                                            const float* __restrict__ y_data, int n_cols, int sub,
+                                                                            long b0, float* __restrict__ out, long ld) {
+  extern __shared__ float acc_all[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long c_beg = ((long)blockIdx.x * CXC_WAVES + w) * sub;
+  if (c_beg >= n_cols) return;                              // (no workgroup barrier below: the waves are independent)
+  const int cb = (int)c_beg, width = cb + sub < n_cols ? sub : n_cols - cb;
+  float* acc = acc_all + (long)w * sub;
+  for (int x = lane; x < width; x += 64) acc[x] = 0.f;
+  const long b = b0 + blockIdx.y;
+  const long r = rows ? rows[b] : b;
+  const long p_end = x_indptr[r + 1];
+  for (long p0 = x_indptr[r]; p0 < p_end; p0 += 64) {
+    const int n_e = p_end - p0 < 64 ? (int)(p_end - p0) : 64;
+    int my_beg = 0, my_len = 0;
+    long my_base = 0;
+    float my_x = 0.f;
+    if (lane < n_e) {
+      const int j = x_indices[p0 + lane];
+      my_x = x_data ? x_data[p0 + lane] : 1.f;
+      my_base = y_indptr[j];
+      my_len = (int)(y_indptr[j + 1] - my_base);
+      if (my_len > CXC_SCAN_MAX) {                          // first entry of Y's row with column >= cb
+        int lo = 0, hi = my_len;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (y_indices[my_base + mid] < cb) lo = mid + 1; else hi = mid;
+        }
+        my_beg = lo;
+      }
+    }
+    for (int e = 0; e < n_e; ++e) {
+      const float xv = __shfl(my_x, e, 64);
+      const long base = __shfl(my_base, e, 64);
+      const int len = __shfl(my_len, e, 64);
+      for (int q = __shfl(my_beg, e, 64) + lane; q < len; q += 64) {
+        const unsigned int x = (unsigned int)(y_indices[base + q] - cb);
+        if ((int)x >= width) break;                         // sorted: the rest of Y's row belongs to later slices
+        if (x < (unsigned int)width) acc[x] = fmaf(xv, y_data ? y_data[base + q] : 1.f, acc[x]);
+      }
+      // the next entry may name the same accumulator from another lane: keep the LDS accesses of two entries in program order
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  float* o = out + b * ld + cb;
+  for (int x = lane; x < width; x += 64) o[x] = acc[x];
+}
+
+extern "C" int sbr_csr_rows_times_csr(const long* x_indptr, const int* x_indices, const float* x_data, const long* rows, long B,
+                                      const long* y_indptr, const int* y_indices, const float* y_data, int n_cols, int tile_cols,
+                                      float* out, long ld, void* stream) {
+  SBR_REQUIRE(B >= 0 && B <= 65535L * 65535L && n_cols >= 0 && ld >= n_cols, "sbr_csr_rows_times_csr: bad shape (B=%ld, n_cols=%d, ld=%ld)", B,
+              n_cols, ld);
+  SBR_REQUIRE(tile_cols >= 0, "sbr_csr_rows_times_csr: negative tile_cols %d", tile_cols);
+  if (B == 0 || n_cols == 0) return SBR_OK;
+  SBR_REQUIRE(x_indptr && y_indptr && out, "sbr_csr_rows_times_csr: null operand");
+  int tile = tile_cols > 0 ? tile_cols : (n_cols < CXC_TILE_DEFAULT ? n_cols : CXC_TILE_DEFAULT);
+  const int sub = (int)((tile + CXC_WAVES - 1) / CXC_WAVES);
+  const long lds = 4L * sub * CXC_WAVES;
+  SBR_REQUIRE(lds <= 65536, "sbr_csr_rows_times_csr: tile_cols=%d asks for %ld bytes of LDS, over 64 KiB", tile_cols, lds);
+  const long per_wg = (long)sub * CXC_WAVES;
+  const unsigned gx = (unsigned)((n_cols + per_wg - 1) / per_wg);
+  // the rows go to gridDim.y (<= 65535): longer batches in slabs
+  for (long b0 = 0; b0 < B; b0 += 65535) {
+    const unsigned gy = (unsigned)(B - b0 < 65535 ? B - b0 : 65535);
+    csr_rows_times_csr_kernel<<<dim3(gx, gy), 64 * CXC_WAVES, (size_t)lds, (hipStream_t)stream>>>(
+        x_indptr, x_indices, x_data, rows, y_indptr, y_indices, y_data, n_cols, sub, b0, out, ld);
+    SBR_CHECK_LAUNCH("sbr_csr_rows_times_csr");
+  }
+  return SBR_OK;
+}

@@ -7,6 +7,7 @@ calling any op with CPU tensors raises.
 from __future__ import annotations
 
 import numbers
+from functools import partial
 from typing import List, Optional, Sequence
 
 import torch
@@ -1172,6 +1173,62 @@ def csr_rows_times_dense(csr, rows: torch.Tensor, dense: torch.Tensor) -> torch.
     if dense.dim() != 2 or not dense.is_contiguous():
         raise ValueError('csr_rows_times_dense: the dense operand must be a contiguous matrix [n_cols, C]')
     return SparseLinearActFn.apply(csr, rows, dense.t(), None, 0)
+
+
+# ---- neighbourhood models (csrc/knn.hip) ------------------------------------------------------------------------------------------
+KNN_SIM_CODES = {'cosine': 0, 'jaccard': 1, 'asymmetric_cosine': 2, 'sorensen_dice': 3, 'tversky': 4}
+KNN_MAX_K = 256
+
+
+def knn_topk(csr, sim, k: int, shrinkage: float = 0., alpha=None, beta=None, rows=None, tile_cols: int = 0):
+    """The ``k`` most similar rows of every row of a binary resident ``features.DeviceCSR`` [n, m] (``compute_similarity_top_k``,
+    utilities/similarities.py:18-61, with the similarity of :64-130 named by ``sim``: a key of ``KNN_SIM_CODES`` or its code) ->
+    ``(idx int32 [n, k], val float32 [n, k], len int32 [n])``, every list sorted by (value descending, index ascending), (-1, 0) behind
+    its length. ``rows=(r0, r1)`` computes that row range only (the other rows come back empty); ``tile_cols`` as in the header."""
+    code = KNN_SIM_CODES.get(getattr(sim, 'name', sim), sim)
+    if not isinstance(code, int) or code not in KNN_SIM_CODES.values():
+        raise ValueError(f'knn_topk: unknown similarity {sim!r} (one of {sorted(KNN_SIM_CODES)})')
+    _need_cuda(csr.indptr)
+    if csr.data is not None:
+        raise ValueError('knn_topk: the similarities are stated for 0/1 data only (utilities/similarities.py:11-15); this matrix has values')
+    n, m = csr.shape
+    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    dev = csr.indptr.device
+    whole = (r0, r1) == (0, n)
+    idx = (torch.empty if whole else partial(torch.full, fill_value=-1))((n, k), device=dev, dtype=torch.int32)
+    val = (torch.empty if whole else torch.zeros)((n, k), device=dev, dtype=torch.float32)
+    length = (torch.empty if whole else torch.zeros)((n,), device=dev, dtype=torch.int32)
+    t_indptr, t_indices, _ = csr.transposed()
+    call('sbr_knn_topk', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, code,
+         float(0. if alpha is None else alpha), float(0. if beta is None else beta), float(shrinkage), int(k), int(tile_cols),
+         ptr(idx), ptr(val), ptr(length), stream())
+    return idx, val, length
+
+
+def _csr_parts(x):
+    """(indptr, indices, data or None, shape) of a ``features.DeviceCSR`` or of a plain tuple of that form"""
+    if isinstance(x, (tuple, list)):
+        return x
+    return x.indptr, x.indices, x.data, tuple(x.shape)
+
+
+def csr_rows_times_csr(x, rows: Optional[torch.Tensor], y, tile_cols: int = 0) -> torch.Tensor:
+    """``X[rows] @ Y`` as dense float32 rows [len(rows), Y.shape[1]] with both operands sparse and resident: ``features.DeviceCSR``s or
+    ``(indptr int64, indices int32 sorted, data float32 | None = ones, shape)`` tuples — ``matrix @ sim_mtx.T`` and ``sim_mtx @ matrix``
+    (algorithms/knn_algs.py:116, :96). ``rows=None``: every row. Fixed summation order (ascending column of X): the same bits on
+    every run."""
+    xp, xi, xd, xs = _csr_parts(x)
+    yp, yi, yd, ys = _csr_parts(y)
+    if xs[1] != ys[0]:
+        raise ValueError(f'csr_rows_times_csr: shapes {tuple(xs)} and {tuple(ys)} do not chain')
+    _need_cuda(xp, yp, rows)
+    if rows is not None:
+        rows = rows.long().contiguous()
+    B = xs[0] if rows is None else rows.numel()
+    out = torch.empty(B, ys[1], device=xp.device, dtype=torch.float32)
+    call('sbr_csr_rows_times_csr', ptr(xp), ptr(xi), ptr(xd), ptr(rows), B, ptr(yp), ptr(yi), ptr(yd), int(ys[1]), int(tile_cols), ptr(out),
+         out.stride(0) if B else ys[1], stream())
+    return out
 
 
 class BiasScoreFn(Function):
