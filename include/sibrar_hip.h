@@ -276,7 +276,7 @@ int sbr_score_cos_bwd(const float* G, const float* U, const float* I, const floa
  * (row stride ld), in place: x[x < mu] = mu, NaN left alone. Applied before the exclusion mask (eval/eval.py:219-220). */
 int sbr_floor_scores(float* scores, long n, long n_cols, long ld, float mu, void* stream);
 /* ProtoMF's similarity to the prototypes — algorithms/sgd_alg.py:48-59 (compute_shifted_cosine_sim) behind the lookups of
- * sgd_alg.py:381-382, 486-488, with the regularisers of sgd_alg.py:394-399, 505-510 (additive to ABI 4; csrc/proto_sim.hip):
+ * sgd_alg.py:381-382, 486-488, with the regularisers of sgd_alg.py:394-399, 505-510 (additive to ABI 4; csrc/proto_cos.hip):
  *   e = W[rows[j], :] (rows NULL: row j; the gather is fused)      sim_out[j, p] = clamp(1 + e^ . p^, 0, 2),  x^ = x / max(|x|, 1e-12)
  *   *proto_loss = mean_p min_j (2 - sim)      *batch_loss = mean_j min_p (2 - sim)      (device scalars, no host sync)
  * 1 <= D <= 512, 2 <= n_proto <= 256 (anything else fails through sbr_last_error), R = 0 returns SBR_OK. Saved for the backward pass:
@@ -301,7 +301,7 @@ int sbr_proto_sim_bwd(const float* G, const float* g_proto, const float* g_batch
                       void* stream);
 /* The simplified ProtoMF family's prototype side — algorithms/sgd_alg.py:62-73 (compute_cosine_sim) behind the lookups of
  * sgd_alg.py:677-678, 742-744, with the ReLU of sgd_alg.py:683, 739, 808, 814 on the other entity's weights and the dot over the
- * prototypes of sgd_alg.py:687, 750, 823-824 (additive to ABI 4; csrc/proto_score.hip). Two forms of one op, selected by Wt:
+ * prototypes of sgd_alg.py:687, 750, 823-824 (additive to ABI 4; csrc/proto_cos.hip). Two forms of one op, selected by Wt:
  *   e = W[rows[j], :] (rows NULL: row j; the gather is fused)      cos[j, p] = clamp(e^ . P^_p, -1, 1),  x^ = x / max(|x|, 1e-12)
  *   cosine form (Wt NULL; out, widx NULL; fan ignored but >= 1): cos_out [R, P] is written
  *   score form: every row j carries fan >= 1 weight rows w[j, f, :] = Wt[widx[j fan + f], :] (widx NULL: row j fan + f; row stride

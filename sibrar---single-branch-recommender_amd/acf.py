@@ -19,25 +19,13 @@ import torch
 from torch import nn
 
 from . import ops
-from .protomf import MAX_ENTITIES, PrototypeWrapper
+from .protomf import PrototypeWrapper, prototype_stats
 
 
 def acf_post_val_light(anchors: torch.Tensor, entity_embeddings: torch.Tensor) -> Dict[str, float]:
-    """explanations/utils.py:223-257 with sim_func = compute_cosine_sim (sgd_alg.py:62-73, 322-329): the plain cosine clamped to
-    [-1, 1], from the two blocks of the similarity matrix it reads — anchors x anchors and entities x anchors. The cosine is the
-    un-clamped one ``sbr_proto_sim_fwd`` writes next to ProtoMF's shifted similarity. From MAX_ENTITIES entities upward a random subset
-    is used, as in the reference."""
-    n_anchors = len(anchors)
-    with torch.no_grad():
-        idx = None
-        if len(entity_embeddings) >= MAX_ENTITIES:
-            idx = torch.randperm(len(entity_embeddings))[:MAX_ENTITIES].to(entity_embeddings.device)
-        sim_mtx_proto = ops.cosine_sim(anchors, None, anchors)
-        entity_to_proto = ops.cosine_sim(entity_embeddings, idx, anchors)
-        sim_mtx_proto_tril = torch.tril(sim_mtx_proto, diagonal=-1)
-        stats = torch.stack([(sim_mtx_proto_tril.sum() * 2) / (n_anchors * (n_anchors - 1)), entity_to_proto.mean(dim=-1).mean(),
-                             entity_to_proto.max(dim=-1).values.mean(), entity_to_proto.min(dim=-1).values.mean()]).tolist()
-    return dict(zip(('avg_pairwise_proto_sim', 'entity_to_proto_mean', 'entity_to_proto_max', 'entity_to_proto_min'), stats))
+    """``prototype_stats`` with sim_func = compute_cosine_sim (sgd_alg.py:62-73, 322-329) on the anchors: the plain cosine clamped to
+    [-1, 1], the un-clamped one ``sbr_proto_sim_fwd`` writes next to ProtoMF's shifted similarity."""
+    return prototype_stats(ops.cosine_sim, anchors, entity_embeddings)
 
 
 class ACF(PrototypeWrapper):
@@ -81,8 +69,7 @@ class ACF(PrototypeWrapper):
 
     def combine_user_item_representations(self, u_repr, i_repr):
         # i_anc [B, N, D] in training, [I, D] in evaluation (eval/eval.py:209-217)
-        i_anc = i_repr[0]
-        return (ops.ScoreAllFn if i_anc.ndim == 2 else ops.ScoreDotFn).apply(u_repr, i_anc)
+        return ops.score(u_repr, i_repr[0])
 
     def fused_score_transform(self):
         """The score is the plain dot product of ``u_anc`` and ``i_anc``: the fused scorers take the first entry of the item tuple."""

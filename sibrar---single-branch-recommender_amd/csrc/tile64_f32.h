@@ -1,4 +1,4 @@
-// The 64 x 64 fp32 tile skeleton that csrc/proto_sim.hip, csrc/anchor_mix.hip and csrc/cluster_affil.hip are built on: a workgroup of 256
+// The 64 x 64 fp32 tile skeleton that csrc/proto_cos.hip, csrc/anchor_mix.hip and csrc/cluster_affil.hip are built on: a workgroup of 256
 // threads owns a tile of 64 rows, a thread a 4 x 4 block of every 64-wide output tile, K-chunks of 32 are staged K-major in LDS, sums
 // that cross workgroups are per-workgroup partials folded in workgroup order. DESIGN.md ("The 64 x 64 fp32 tile skeleton") has the
 // work-item map, the LDS layout and the determinism rule; what is here is the code, once. Everything is inlined into the including
@@ -81,7 +81,7 @@ __device__ __forceinline__ float t64_row_max(float v) {
   return v;
 }
 // sum over the 32 lanes sk of a half wave (the pieces of a row that the transposed staging leaves in its 32 lanes). DOWN: xor offsets
-// 16, 8, 4, 2, 1 (proto_sim); otherwise 1, 2, 4, 8, 16 (cluster_affil). The two associate differently and each kernel keeps its own.
+// 16, 8, 4, 2, 1 (proto_cos); otherwise 1, 2, 4, 8, 16 (cluster_affil). The two associate differently and each kernel keeps its own.
 template <bool DOWN>
 __device__ __forceinline__ float t64_half_sum(float v) {
   if (DOWN) {

@@ -85,7 +85,7 @@ class DropoutNet(SGDBasedRecommenderAlgorithm):
         return self.item_net(i_idxs, self._preferences(i_idxs, self._item_rows, strategy))
 
     def combine_user_item_representations(self, u_repr, i_repr):
-        return (ops.ScoreAllFn if i_repr.ndim == 2 else ops.ScoreDotFn).apply(u_repr, i_repr)
+        return ops.score(u_repr, i_repr)
 
     @staticmethod
     def build_from_conf(conf: dict, dataset):

@@ -108,9 +108,7 @@ class ECF(PrototypeWrapper):
         return a_i, u_embed
 
     def combine_user_item_representations(self, u_repr, i_repr):
-        # x_i [B, N, C] in training, [I, C] in evaluation (eval/eval.py:209-217)
-        a_i, x_i = u_repr[0], i_repr[0]
-        return (ops.ScoreAllFn if x_i.ndim == 2 else ops.ScoreDotFn).apply(a_i, x_i)
+        return ops.score(u_repr[0], i_repr[0])                  # a_i . x_i
 
     def forward(self, u_idxs, i_idxs):
         i_repr = self.get_item_representations(i_idxs)

@@ -804,8 +804,25 @@ def _tile_ws(entry, device, R, D, N, backward, min_bytes=8):
     return torch.empty(max(n, min_bytes), device=device, dtype=torch.uint8)
 
 
+def _tile_view(out, idx):
+    """out [R, n] as [*idx.shape, n] (``idx`` None: the rows are the table's)"""
+    return out if idx is None else out.view(*idx.shape, out.shape[1])
+
+
+def _tile_grads(entry, device, R, D, N, need_t, need_n):
+    """the outputs of a backward entry point, each where needed: dE [R, D], the [N, D] gradient of the matrix, and ``entry``'s backward
+    workspace (the matrix gradient's). -> (dE, dN, ws, ws bytes)"""
+    dE = torch.empty(R, D, device=device, dtype=torch.float32) if need_t else None
+    dN = torch.empty(N, D, device=device, dtype=torch.float32) if need_n else None
+    ws = _tile_ws(entry, device, R, D, N, True) if need_n and R > 0 else None
+    return dE, dN, ws, 0 if ws is None else ws.numel()
+
+
 def _table_grad(table, rows, dE):
-    """the dense table gradient from dE [R, D] = d / d table[rows] (``rows`` None: the rows are the table), as ``LookupFn`` returns it"""
+    """the dense table gradient from dE [R, D] = d / d table[rows] (``rows`` None: the rows are the table), as ``LookupFn`` returns it;
+    None where dE is None (the table needs no gradient)"""
+    if dE is None:
+        return None
     d_table = torch.zeros(table.shape, device=dE.device, dtype=torch.float32)
     if rows is None:
         d_table.copy_(dE)
@@ -816,11 +833,22 @@ def _table_grad(table, rows, dE):
 
 
 # ---- ProtoMF: shifted cosine similarity to the prototypes -----------------------------------------------------------------------------
-PROTO_MAX_D, PROTO_MAX_P = 512, 256          # csrc/proto_sim.hip
+PROTO_MAX_D, PROTO_MAX_P = 512, 256          # csrc/proto_cos.hip
 
 
 def _proto_operands(table, idx, prototypes, who):
     return _tile_operands(table, idx, prototypes, who, 'prototypes', 'n_prototypes', PROTO_MAX_D, PROTO_MAX_P)
+
+
+def _proto_sim_fwd(table, rows, protos, R, D, P, cos=None, saved=(None,) * 7):
+    """``sbr_proto_sim_fwd`` -> sim [R, P]. ``cos``: where the un-clamped cosine goes; ``saved``: row_stat, proto_stat, row_best, col_val,
+    col_row, proto_loss, batch_loss of the training form"""
+    sim = torch.empty(R, P, device=table.device, dtype=torch.float32)
+    ws = _tile_ws('sbr_proto_sim_workspace', table.device, R, D, P, False)
+    _timed(('proto_sim_fwd', R, D, P),
+           lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(sim), ptr(cos),
+                        *map(ptr, saved), ptr(ws), ws.numel(), stream()))
+    return sim
 
 
 class ProtoSimFn(Function):
@@ -835,19 +863,14 @@ class ProtoSimFn(Function):
         table, rows, protos, R, D, P = _proto_operands(table, idx, prototypes, 'ProtoSimFn')
         dev = table.device
         f32 = dict(device=dev, dtype=torch.float32)
-        sim, cos = torch.empty(R, P, **f32), torch.empty(R, P, **f32)
+        cos = torch.empty(R, P, **f32)
         row_stat, proto_stat = torch.empty(R, 2, **f32), torch.empty(P, 2, **f32)
         row_best = torch.empty(R, device=dev, dtype=torch.int32)
         col_val, col_row = torch.empty(P, **f32), torch.empty(P, device=dev, dtype=torch.int32)
         proto_loss, batch_loss = torch.zeros((), **f32), torch.zeros((), **f32)
-        ws = _tile_ws('sbr_proto_sim_workspace', dev, R, D, P, False)
-        _timed(('proto_sim_fwd', R, D, P),
-               lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(sim), ptr(cos),
-                            ptr(row_stat), ptr(proto_stat), ptr(row_best), ptr(col_val), ptr(col_row), ptr(proto_loss), ptr(batch_loss),
-                            ptr(ws), ws.numel(), stream()))
+        sim = _proto_sim_fwd(table, rows, protos, R, D, P, cos, (row_stat, proto_stat, row_best, col_val, col_row, proto_loss, batch_loss))
         ctx.save_for_backward(table, rows, protos, cos, row_stat, proto_stat, row_best, col_row)
-        shape = (R,) if idx is None else tuple(idx.shape)
-        return sim.view(*shape, P), proto_loss, batch_loss
+        return _tile_view(sim, idx), proto_loss, batch_loss
 
     @staticmethod
     def backward(ctx, g_sim, g_proto, g_batch):
@@ -855,47 +878,35 @@ class ProtoSimFn(Function):
         (R, P), D = cos.shape, table.shape[1]
         g_sim = _f32c(g_sim).reshape(R, P)
         g_proto, g_batch = (None if g is None else g.reshape(1).float().contiguous() for g in (g_proto, g_batch))
-        need_t, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
-        dE = torch.empty(R, D, device=cos.device, dtype=torch.float32) if need_t else None
-        dP = torch.empty(P, D, device=cos.device, dtype=torch.float32) if need_p else None
-        ws = _tile_ws('sbr_proto_sim_workspace', cos.device, R, D, P, True) if need_p and R > 0 else None
+        dE, dP, ws, ws_bytes = _tile_grads('sbr_proto_sim_workspace', cos.device, R, D, P, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
         _timed(('proto_sim_bwd', R, D, P),
                lambda: call('sbr_proto_sim_bwd', ptr(g_sim), ptr(g_proto), ptr(g_batch), ptr(table), table.stride(0), ptr(rows), R, D,
                             ptr(protos), P, ptr(cos), ptr(row_stat), ptr(proto_stat), ptr(row_best), ptr(col_row), ptr(dE), ptr(dP),
-                            ptr(ws), 0 if ws is None else ws.numel(), stream()))
-        return _table_grad(table, rows, dE) if need_t else None, None, dP
+                            ptr(ws), ws_bytes, stream()))
+        return _table_grad(table, rows, dE), None, dP
 
 
 def proto_sim(table: torch.Tensor, idx: Optional[torch.Tensor], prototypes: torch.Tensor) -> torch.Tensor:
     """The evaluation form of ``ProtoSimFn`` (no autograd, no arg-mins): clamp(1 + cos(table[idx], prototypes), 0, 2) as
     [*idx.shape, P]; ``idx`` None: every row of ``table``."""
     table, rows, protos, R, D, P = _proto_operands(table.detach(), idx, prototypes.detach(), 'proto_sim')
-    sim = torch.empty(R, P, device=table.device, dtype=torch.float32)
-    ws = _tile_ws('sbr_proto_sim_workspace', table.device, R, D, P, False)
-    _timed(('proto_sim_fwd', R, D, P),
-           lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(sim), None, None, None,
-                        None, None, None, None, None, ptr(ws), ws.numel(), stream()))
-    return sim.view(*((R,) if idx is None else tuple(idx.shape)), P)
+    return _tile_view(_proto_sim_fwd(table, rows, protos, R, D, P), idx)
 
 
 def cosine_sim(table: torch.Tensor, idx: Optional[torch.Tensor], others: torch.Tensor) -> torch.Tensor:
     """sgd_alg.py:62-73 (compute_cosine_sim): clamp(cos(table[idx], others), -1, 1) as [*idx.shape, P] — the un-clamped cosine that
     ``sbr_proto_sim_fwd`` writes next to the shifted similarity, clamped in place. No autograd (ACF's post_val statistics)."""
     table, rows, others, R, D, P = _proto_operands(table.detach(), idx, others.detach(), 'cosine_sim')
-    sim = torch.empty(R, P, device=table.device, dtype=torch.float32)
     cos = torch.empty(R, P, device=table.device, dtype=torch.float32)
-    ws = _tile_ws('sbr_proto_sim_workspace', table.device, R, D, P, False)
-    _timed(('proto_sim_fwd', R, D, P),
-           lambda: call('sbr_proto_sim_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(others), P, ptr(sim), ptr(cos), None, None,
-                        None, None, None, None, None, ptr(ws), ws.numel(), stream()))
-    return cos.clamp_(min=-1., max=1.).view(*((R,) if idx is None else tuple(idx.shape)), P)
+    _proto_sim_fwd(table, rows, others, R, D, P, cos)
+    return _tile_view(cos.clamp_(min=-1., max=1.), idx)
 
 
 # ---- ProtoMFs: plain cosine similarity to the prototypes, and its dot with the relu'd weights of the other entity -------------------------
 class ProtoCosFn(Function):
     """sgd_alg.py:62-73 (compute_cosine_sim) on ``table[idx]`` against ``prototypes`` (sgd_alg.py:677-678, 742-746), differentiable:
     ``-> clamp(cos, -1, 1) [*idx.shape, P]`` (``idx`` None: every row of ``table``). The lookup is fused; the backward pass returns the
-    dense table gradient, as ``LookupFn`` does, and the prototype gradient. One fixed-order form (csrc/proto_score.hip)."""
+    dense table gradient, as ``LookupFn`` does, and the prototype gradient. One fixed-order form (csrc/proto_cos.hip)."""
 
     @staticmethod
     def forward(ctx, table, idx, prototypes):
@@ -908,22 +919,18 @@ class ProtoCosFn(Function):
                lambda: call('sbr_proto_score_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, None, 0, None, 1, ptr(cos),
                             None, ptr(raw), ptr(row_stat), ptr(proto_stat), ptr(ws), ws.numel(), stream()))
         ctx.save_for_backward(table, rows, protos, raw, row_stat, proto_stat)
-        return cos.view(*((R,) if idx is None else tuple(idx.shape)), P)
+        return _tile_view(cos, idx)
 
     @staticmethod
     def backward(ctx, g):
         table, rows, protos, raw, row_stat, proto_stat = ctx.saved_tensors
         (R, P), D = raw.shape, table.shape[1]
         g = _f32c(g).reshape(R, P)
-        need_t, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
-        dE = torch.empty(R, D, device=raw.device, dtype=torch.float32) if need_t else None
-        dP = torch.empty(P, D, device=raw.device, dtype=torch.float32) if need_p else None
-        ws = _tile_ws('sbr_proto_score_workspace', raw.device, R, D, P, True) if need_p and R > 0 else None
+        dE, dP, ws, ws_bytes = _tile_grads('sbr_proto_score_workspace', raw.device, R, D, P, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
         _timed(('proto_score_bwd', R, D, P, 0),
                lambda: call('sbr_proto_score_bwd', ptr(g), ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, None, 0, None, 1,
-                            ptr(raw), ptr(row_stat), ptr(proto_stat), ptr(dE), ptr(dP), None, ptr(ws), 0 if ws is None else ws.numel(),
-                            stream()))
-        return _table_grad(table, rows, dE) if need_t else None, None, dP
+                            ptr(raw), ptr(row_stat), ptr(proto_stat), ptr(dE), ptr(dP), None, ptr(ws), ws_bytes, stream()))
+        return _table_grad(table, rows, dE), None, dP
 
 
 class ProtoScoreFn(Function):
@@ -932,7 +939,7 @@ class ProtoScoreFn(Function):
     idx.numel(). ``widx`` None: ``weights`` holds the R * fan weight rows themselves, in order. Neither the cosines' lookup nor the
     relu'd weight gather is written. The backward pass returns the dense table gradient, the prototype gradient and the weight
     gradient: dense (scattered over ``widx``) when ``widx`` is given, the row gradient itself when it is None; zero where
-    ``weights <= 0``, as torch's ReLU. One fixed-order form (csrc/proto_score.hip)."""
+    ``weights <= 0``, as torch's ReLU. One fixed-order form (csrc/proto_cos.hip)."""
 
     @staticmethod
     def forward(ctx, table, idx, prototypes, weights, widx, fan):
@@ -965,19 +972,15 @@ class ProtoScoreFn(Function):
         table, rows, protos, wt, wrows, raw, row_stat, proto_stat = ctx.saved_tensors
         (R, P), D, fan = raw.shape, table.shape[1], ctx.fan
         g = _f32c(g).reshape(R, fan)
-        need_t, need_p, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        f32 = dict(device=raw.device, dtype=torch.float32)
-        dE = torch.empty(R, D, **f32) if need_t else None
-        dP = torch.empty(P, D, **f32) if need_p else None
-        dW = torch.empty(R * fan, P, **f32) if need_w else None
-        ws = _tile_ws('sbr_proto_score_workspace', raw.device, R, D, P, True) if need_p and R > 0 else None
+        dE, dP, ws, ws_bytes = _tile_grads('sbr_proto_score_workspace', raw.device, R, D, P, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        dW = torch.empty(R * fan, P, device=raw.device, dtype=torch.float32) if ctx.needs_input_grad[3] else None
         _timed(('proto_score_bwd', R, D, P, fan),
                lambda: call('sbr_proto_score_bwd', ptr(g), ptr(table), table.stride(0), ptr(rows), R, D, ptr(protos), P, ptr(wt),
                             wt.stride(0), ptr(wrows), fan, ptr(raw), ptr(row_stat), ptr(proto_stat), ptr(dE), ptr(dP), ptr(dW), ptr(ws),
-                            0 if ws is None else ws.numel(), stream()))
-        if need_w and wrows is not None:
+                            ws_bytes, stream()))
+        if wrows is not None:
             dW = _table_grad(wt, wrows, dW)
-        return _table_grad(table, rows, dE) if need_t else None, None, dP, dW, None, None
+        return _table_grad(table, rows, dE), None, dP, dW, None, None
 
 
 # ---- ACF: softmax mixing of the anchors ------------------------------------------------------------------------------------------------
@@ -1016,10 +1019,9 @@ class AnchorMixFn(Function):
                                 0 if ws is None else ws.numel(), stream()))
         ctx.save_for_backward(table, rows, anc, c, lse, dinc)
         ctx.with_losses = q is not None
-        shape = (R,) if idx is None else tuple(idx.shape)
-        c_out = c.view(*shape, K)
+        c_out = _tile_view(c, idx)
         ctx.mark_non_differentiable(c_out)
-        return r.view(*shape, D), c_out, exc, inc
+        return _tile_view(r, idx), c_out, exc, inc
 
     @staticmethod
     def backward(ctx, g_r, _g_c, g_exc, g_inc):
@@ -1029,14 +1031,11 @@ class AnchorMixFn(Function):
         if not ctx.with_losses:
             g_exc = g_inc = None
         g_exc, g_inc = (None if g is None else g.reshape(1).float().contiguous() for g in (g_exc, g_inc))
-        need_t, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
-        dE = torch.empty(R, D, device=c.device, dtype=torch.float32) if need_t else None
-        dA = torch.empty(K, D, device=c.device, dtype=torch.float32) if need_a else None
-        ws = _tile_ws('sbr_anchor_mix_workspace', c.device, R, D, K, True) if need_a and R > 0 else None
+        dE, dA, ws, ws_bytes = _tile_grads('sbr_anchor_mix_workspace', c.device, R, D, K, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
         _timed(('anchor_mix_bwd', R, D, K),
                lambda: call('sbr_anchor_mix_bwd', ptr(g_r), ptr(g_exc), ptr(g_inc), ptr(table), table.stride(0), ptr(rows), R, D, ptr(anc),
-                            K, ptr(c), ptr(lse), ptr(dinc), ptr(dE), ptr(dA), ptr(ws), 0 if ws is None else ws.numel(), stream()))
-        return _table_grad(table, rows, dE) if need_t else None, None, dA, None
+                            K, ptr(c), ptr(lse), ptr(dinc), ptr(dE), ptr(dA), ptr(ws), ws_bytes, stream()))
+        return _table_grad(table, rows, dE), None, dA, None
 
 
 def anchor_mix(table: torch.Tensor, idx: Optional[torch.Tensor], anchors: torch.Tensor, want: str = 'r') -> torch.Tensor:
@@ -1051,7 +1050,7 @@ def anchor_mix(table: torch.Tensor, idx: Optional[torch.Tensor], anchors: torch.
         _timed(('anchor_mix_fwd', R, D, K),
                lambda: call('sbr_anchor_mix_fwd', ptr(table), table.stride(0), ptr(rows), R, D, ptr(anc), K, ptr(out) if want == 'r' else None,
                             ptr(out) if want == 'c' else None, None, None, None, None, None, None, 0, stream()))
-    return out.view(*((R,) if idx is None else tuple(idx.shape)), n)
+    return _tile_view(out, idx)
 
 
 # ---- ECF: sparse affiliation of a row to its clusters ----------------------------------------------------------------------------------
@@ -1278,6 +1277,12 @@ class ScoreAllFn(Function):
         du = matmul_nn(g, i) if ctx.needs_input_grad[0] else None
         di = matmul_tn(g, u) if ctx.needs_input_grad[1] else None
         return du, di
+
+
+def score(u_repr: torch.Tensor, i_repr: torch.Tensor) -> torch.Tensor:
+    """The dot-product score of every model: the item side is [B, N, E] in training (``ScoreDotFn``: one dot per slot) and a matrix
+    [I, E] in evaluation (``ScoreAllFn``: all pairs, eval/eval.py:209-217)."""
+    return (ScoreAllFn if i_repr.ndim == 2 else ScoreDotFn).apply(u_repr, i_repr)
 
 
 # ---- losses -------------------------------------------------------------------------------------------------------------------

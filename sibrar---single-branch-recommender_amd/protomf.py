@@ -2,7 +2,7 @@
 ``iprotomf``, ``uiprotomf``; sibling models of SingleBranchNet behind the same plugin surface (algorithms/base_classes.py:173-188:
 PrototypeWrapper). An entity is represented by its shifted cosine similarities to a small set of learned prototypes.
 
-The prototype side of a forward pass is ONE op, ``ops.ProtoSimFn`` (csrc/proto_sim.hip): embedding lookup, both normalisations, the
+The prototype side of a forward pass is ONE op, ``ops.ProtoSimFn`` (csrc/proto_cos.hip): embedding lookup, both normalisations, the
 similarity matrix, the clamp and the two arg-min regularisers of ``compute_reg_losses``; the other side is a plain ``ops.LookupFn``, the
 per-slot dot ``ops.ScoreDotFn`` and the all-pairs evaluation form ``ops.ScoreAllFn``. UIProtoMF's projections are GEMMs on gathered rows
 (``ops.GatherLinearFn``). state_dict keys, their order, constructor arguments, configuration keys and loss-dictionary keys are the
@@ -10,7 +10,7 @@ reference's. The regulariser values stay on the device: ``get_and_reset_other_lo
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 from torch import nn
@@ -37,21 +37,33 @@ class PrototypeWrapper(SGDBasedRecommenderAlgorithm):
         raise NotImplementedError('This method has not been implemented for this class!')
 
 
-def protomf_post_val_light(prototypes: torch.Tensor, entity_embeddings: torch.Tensor) -> Dict[str, float]:
-    """explanations/utils.py:223-257 with the shifted similarity (sgd_alg.py:424-431, 528-535), from the two blocks of the similarity
-    matrix it reads — prototypes x prototypes and entities x prototypes — through ``ops.proto_sim``; the (P + n)^2 matrix of the
-    reference is never built. From MAX_ENTITIES entities upward a random subset is used, as in the reference."""
+def prototype_stats(sim, prototypes: torch.Tensor, entity_embeddings: torch.Tensor,
+                    other_weights: Optional[torch.Tensor] = None) -> Dict[str, float]:
+    """explanations/utils.py:223-257 (and the scalar entries of 260-300) for the similarity ``sim(table, idx, prototypes)``
+    (``ops.proto_sim``, ``ops.cosine_sim``, ``ops.ProtoCosFn.apply``), from the two blocks of the similarity matrix they read — prototypes
+    x prototypes and entities x prototypes; the (P + n)^2 matrix of the reference is never built. ``other_weights`` (ProtoMFs: the relu'd
+    weights of the other entity) adds the means of the non-zero count and of the sum of its rows. From MAX_ENTITIES entities upward a
+    random subset is used, as in the reference."""
     n_prototypes = len(prototypes)
+    names = ['avg_pairwise_proto_sim', 'entity_to_proto_mean', 'entity_to_proto_max', 'entity_to_proto_min']
     with torch.no_grad():
         idx = None
         if len(entity_embeddings) >= MAX_ENTITIES:
             idx = torch.randperm(len(entity_embeddings))[:MAX_ENTITIES].to(entity_embeddings.device)
-        sim_mtx_proto = ops.proto_sim(prototypes, None, prototypes)
-        entity_to_proto = ops.proto_sim(entity_embeddings, idx, prototypes)
+        sim_mtx_proto = sim(prototypes, None, prototypes)
+        entity_to_proto = sim(entity_embeddings, idx, prototypes)
         sim_mtx_proto_tril = torch.tril(sim_mtx_proto, diagonal=-1)
-        stats = torch.stack([(sim_mtx_proto_tril.sum() * 2) / (n_prototypes * (n_prototypes - 1)), entity_to_proto.mean(dim=-1).mean(),
-                             entity_to_proto.max(dim=-1).values.mean(), entity_to_proto.min(dim=-1).values.mean()]).tolist()
-    return dict(zip(('avg_pairwise_proto_sim', 'entity_to_proto_mean', 'entity_to_proto_max', 'entity_to_proto_min'), stats))
+        stats = [(sim_mtx_proto_tril.sum() * 2) / (n_prototypes * (n_prototypes - 1)), entity_to_proto.mean(dim=-1).mean(),
+                 entity_to_proto.max(dim=-1).values.mean(), entity_to_proto.min(dim=-1).values.mean()]
+        if other_weights is not None:
+            names += ['bin_weights_mean', 'sum_weights_mean']
+            stats += [(other_weights != 0).sum(dim=-1).float().mean(), other_weights.sum(dim=-1).mean()]
+        return dict(zip(names, torch.stack(stats).tolist()))
+
+
+def protomf_post_val_light(prototypes: torch.Tensor, entity_embeddings: torch.Tensor) -> Dict[str, float]:
+    """``prototype_stats`` with the shifted similarity (sgd_alg.py:424-431, 528-535)."""
+    return prototype_stats(ops.proto_sim, prototypes, entity_embeddings)
 
 
 class _ProtoSide(PrototypeWrapper):
@@ -98,8 +110,7 @@ class _ProtoSide(PrototypeWrapper):
         return {'reg_loss': proto_loss + batch_loss, 'proto_loss': proto_loss, 'batch_loss': batch_loss}
 
     def combine_user_item_representations(self, u_repr, i_repr):
-        # i_repr [B, N, P] in training, [I, P] in evaluation (eval/eval.py:209-217)
-        return (ops.ScoreAllFn if i_repr.ndim == 2 else ops.ScoreDotFn).apply(u_repr, i_repr)
+        return ops.score(u_repr, i_repr)
 
 
 class UProtoMF(_ProtoSide):
@@ -217,9 +228,7 @@ class UIProtoMF(PrototypeWrapper):
         # u_sim . i_proj + u_proj . i_sim (sgd_alg.py:590-592) as ONE product over the concatenated widths
         u_sim_mtx, u_proj = u_repr
         i_sim_mtx, i_proj = i_repr
-        u_cat = torch.cat([u_sim_mtx, u_proj], dim=-1)
-        i_cat = torch.cat([i_proj, i_sim_mtx], dim=-1)
-        return (ops.ScoreAllFn if i_cat.ndim == 2 else ops.ScoreDotFn).apply(u_cat, i_cat)
+        return ops.score(torch.cat([u_sim_mtx, u_proj], dim=-1), torch.cat([i_proj, i_sim_mtx], dim=-1))
 
     def get_item_representations_pre_tune(self, i_idxs):
         return self.get_item_representations(i_idxs)

@@ -3,7 +3,7 @@
 with the plain cosine ``clamp(x^ . y^, -1, 1)`` (compute_cosine_sim, sgd_alg.py:62-73) instead of the shifted one, and with a ReLU on the
 other entity's weights.
 
-A training forward pass is ONE op per prototype side, ``ops.ProtoScoreFn`` (csrc/proto_score.hip): embedding lookup, both
+A training forward pass is ONE op per prototype side, ``ops.ProtoScoreFn`` (csrc/proto_cos.hip): embedding lookup, both
 normalisations, the cosine, the clamp, the gather of the other entity's weights, their ReLU and the dot over the prototypes; neither the
 similarity matrix's inputs nor the ``[B, N + 1, P]`` weight gather is written. ``get_user_representations`` /
 ``get_item_representations`` / ``combine_user_item_representations`` are the composed route (``ops.ProtoCosFn``, ``ops.LookupFn`` +
@@ -18,33 +18,14 @@ import torch
 from torch import nn
 
 from . import ops
-from .protomf import MAX_ENTITIES
+from .protomf import prototype_stats
 from .sbnet import SGDBasedRecommenderAlgorithm, general_weight_init
 
 
 def protomfs_post_val(prototypes: torch.Tensor, entity_embeddings: torch.Tensor, other_weights: torch.Tensor) -> Dict[str, float]:
-    """The scalar entries of explanations/utils.py:260-300: the four similarity statistics of protomf_post_val_light with the plain
-    cosine, from the two blocks of the similarity matrix they read (``ops.ProtoCosFn``; the (P + n)^2 matrix is never built), and the
-    means of the non-zero count and of the sum of a row of ``other_weights`` (the relu'd weights of the other entity). The images and
-    the t-SNE are left out. From MAX_ENTITIES entities upward a random subset is used, as in the reference."""
-    n_prototypes = len(prototypes)
-    with torch.no_grad():
-        idx = None
-        if len(entity_embeddings) >= MAX_ENTITIES:
-            idx = torch.randperm(len(entity_embeddings))[:MAX_ENTITIES].to(entity_embeddings.device)
-        sim_mtx_proto = ops.ProtoCosFn.apply(prototypes, None, prototypes)
-        entity_to_proto = ops.ProtoCosFn.apply(entity_embeddings, idx, prototypes)
-        sim_mtx_proto_tril = torch.tril(sim_mtx_proto, diagonal=-1)
-        stats = torch.stack([(sim_mtx_proto_tril.sum() * 2) / (n_prototypes * (n_prototypes - 1)), entity_to_proto.mean(dim=-1).mean(),
-                             entity_to_proto.max(dim=-1).values.mean(), entity_to_proto.min(dim=-1).values.mean(),
-                             (other_weights != 0).sum(dim=-1).float().mean(), other_weights.sum(dim=-1).mean()]).tolist()
-    return dict(zip(('avg_pairwise_proto_sim', 'entity_to_proto_mean', 'entity_to_proto_max', 'entity_to_proto_min', 'bin_weights_mean',
-                     'sum_weights_mean'), stats))
-
-
-def _score(u_repr, i_repr):
-    # i_repr [B, N, P] in training, [I, P] in evaluation (eval/eval.py:209-217)
-    return (ops.ScoreAllFn if i_repr.ndim == 2 else ops.ScoreDotFn).apply(u_repr, i_repr)
+    """The scalar entries of explanations/utils.py:260-300: ``prototype_stats`` with the plain cosine and ``other_weights``, the relu'd
+    weights of the other entity. The images and the t-SNE are left out."""
+    return prototype_stats(ops.ProtoCosFn.apply, prototypes, entity_embeddings, other_weights)
 
 
 class _ProtoSideS(SGDBasedRecommenderAlgorithm):
@@ -62,7 +43,7 @@ class _ProtoSideS(SGDBasedRecommenderAlgorithm):
         torch.nn.init.trunc_normal_(weight_side.weight, mean=0.5, std=.1 / self.embedding_dim, a=0, b=1)
 
     def combine_user_item_representations(self, u_repr, i_repr):
-        return _score(u_repr, i_repr)
+        return ops.score(u_repr, i_repr)
 
 
 class UProtoMFs(_ProtoSideS):
@@ -168,7 +149,7 @@ class UIProtoMFs(SGDBasedRecommenderAlgorithm):
         # u_sim . i_proj + u_proj . i_sim (sgd_alg.py:823-825) as ONE product over the concatenated widths
         u_sim_mtx, u_proj = u_repr
         i_sim_mtx, i_proj = i_repr
-        return _score(torch.cat([u_sim_mtx, u_proj], dim=-1), torch.cat([i_proj, i_sim_mtx], dim=-1))
+        return ops.score(torch.cat([u_sim_mtx, u_proj], dim=-1), torch.cat([i_proj, i_sim_mtx], dim=-1))
 
     @staticmethod
     def build_from_conf(conf: dict, dataset):

@@ -1,5 +1,5 @@
 """The simplified ProtoMF models (uprotomfs, iprotomfs, uiprotomfs) on the GPU: the product classes against the G21 fixture of the real
-reference, ops.ProtoCosFn / ops.ProtoScoreFn (csrc/proto_score.hip) and the models against float64 under the three-way criterion of
+reference, ops.ProtoCosFn / ops.ProtoScoreFn (csrc/proto_cos.hip) and the models against float64 under the three-way criterion of
 tests/test_hip_protomf.py (its KAPPA, REL_FLOOR, TOL and Report; the measured ratios are printed), the kinks compared exactly, the fused
 route against the composed one, the deterministic mode, full-catalogue evaluation and one end-to-end fit per registry name."""
 import json
@@ -264,6 +264,42 @@ def test_proto_score_relu_gate_is_exact():
     # the order form (widx None) is the same arithmetic
     ordered = ops.ProtoScoreFn.apply(t, rows.to(DEV), p, wt[widx.long()].to(DEV), None, fan)
     assert torch.equal(out.detach(), ordered)
+
+
+def _bits(x):
+    return x.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize('R,D,P', [(3, 1, 2), (65, 33, 65), (130, 100, 70)])
+def test_sim_and_cos_entries_share_one_backward(R, D, P):
+    """sbr_proto_sim_* and sbr_proto_score_* (cosine form) are one front end and one backward (csrc/proto_cos.hip), compared in bits on
+    rows named several times: ops.cosine_sim == ops.ProtoCosFn (the same cosine, clamped to [-1, 1]); and with a random G [R, P] into the
+    similarity and nothing into ProtoSimFn's two losses (autograd materialises zeros: the arg-min terms subtract 0) the table gradient
+    and dP of ProtoSimFn == those of ProtoCosFn. Every cosine is away from +-1 (asserted; D = 1: exactly +-1, which both closed intervals
+    pass), so both clamps pass every element and g' is G in both. Deterministic mode fixes the order in which the table gradient adds the
+    rows of a duplicate."""
+    ops = S().ops
+    table, _, protos, _, _, gen = _inputs(R, D, P, 1, seed=R + D + P)
+    rows = torch.randint(0, R + 3, (R,), generator=gen).to(torch.int32)
+    rows[-1] = rows[0]
+    assert len(rows.unique()) < R
+    _assert_away_from_kinks(table[rows.long()], protos, torch.zeros(1))
+    G, idx = torch.randn(R, P, generator=gen).to(DEV), rows.to(DEV)
+    got = {}
+    prev = ops.set_deterministic(True)
+    try:
+        for name, fn in (('sim', lambda t, p: ops.ProtoSimFn.apply(t, idx, p)[0]), ('cos', lambda t, p: ops.ProtoCosFn.apply(t, idx, p))):
+            t, p = table.to(DEV).requires_grad_(True), protos.to(DEV).requires_grad_(True)
+            out = fn(t, p)
+            (out * G).sum().backward()
+            got[name] = (out.detach(), t.grad, p.grad)
+    finally:
+        ops.set_deterministic(prev)
+    assert torch.equal(_bits(ops.cosine_sim(table.to(DEV), idx, protos.to(DEV))), _bits(got['cos'][0])), 'cosine_sim != ProtoCosFn'
+    for n, what in ((1, 'table gradient'), (2, 'dP')):
+        assert tuple(got['sim'][n].shape) == tuple(got['cos'][n].shape)
+        assert torch.equal(_bits(got['sim'][n]), _bits(got['cos'][n])), f'{what} of ProtoSimFn != that of ProtoCosFn'
+        assert D == 1 or bool((got['cos'][n] != 0).any()), f'{what} is all zero'
 
 
 # ---- 5. the fused route against the composed one ------------------------------------------------------------------------------------

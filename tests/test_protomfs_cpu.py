@@ -138,7 +138,7 @@ def test_new_symbols_declared_and_exported():
         assert hasattr(handle, name), f'{name} is not exported by the library'
     assert S.lib().sbr_abi_version() == 4
     header = open(os.path.join(ROOT, 'include', 'sibrar_hip.h')).read()
-    assert 'sgd_alg.py:62-73' in header and 'csrc/proto_score.hip' in header
+    assert 'sgd_alg.py:62-73' in header and 'csrc/proto_cos.hip' in header
     # the workspace sizes are host arithmetic: the reference defaults, and shapes outside the range
     for R in (1, 256, 8192, 45056):
         assert S.lib().sbr_proto_score_workspace(R, 100, 20, 0) > 0 and S.lib().sbr_proto_score_workspace(R, 100, 20, 1) > 0
