@@ -650,6 +650,39 @@ int sbr_csr_rows_times_csr(const long* x_indptr, const int* x_indices, const flo
                            const long* y_indptr, const int* y_indices, const float* y_data, int n_cols, int tile_cols, float* out,
                            long ld, void* stream);
 
+/* ---- EASE on 0/1 data (csrc/ease.hip) ------------------------------------------------------------------------------------------
+ * G = X^T X + diag_add I — algorithms/linear_algs.py:150-153 (`matrix.transpose().dot(matrix).toarray()`, `G[diag] += int(lam)`) as
+ * dense fp32 rows G [m, m] with leading dimension ld >= m. X [n, m] and X^T in the forms sbr_knn_topk takes (binary CSR, sorted,
+ * unique); n <= 2^24, so every count converts to fp32 exactly. A workgroup owns row i of [r0, r1): it walks X^T's row i and, for every
+ * user in it, that user's row of X, counting into int32 LDS counters (integer atomics); each count is converted once, diag_add is
+ * added to the diagonal element (one fp32 addition) and the whole row [0, m) is written, zeros included. Only the rows of [r0, r1)
+ * are written. tile_cols: columns per tile of counters (4 bytes each); 0 = min(max(m, 64), 32768), the default of sbr_knn_topk; a
+ * request over 160 KiB of LDS is an error. The same bits on every run, valid in deterministic mode. New (additive to ABI 4). */
+int sbr_gram_dense(const long* indptr, const int* indices, const long* t_indptr, const int* t_indices, int n, int m, int r0, int r1,
+                   float diag_add, int tile_cols, float* G, long ld, void* stream);
+/* A <- A^-1 in place for a symmetric positive definite fp32 A [n, n], leading dimension ld >= n — `np.linalg.inv(G)`,
+ * algorithms/linear_algs.py:155. Blocked symmetric sweep, pivot blocks K = [k0, min(k0 + 64, n)) in ascending order, three launches
+ * per block:
+ *   1. one workgroup inverts D = A[K, K] by unpivoted Gauss-Jordan (step p: d = 1 / D[p][p]; D[p][p] = d; D[p][j] = D[p][j] * d;
+ *      D[i][p] = -D[i][p] * d; D[i][j] = D[i][j] - D[i][p] * (D[p][j] * d) for i, j != p) and sets *info = 1 + (k0 + p) at the first
+ *      pivot that is <= 0 or not finite, if *info is still 0;
+ *   2. P = A[K, :], R = D^-1 P with R[p][j] = fmaf(D^-1[p][q], P[q][j], .) over q ascending from +0;
+ *   3. A[i][j] <- A[i][j] - S[i][j], S[i][j] = fmaf(P[p][i], R[p][j], .) over p ascending from +0 (the fp32 matrix pipe: the same
+ *      bits as the fmaf chain), for i, j outside K; A[K, j] <- R[:, j], A[i, K] <- R[:, i]^T, A[K, K] <- -D^-1.
+ * After the last block A = -A_in^-1; the last update stores the negated values. Every element has one owner per launch, no float
+ * atomics: the same bits on every run, valid in deterministic mode. Elements outside the n x n view are neither read nor written.
+ * info: one device int32, zero on entry; non-zero afterwards = the matrix was not positive definite in fp32 and A holds no inverse
+ * (an error return, not a fault). workspace: sbr_spd_inverse_f32_workspace(n) bytes at a 16-byte boundary. n = 0 returns at once.
+ * New (additive to ABI 4). */
+int sbr_spd_inverse_f32(float* A, int n, long ld, void* workspace, long workspace_bytes, int* info, void* stream);
+/* bytes of `workspace` for sbr_spd_inverse_f32: D^-1 [64, 64] and the two panels P, R [64, n rounded up to 128]
+ * (algorithms/linear_algs.py:155) */
+long sbr_spd_inverse_f32_workspace(int n);
+/* B[i][j] = P[i][j] / (-P[j][j]) for i != j, B[j][j] = 0, in place on P [n, n] with leading dimension ld —
+ * algorithms/linear_algs.py:157-158 (`P / (-np.diag(P))` divides column j; B is not symmetric). One correctly rounded fp32
+ * division per element. diag: n floats of scratch (the diagonal is read before it is overwritten). New (additive to ABI 4). */
+int sbr_ease_weights_f32(float* P, int n, long ld, float* diag, void* stream);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

@@ -22,6 +22,7 @@ from .acf import ACF                                                            
 from .ecf import ECF, ecf_tag_matrix                                                        # noqa: F401
 from .knn import (ItemKNN, KNNAlgorithm, SimilarityFunctionEnum, SparseMatrixBasedRecommenderAlgorithm,   # noqa: F401
                   UserKNN)
+from .ease import EASE                                                                      # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
                      RecSampledSoftmaxLoss, RecommenderSystemLoss, RecommenderSystemLossesEnum)
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
@@ -48,9 +49,9 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
     ops.set_deterministic(deterministic)
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
-# .uiprotomfs / .acf / .ecf / .uknn / .iknn -> class
+# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ease -> class
 # (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
-              'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN}
+              'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ease': EASE}

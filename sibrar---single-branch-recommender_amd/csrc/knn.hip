@@ -6,6 +6,7 @@
 // No float atomics anywhere: the counts are integers (LDS integer atomics: exact, order-free), every float has one owner and a fixed
 // operation order, so both entries give the same bits on every run and are valid in deterministic mode.
 #include "common.h"
+#include "cooc_count.h"
 
 #define KNN_THREADS 1024
 #define KNN_WAVES (KNN_THREADS / 64)
@@ -125,23 +126,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_topk_kernel(const long* __res
     for (int x = t; x < width; x += KNN_THREADS) cnt[x] = 0u;
     __syncthreads();
     // ---- count
-    for (long p = f_beg + w; p < f_end; p += KNN_WAVES) {
-      const int f = indices[p];
-      long lo = t_indptr[f];
-      const long end = t_indptr[f + 1];
-      if (t0 > 0) {            // first entry with entity id >= t0
-        long hi = end;
-        while (lo < hi) {
-          const long mid = (lo + hi) >> 1;
-          if (t_indices[mid] < t0) lo = mid + 1; else hi = mid;
-        }
-      }
-      for (long q = lo + lane; q < end; q += 64) {
-        const unsigned int x = (unsigned int)(t_indices[q] - t0);
-        if (x >= (unsigned int)width) break;            // sorted: everything behind it lies in a later tile
-        atomicAdd(&cnt[x], 1u);
-      }
-    }
+    sbr_cooc_count_tile(indices, f_beg, f_end, t_indptr, t_indices, t0, width, w, KNN_WAVES, lane, cnt);
     __syncthreads();
     // ---- value, in place
     for (int x = t; x < width; x += KNN_THREADS) {

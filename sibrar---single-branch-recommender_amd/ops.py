@@ -1230,6 +1230,73 @@ def csr_rows_times_csr(x, rows: Optional[torch.Tensor], y, tile_cols: int = 0) -
     return out
 
 
+# ---- EASE (csrc/ease.hip) ---------------------------------------------------------------------------------------------------------
+_SPD_WS = {}
+
+
+def gram_dense(csr, diag_add: float = 0., rows=None, tile_cols: int = 0, out=None) -> torch.Tensor:
+    """``X^T X + diag_add * I`` of a binary resident ``features.DeviceCSR`` X [n, m] as dense float32 [m, m], counted exactly
+    (algorithms/linear_algs.py:150-153). ``rows=(r0, r1)`` computes that row range only (the other rows of a new result are zero, those
+    of ``out`` keep what they hold); ``out``: a float32 [m, m] view with unit column stride to write into; ``tile_cols`` as in the header."""
+    _need_cuda(csr.indptr, out)
+    if csr.data is not None:
+        raise ValueError('gram_dense: the counts are integers for 0/1 data only; this matrix has values')
+    n, m = csr.shape
+    r0, r1 = (0, m) if rows is None else (int(rows[0]), int(rows[1]))
+    if out is None:
+        out = (torch.empty if (r0, r1) == (0, m) else torch.zeros)((m, m), device=csr.indptr.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (m, m) or (m > 1 and out.stride(1) != 1):
+        raise ValueError(f'gram_dense: out must be a float32 [{m}, {m}] view with unit column stride, got {out.dtype} {tuple(out.shape)} '
+                         f'strides {out.stride()}')
+    t_indptr, t_indices, _ = csr.transposed()
+    call('sbr_gram_dense', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, float(diag_add), int(tile_cols),
+         ptr(out), out.stride(0) if m > 1 else max(m, 1), stream())
+    return out
+
+
+def _square_f32_view(A, who):
+    if A.dtype != torch.float32:
+        raise ValueError(f'{who}: float32 only, got {A.dtype}')
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or (A.shape[0] > 1 and (A.stride(1) != 1 or A.stride(0) < A.shape[0])):
+        raise ValueError(f'{who}: a square row-major view is needed, got shape {tuple(A.shape)} strides {A.stride()}')
+    return A.shape[0], (A.stride(0) if A.shape[0] > 1 else 1)
+
+
+def _spd_workspace(device, n):
+    need = (int(lib().sbr_spd_inverse_f32_workspace(n)) + 3) // 4
+    ws = _SPD_WS.get(device)
+    if ws is None or ws.numel() < need:
+        ws = _grow(_SPD_WS, device, need, lambda k: torch.empty(k, device=device, dtype=torch.float32))
+    return ws
+
+
+def spd_inverse_(A: torch.Tensor) -> torch.Tensor:
+    """In-place inverse of a symmetric positive definite float32 matrix (a square row-major view; what lies outside the view is left
+    alone) by the blocked symmetric sweep of ``sbr_spd_inverse_f32`` — ``np.linalg.inv(G)``, algorithms/linear_algs.py:155. Fixed
+    operation order: the same bits on every run. Raises ``ValueError`` naming the pivot when one is not positive (A then holds no
+    inverse). Reads one int32 back: synchronises with the stream."""
+    _need_cuda(A)
+    n, ld = _square_f32_view(A, 'spd_inverse_')
+    if n == 0:
+        return A
+    ws = _spd_workspace(A.device, n)
+    info = torch.zeros(1, device=A.device, dtype=torch.int32)
+    call('sbr_spd_inverse_f32', ptr(A), n, ld, ptr(ws), ws.numel() * 4, ptr(info), stream())
+    bad = int(info.item())
+    if bad:
+        raise ValueError(f'spd_inverse_: pivot {bad - 1} is not positive: the matrix is not positive definite in float32')
+    return A
+
+
+def ease_weights_(P: torch.Tensor) -> torch.Tensor:
+    """``B = P / (-diag(P))`` (column j divided by ``-P[j, j]``) with a zero diagonal, in place — algorithms/linear_algs.py:157-158."""
+    _need_cuda(P)
+    n, ld = _square_f32_view(P, 'ease_weights_')
+    if n:
+        call('sbr_ease_weights_f32', ptr(P), n, ld, ptr(_spd_workspace(P.device, n)), stream())
+    return P
+
+
 class BiasScoreFn(Function):
     """out[b, n] = base[b, n] + user_bias[u[b]] + item_bias[i[b, n]] + global_bias (sgd_alg.py:186-194, 110-119); every term
     optional (None). Bias tables are 1-D float views of the [n, 1] embedding weights. u None: row b; i None: column n."""
