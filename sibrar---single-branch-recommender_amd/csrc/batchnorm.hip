@@ -91,16 +91,9 @@ __global__ void bn_finalize_kernel(double* __restrict__ ws, long n, int D, float
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c == 0 && num_batches) num_batches[0] += 1;
   if (c >= D) return;
-  const double m = sbr_colred_take(ws, 2 * D, c) / (double)n;                 // also re-zeroes the replicas
-  double var = sbr_colred_take(ws, 2 * D, D + c) / (double)n - m * m;
-  if (var < 0.0) var = 0.0;
-  mean[c] = (float)m;
-  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) {
-    const double unbiased = n > 1 ? var * (double)n / (double)(n - 1) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  const double sum = sbr_colred_take(ws, 2 * D, c);                           // also re-zeroes the replicas
+  const double sq = sbr_colred_take(ws, 2 * D, D + c);
+  sbr_bn_finish_column(sum, sq, n, c, eps, momentum, mean, rstd, running_mean, running_var);
 }
 
 __global__ void bn_apply_kernel(const float* __restrict__ X, float* __restrict__ Y, long n, int D,

@@ -180,6 +180,22 @@ __device__ __forceinline__ double sbr_colred_take(double* __restrict__ ws, int K
   return s;
 }
 
+// (sum, sum of squares) of column c over n rows -> the BatchNorm's batch mean / rstd and running statistics (running_mean / running_var
+// may be null together): shared by bn_finalize_kernel (batchnorm.hip) and the last-arriver block of gemm_split_kernel<0, 2>
+__device__ __forceinline__ void sbr_bn_finish_column(double sum, double sq, long n, int c, float eps, float momentum, float* mean, float* rstd,
+                                                     float* running_mean, float* running_var) {
+  const double m = sum / (double)n;
+  double var = sq / (double)n - m * m;
+  if (var < 0.0) var = 0.0;
+  mean[c] = (float)m;
+  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+  if (running_mean) {
+    const double unbiased = n > 1 ? var * (double)n / (double)(n - 1) : var;
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+  }
+}
+
 static __global__ void sbr_colred_final_kernel(double* __restrict__ ws, int KD) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < KD) ws[i] = sbr_colred_take(ws, KD, i);

@@ -1,5 +1,6 @@
-// Shared pieces of the bf16-split fp32 GEMM kernels (gemm_split_f32.hip, gemm_split_tn_f32.hip): the exact three-way split of an
-// fp32 number into bf16 numbers and the MFMA wrapper. See the header of gemm_split_f32.hip for the arithmetic.
+// Shared pieces of the bf16-split fp32 GEMM kernels (gemm_split_f32.hip, gemm_split_wide_f32.hip, gemm_split_tn_f32.hip): the exact
+// three-way split of an fp32 number into bf16 numbers, the six-term multiply-accumulate, the operand loaders / plane stores, the
+// accumulator layout and the launch helper. See the header of gemm_split_f32.hip for the arithmetic.
 #pragma once
 #include "gemm_args.h"
 
@@ -38,3 +39,69 @@ __device__ __forceinline__ sp_f32x16 sp_mfma(const sp_u32x4 a, const sp_u32x4 b,
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(sp_bf16x8, a), __builtin_bit_cast(sp_bf16x8, b), c, 0, 0, 0);
 }
 
+// acc += the six leading partial products of one A triple and one W triple (a[p], w[p]: plane p of the split), smallest terms first:
+// (2,0) (0,2) (1,1) (1,0) (0,1) (0,0). The order is part of the results' bits.
+__device__ __forceinline__ void sp_mac6(const sp_u32x4 (&a)[3], const sp_u32x4 (&w)[3], sp_f32x16& acc) {
+  acc = sp_mfma(a[2], w[0], acc);
+  acc = sp_mfma(a[0], w[2], acc);
+  acc = sp_mfma(a[1], w[1], acc);
+  acc = sp_mfma(a[1], w[0], acc);
+  acc = sp_mfma(a[0], w[1], acc);
+  acc = sp_mfma(a[0], w[0], acc);
+}
+
+// the same for two W triples and two accumulators, term by term: two independent chains, each MFMA behind one of the other chain
+__device__ __forceinline__ void sp_mac6x2(const sp_u32x4 (&a)[3], const sp_u32x4 (&w0)[3], const sp_u32x4 (&w1)[3], sp_f32x16& acc0,
+                                          sp_f32x16& acc1) {
+  acc0 = sp_mfma(a[2], w0[0], acc0); acc1 = sp_mfma(a[2], w1[0], acc1);
+  acc0 = sp_mfma(a[0], w0[2], acc0); acc1 = sp_mfma(a[0], w1[2], acc1);
+  acc0 = sp_mfma(a[1], w0[1], acc0); acc1 = sp_mfma(a[1], w1[1], acc1);
+  acc0 = sp_mfma(a[1], w0[0], acc0); acc1 = sp_mfma(a[1], w1[0], acc1);
+  acc0 = sp_mfma(a[0], w0[1], acc0); acc1 = sp_mfma(a[0], w1[1], acc1);
+  acc0 = sp_mfma(a[0], w0[0], acc0); acc1 = sp_mfma(a[0], w1[0], acc1);
+}
+
+__device__ __forceinline__ void sp_clear(sp_f32x16* acc, const int tiles) {
+#pragma unroll
+  for (int j = 0; j < tiles; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+}
+
+// split 8 values and store their three bf16 planes (16 bytes each, `plane` bytes apart) at LDS address d
+__device__ __forceinline__ void sp_split8_store(unsigned char* d, const int plane, const float4 lo, const float4 hi) {
+  sp_u32x4 p0, p1, p2;
+  sp_split8(lo, hi, p0, p1, p2);
+  *(sp_lds_u32x4*)(d) = p0;
+  *(sp_lds_u32x4*)(d + plane) = p1;
+  *(sp_lds_u32x4*)(d + 2 * plane) = p2;
+}
+
+// the MFMA A operand of `steps` k steps of one row, raw: per k step the 8 floats at p + 16 s (p: the row + 8 * half of the lane)
+__device__ __forceinline__ void sp_load_ksteps(const float* p, float4 (*raw)[2], const int steps) {
+#pragma unroll
+  for (int s = 0; s < steps; ++s) {
+    raw[s][0] = *reinterpret_cast<const float4*>(p + s * 16);
+    raw[s][1] = *reinterpret_cast<const float4*>(p + s * 16 + 4);
+  }
+}
+
+// accumulator register r of a 32 x 32 tile holds row sp_acc_row(r) + 4 * (lane >> 5), column lane & 31
+__device__ __forceinline__ constexpr int sp_acc_row(const int r) { return (r & 3) + 8 * (r >> 2); }
+
+// forward epilogue: bias, then the activation (the two common ones without the switch of sbr_act)
+__device__ __forceinline__ float sp_bias_act(const float acc, const float bias, const int act) {
+  const float v = acc + bias;
+  return act == SBR_ACT_NONE ? v : (act == SBR_ACT_RELU ? sbr_relu(v) : sbr_act(v, act));
+}
+
+static inline bool sp_al16(const void* p, long ld) { return (((uintptr_t)p) & 15) == 0 && (ld & 3) == 0; }
+
+// raise a kernel's dynamic LDS limit once per device (slot: one static int per kernel instantiation, see sbr_attr_stale)
+static inline int sp_raise_lds(const void* kernel, size_t lds, int* slot, const char* message) {
+  if (sbr_attr_stale(slot) && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    sbr_set_error("%s", message);
+    return SBR_ERR_HIP;
+  }
+  return SBR_OK;
+}

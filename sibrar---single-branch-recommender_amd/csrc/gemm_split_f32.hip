@@ -31,9 +31,6 @@
 #define SP_N 128
 #define SP_K 128
 #define SP_WAVES 8
-#ifndef SPM_WAVES
-#define SPM_WAVES 8                         // waves per workgroup of the K = N = 128 kernel (the projector kernel keeps SP_WAVES)
-#endif
 #define SP_PLANE (4 * 8 * 64 * 16)           // bytes of one bf16 plane of W in fragment order: [4 column tiles][8 k steps][64 lanes][8 bf16]
 
 struct SplitArgs {
@@ -56,7 +53,7 @@ struct SplitArgs {
 // EPI 2 (MODE 0): EPI 0 + per-column sums and sums of squares of what is stored (the batch statistics of a BatchNorm that follows,
 // left pending in colsum_ws in the replica layout of sbr_col_reduce<2>: the separate statistics pass over the output is not needed).
 template <int MODE, int EPI>
-__global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs g, int n_blocks) {
+__global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_kernel(SplitArgs g, int n_blocks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int t = threadIdx.x;
   const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -65,67 +62,41 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
   // Block -> wave: SIMD sid = 4 blockIdx + (wave & 3) of the chip takes blocks sid, sid + S, sid + 2 S, ... (S = SIMDs in the grid),
   // alternating between its two waves, so that the matrix pipes - the shared resource of the two waves - get equal block counts
   // (2,816 blocks over 1,024 pipes: 3 or 2 each; numbering the waves 8 blockIdx + wave would give 4 or 2).
-#if SPM_WAVES == 8
-  const int gw = (wave >> 2) * (gridDim.x * 4) + blockIdx.x * 4 + (wave & 3), nw = gridDim.x * SPM_WAVES;
-#else
-  const int gw = wave * gridDim.x + blockIdx.x, nw = gridDim.x * SPM_WAVES;
-#endif
+  const int gw = (wave >> 2) * (gridDim.x * 4) + blockIdx.x * 4 + (wave & 3), nw = gridDim.x * SP_WAVES;
 
   // raw A of one half block: k steps 4 h .. 4 h + 3, per step the 8 floats k = 16 s + 8 half .. + 7 of row l31 of the block
   auto load_half = [&](int blk, int h, float4 (&raw)[4][2]) {
     long row = (long)blk * 32 + l31;
     if (row >= g.M) row = g.M - 1;                               // rows past the end are computed on a valid row and never stored
-    const float* p = g.A + row * g.lda + h * 64 + half * 8;
-#ifdef SP_ABL_COALESCED       /* lab (timing only, wrong results): the same bytes of the block with whole-line wave instructions */
-    const float* pc = g.A + (long)blk * 32 * g.lda + h * 2048 + lane * 4;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      raw[s][0] = *reinterpret_cast<const float4*>(pc + (2 * s) * 256);
-      raw[s][1] = *reinterpret_cast<const float4*>(pc + (2 * s + 1) * 256);
-    }
-    (void)p;
-    return;
-#endif
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      raw[s][0] = *reinterpret_cast<const float4*>(p + s * 16);
-      raw[s][1] = *reinterpret_cast<const float4*>(p + s * 16 + 4);
-    }
+    sp_load_ksteps(g.A + row * g.lda + h * 64 + half * 8, raw, 4);
   };
   float4 r0[4][2], r1[4][2];
   if (gw < n_blocks) load_half(gw, 0, r0);                       // in flight during the set-up
 
   // ---- set-up: the weight as three bf16 planes in fragment order. Chunk (n, kc) = the 8 values W(n, 8 kc .. 8 kc + 7) is the operand
   // of lane (n & 31) + 32 (kc & 1) in fragment (column tile n >> 5, k step kc >> 1). 2048 chunks, 4 per thread.
-  constexpr int SETUP_IT = (2048 + 64 * SPM_WAVES - 1) / (64 * SPM_WAVES);
 #pragma unroll
-  for (int i = 0; i < SETUP_IT; ++i) {
+  for (int i = 0; i < 2048 / (64 * SP_WAVES); ++i) {
     int n, kc;
     float4 lo, hi;
-    if (SPM_WAVES != 8 && (MODE == 0 ? wave + i * SPM_WAVES >= 32 : t + i * 64 * SPM_WAVES >= 2048)) break;
     if constexpr (MODE == 0) {
       // rows of W are contiguous in k. A wave-instruction handles ONE operand fragment (column tile j, k step ks): lane L reads the
       // 8 values W(32 j + (L & 31), 16 ks + 8 (L >> 5) .. + 7) and writes its 16 bytes at lane position L of the fragment —
       // consecutive lanes, consecutive LDS addresses. (Thread order along k — 16 consecutive threads per row — makes 16 lanes write
       // 512 bytes apart: a 16-way bank conflict on every ds_write_b128 of the set-up.)
-      const int f = SPM_WAVES == 8 ? wave * 4 + i : wave + i * SPM_WAVES;      // fragments 4 w .. 4 w + 3 of the 32 (eight waves)
+      const int f = wave * 4 + i;                                // fragments 4 w .. 4 w + 3 of the 32
       n = (f >> 3) * 32 + l31; kc = (f & 7) * 2 + half;
       const float* p = g.W + (long)n * g.ldw + kc * 8;
       lo = *reinterpret_cast<const float4*>(p);
       hi = *reinterpret_cast<const float4*>(p + 4);
     } else {                                                     // rows of W are contiguous in n: consecutive threads read consecutive n
-      const int c = t + i * 64 * SPM_WAVES;
+      const int c = t + i * 64 * SP_WAVES;
       n = c & 127; kc = c >> 7;
       const float* p = g.W + (long)(kc * 8) * g.ldw + n;
       lo = make_float4(p[0], p[g.ldw], p[2 * g.ldw], p[3 * g.ldw]);
       hi = make_float4(p[4 * g.ldw], p[5 * g.ldw], p[6 * g.ldw], p[7 * g.ldw]);
     }
-    sp_u32x4 p0, p1, p2;
-    sp_split8(lo, hi, p0, p1, p2);
-    const int off = ((((n >> 5) * 8 + (kc >> 1)) * 64) + (kc & 1) * 32 + (n & 31)) * 16;
-    *(sp_lds_u32x4*)(smem + off) = p0;
-    *(sp_lds_u32x4*)(smem + SP_PLANE + off) = p1;
-    *(sp_lds_u32x4*)(smem + 2 * SP_PLANE + off) = p2;
+    sp_split8_store(smem + ((((n >> 5) * 8 + (kc >> 1)) * 64) + (kc & 1) * 32 + (n & 31)) * 16, SP_PLANE, lo, hi);
   }
   float bj[4] = {0.f, 0.f, 0.f, 0.f};
   if constexpr (EPI == 0 || EPI == 2) {
@@ -144,8 +115,8 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
   auto mult_half = [&](int h, const float4 (&raw)[4][2]) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      sp_u32x4 a0, a1, a2;
-      sp_split8(raw[s][0], raw[s][1], a0, a1, a2);
+      sp_u32x4 a[3];
+      sp_split8(raw[s][0], raw[s][1], a[0], a[1], a[2]);
       const int ks = h * 4 + s;
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {                           // two column tiles at a time: two independent accumulator chains
@@ -155,19 +126,7 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
 #pragma unroll
           for (int p = 0; p < 3; ++p)
             w[jj][p] = *(const sp_lds_u32x4*)(wfrag + p * SP_PLANE + (((jp * 2 + jj) * 8 + ks) * 64) * 16);
-        // smallest terms first
-        acc[jp * 2 + 0] = sp_mfma(a2, w[0][0], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a2, w[1][0], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a0, w[0][2], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a0, w[1][2], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a1, w[0][1], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a1, w[1][1], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a1, w[0][0], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a1, w[1][0], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a0, w[0][1], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a0, w[1][1], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a0, w[0][0], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a0, w[1][0], acc[jp * 2 + 1]);
+        sp_mac6x2(a, w[0], w[1], acc[jp * 2], acc[jp * 2 + 1]);
       }
     }
   };
@@ -176,15 +135,12 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
   for (int blk = gw; blk < n_blocks; blk += nw) {
     const long m0 = (long)blk * 32;
     load_half(blk, 1, r1);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    sp_clear(acc, 4);
     mult_half(0, r0);
     if (blk + nw < n_blocks) load_half(blk + nw, 0, r0);
     mult_half(1, r1);
 
-    // ---- epilogue: accumulator register r of column tile j is row (r & 3) + 8 (r >> 2) + 4 half of the block, column 32 j + l31
+    // ---- epilogue: accumulator register r of column tile j is row sp_acc_row(r) + 4 half of the block, column 32 j + l31
     const int rows_left = (int)(g.M - m0) - 4 * half;
     auto finish = [&](auto kind_tag, auto full_tag) {
       constexpr int KIND = decltype(kind_tag)::value;            // 0: + bias, 1: relu(+ bias), 2: sbr_act(+ bias), 3: * act'(Y)
@@ -199,13 +155,13 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
         if constexpr (KIND == 3) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int lr = (r & 3) + 8 * (r >> 2);
+            const int lr = sp_acc_row(r);
             yv[r] = (FULL || lr < rows_left) ? yp[(long)lr * g.ldy + j * 32] : 0.f;
           }
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int lr = (r & 3) + 8 * (r >> 2);
+          const int lr = sp_acc_row(r);
           float v = acc[j][r];
           if constexpr (KIND <= 2) v += bj[j];
           if constexpr (KIND == 1) v = sbr_relu(v);
@@ -219,11 +175,7 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
             // error by (mean / std)^2 (batchnorm.hip: bn_stats4_kernel; DESIGN.md, numerical contract of the BatchNorm statistics)
             if (FULL || lr < rows_left) { const double dv = (double)v; cs[j] += dv; cq[j] = fma(dv, dv, cq[j]); }
           }
-#ifdef SP_ABL_NOSTORE       /* lab (timing only): the epilogue stores nothing */
-          asm volatile("" ::"v"(v));
-#else
           if (FULL || lr < rows_left) cp[(long)lr * g.ldc + j * 32] = v;
-#endif
         }
         if constexpr (KIND == 3) cs[j] += (double)ts;
       }
@@ -268,17 +220,7 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
           g.colsum_ws[(long)r * KD + t] = 0.0;
           g.colsum_ws[(long)r * KD + SP_N + t] = 0.0;
         }
-        const double n = (double)g.M;
-        const double m = sm / n;
-        double var = sq / n - m * m;
-        if (var < 0.0) var = 0.0;
-        g.fin_mean[t] = (float)m;
-        g.fin_rstd[t] = (float)(1.0 / sqrt(var + (double)g.fin_eps));
-        if (g.fin_running_mean) {
-          const double unbiased = g.M > 1 ? var * n / (n - 1.0) : var;
-          g.fin_running_mean[t] = (1.f - g.fin_momentum) * g.fin_running_mean[t] + g.fin_momentum * (float)m;
-          g.fin_running_var[t] = (1.f - g.fin_momentum) * g.fin_running_var[t] + g.fin_momentum * (float)unbiased;
-        }
+        sbr_bn_finish_column(sm, sq, g.M, t, g.fin_eps, g.fin_momentum, g.fin_mean, g.fin_rstd, g.fin_running_mean, g.fin_running_var);
         if (t == 0) {
           if (g.fin_nbt) g.fin_nbt[0] += 1;
           __hip_atomic_store(g.fin_arrive, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -298,8 +240,6 @@ __global__ __launch_bounds__(64 * SPM_WAVES, 1) void gemm_split_kernel(SplitArgs
   }
 }
 
-static bool sp_al16(const void* p, long ld) { return (((uintptr_t)p) & 15) == 0 && (ld & 3) == 0; }
-
 // 1 when sbr_gemm_split_f32 takes this product (else use sbr_gemm_f32 / sbr_gemm_wres_f32): N = K = 128
 extern "C" int sbr_gemm_split_supported(long M, int N, int K) { return M >= 1 && N == SP_N && K == SP_K; }
 
@@ -309,6 +249,17 @@ extern "C" int sbr_gemm_split_supported(long M, int N, int K) { return M >= 1 &&
 // contract of sbr_colsum / sbr_colred_finish, may be NULL) receives the pending column sums of C.
 // mode 0 with colsum_ws != NULL (17 * 2 * 128 doubles, zero on entry like every column-reduction workspace): the per-column sums
 // and sums of squares of C are left pending there (sbr_bn_finalize_stats turns them into the statistics of the BatchNorm behind C).
+template <int MODE, int EPI>
+static int sp_launch(const SplitArgs& g, int n_blocks, int grid, hipStream_t s) {
+  static int attr_dev = -1;
+  const size_t lds = 3 * SP_PLANE;
+  const int rc = sp_raise_lds((const void*)gemm_split_kernel<MODE, EPI>, lds, &attr_dev, "sbr_gemm_split_f32: cannot raise the dynamic LDS limit");
+  if (rc != SBR_OK) return rc;
+  gemm_split_kernel<MODE, EPI><<<grid, 64 * SP_WAVES, lds, s>>>(g, n_blocks);
+  SBR_CHECK_LAUNCH("sbr_gemm_split_f32");
+  return SBR_OK;
+}
+
 struct SplitFin { unsigned long long* arrive; float *mean, *rstd, *running_mean, *running_var; long* nbt; float eps, momentum; };
 
 static int gemm_split_impl(int mode, const float* A, long lda, const float* W, long ldw, const float* bias, float* C, long ldc,
@@ -330,28 +281,13 @@ static int gemm_split_impl(int mode, const float* A, long lda, const float* W, l
   g.fin_running_mean = fin ? fin->running_mean : nullptr; g.fin_running_var = fin ? fin->running_var : nullptr;
   g.fin_nbt = fin ? fin->nbt : nullptr; g.fin_eps = fin ? fin->eps : 0.f; g.fin_momentum = fin ? fin->momentum : 0.f;
   const int n_blocks = sbr_cdiv(M, 32);
-  int grid = sbr_cdiv(n_blocks, SPM_WAVES);
+  int grid = sbr_cdiv(n_blocks, SP_WAVES);
   if (grid > 256) grid = 256;
-  const size_t lds = 3 * SP_PLANE;
   hipStream_t s = (hipStream_t)stream;
-#define SP_LAUNCH(MODE, EPI)                                                                                              \
-  do {                                                                                                                     \
-    static int attr_dev = -1;                                                                                          \
-    if (sbr_attr_stale(&attr_dev)) {                                                                                                       \
-      if (hipFuncSetAttribute((const void*)gemm_split_kernel<MODE, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        sbr_set_error("sbr_gemm_split_f32: cannot raise the dynamic LDS limit");                                           \
-        return SBR_ERR_HIP;                                                                                                \
-      }                                                                                                                    \
-    }                                                                                                                      \
-    gemm_split_kernel<MODE, EPI><<<grid, 64 * SPM_WAVES, lds, s>>>(g, n_blocks);                                            \
-  } while (0)
-  if (mode == 0 && colsum_ws) SP_LAUNCH(0, 2);
-  else if (mode == 0) SP_LAUNCH(0, 0);
-  else if (Y) SP_LAUNCH(1, 1);
-  else SP_LAUNCH(1, 0);
-#undef SP_LAUNCH
-  SBR_CHECK_LAUNCH("sbr_gemm_split_f32");
-  return SBR_OK;
+  if (mode == 0 && colsum_ws) return sp_launch<0, 2>(g, n_blocks, grid, s);
+  if (mode == 0) return sp_launch<0, 0>(g, n_blocks, grid, s);
+  if (Y) return sp_launch<1, 1>(g, n_blocks, grid, s);
+  return sp_launch<1, 0>(g, n_blocks, grid, s);
 }
 
 extern "C" int sbr_gemm_split_f32(int mode, const float* A, long lda, const float* W, long ldw, const float* bias, float* C, long ldc,
@@ -383,12 +319,6 @@ extern "C" int sbr_gemm_split_bnstats_f32(const float* A, long lda, const float*
 // weight values of the next chunk and the next half block of A are in flight while the current ones are multiplied.
 // With v_mfma_f32_32x32x2_f32 this product (45,824 x 128 x 768 at the bench's batch) is bound by the fp32 matrix pipe: 57 us of
 // pipe time, 96 us measured; here it needs 6 x 1/16 of that and reads 141 MB of feature rows.
-#ifndef PJ_ABL
-#define PJ_ABL 0                         // lab (timing only): 2 weight planes written once, 3 the first two A chunks only, 4 = 2 + 3, 5 no A split
-#endif
-#ifndef PJ_ALLHALF
-#define PJ_ALLHALF 0                     // 1: EVERY block is shared by the two waves of a SIMD (64 output columns each)
-#endif
 struct ProjArgs {
   const float* A; long lda; const int* a_idx;
   const float* W; long ldw;
@@ -408,7 +338,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_proj_kernel(ProjA
   const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int l31 = lane & 31, half = lane >> 5;
   const int gw = (wave >> 2) * (gridDim.x * 4) + blockIdx.x * 4 + (wave & 3), nw = gridDim.x * SP_WAVES;
-  const int n_it = PJ_ALLHALF ? (n_blocks + gridDim.x * 4 - 1) / (gridDim.x * 4) : (n_blocks + nw - 1) / nw;
+  const int n_it = (n_blocks + nw - 1) / nw;
   const int KC = g.K / PJ_KC;
   constexpr int PL = 4 * 4 * 64 * 16;                            // bytes of one plane of a chunk
   // Work items. A round hands out nw blocks of 32 rows: the first S = nw / 2 to waves 0-3 (one per SIMD), the rest to waves 4-7
@@ -421,16 +351,15 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_proj_kernel(ProjA
   const int rem = n_blocks - last_it * nw;                       // blocks of the last round: 1 .. nw
   const bool half_mode = rem > S && 2 * rem <= 3 * S;
   const int hs = blockIdx.x * 4 + (wave & 3);                    // half item of this wave (waves 4-7, last round, half mode)
-#define PJ_ITEM(it_, blk_, jlo_, jhi_, valid_) do { \
-    if (PJ_ALLHALF) { \
-      blk_ = (it_) * S + blockIdx.x * 4 + (wave & 3); jlo_ = wave >> 2; jhi_ = (wave >> 2) + 1; valid_ = blk_ < n_blocks; \
-    } else \
-    if ((it_) == last_it && half_mode && wave >= 4) { \
-      blk_ = last_it * nw + S + (hs >> 1); jlo_ = hs & 1; jhi_ = (hs & 1) + 1; valid_ = S + (hs >> 1) < rem; \
-    } else { \
-      blk_ = gw + (it_) * nw; jlo_ = 0; jhi_ = 2; valid_ = blk_ < n_blocks; \
-    } \
-  } while (0)
+  // item of this wave in round `it`: row block, the pairs of column tiles jlo .. jhi - 1 it multiplies; false: nothing to do
+  auto item_of = [&](int it, int& blk, int& jlo, int& jhi) __attribute__((always_inline)) -> bool {
+    if (it == last_it && half_mode && wave >= 4) {
+      blk = last_it * nw + S + (hs >> 1); jlo = hs & 1; jhi = (hs & 1) + 1;
+      return S + (hs >> 1) < rem;
+    }
+    blk = gw + it * nw; jlo = 0; jhi = 2;
+    return blk < n_blocks;
+  };
 
   // raw weight values of one chunk. A wave-instruction handles ONE operand fragment (column tile j, k step ks): lane L reads the
   // 8 values W(32 j + (L & 31), 16 ks + 8 (L >> 5) .. + 7) and, after the split, writes its 16 bytes at lane position L of the
@@ -450,22 +379,12 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_proj_kernel(ProjA
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int f = wave * 2 + i;
-      sp_u32x4 p0, p1, p2;
-      sp_split8(wraw[i][0], wraw[i][1], p0, p1, p2);
-      const int off = buf * PJ_BUF + (f * 64 + lane) * 16;
-      *(sp_lds_u32x4*)(smem + off) = p0;
-      *(sp_lds_u32x4*)(smem + PL + off) = p1;
-      *(sp_lds_u32x4*)(smem + 2 * PL + off) = p2;
+      sp_split8_store(smem + buf * PJ_BUF + (f * 64 + lane) * 16, PL, wraw[i][0], wraw[i][1]);
     }
   };
   // chunk q of a row: the 64 values k = 64 q .. 64 q + 63, per k step the 8 floats 16 s + 8 half .. + 7
   auto load_chunk = [&](const float* arow, int q, float4 (&raw)[4][2]) __attribute__((always_inline)) {
-    const float* p = arow + q * PJ_KC + half * 8;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      raw[s][0] = *reinterpret_cast<const float4*>(p + s * 16);
-      raw[s][1] = *reinterpret_cast<const float4*>(p + s * 16 + 4);
-    }
+    sp_load_ksteps(arow + q * PJ_KC + half * 8, raw, 4);
   };
   auto row_ptr = [&](int blk) -> const float* {
     long m = (long)blk * 32 + l31;
@@ -485,13 +404,8 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_proj_kernel(ProjA
     const unsigned char* wfrag = smem + buf * PJ_BUF + lane * 16;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      sp_u32x4 a0, a1, a2;
-      if constexpr (PJ_ABL == 5) {                                 // lab (timing only): no split of the A values — their bits as they are
-        a0 = __builtin_bit_cast(sp_u32x4, raw[s][0]);
-        a1 = __builtin_bit_cast(sp_u32x4, raw[s][1]);
-        a2 = a0 ^ a1;
-      } else
-      sp_split8(raw[s][0], raw[s][1], a0, a1, a2);
+      sp_u32x4 a[3];
+      sp_split8(raw[s][0], raw[s][1], a[0], a[1], a[2]);
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
         if (jp < jlo || jp >= jhi) continue;                       // wave-uniform: a half item multiplies one pair of column tiles
@@ -501,18 +415,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_proj_kernel(ProjA
 #pragma unroll
           for (int p = 0; p < 3; ++p)
             w[jj][p] = *(const sp_lds_u32x4*)(wfrag + p * PL + (((jp * 2 + jj) * 4 + s) * 64) * 16);
-        acc[jp * 2 + 0] = sp_mfma(a2, w[0][0], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a2, w[1][0], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a0, w[0][2], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a0, w[1][2], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a1, w[0][1], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a1, w[1][1], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a1, w[0][0], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a1, w[1][0], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a0, w[0][1], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a0, w[1][1], acc[jp * 2 + 1]);
-        acc[jp * 2 + 0] = sp_mfma(a0, w[0][0], acc[jp * 2 + 0]);
-        acc[jp * 2 + 1] = sp_mfma(a0, w[1][0], acc[jp * 2 + 1]);
+        sp_mac6x2(a, w[0], w[1], acc[jp * 2], acc[jp * 2 + 1]);
       }
     }
   };
@@ -528,51 +431,41 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_proj_kernel(ProjA
   load_w(0);
   {
     int blk0, jl0, jh0;
-    bool v0;
-    PJ_ITEM(0, blk0, jl0, jh0, v0);
-    if (v0) { ap0 = row_ptr(blk0); load_chunk(ap0, 0, r0); load_chunk(ap0, 1, r1); }
+    if (item_of(0, blk0, jl0, jh0)) { ap0 = row_ptr(blk0); load_chunk(ap0, 0, r0); load_chunk(ap0, 1, r1); }
   }
   store_w(0);
   if (n_steps > 1) load_w(1 % KC);
   __syncthreads();
 
+  // A macro, not a lambda: as a lambda over the rotating raw buffers hipcc keeps r0 .. r2 and the accumulators in scratch.
 #define PJ_STEP(CC, cur, fill) do { \
     const int c = (CC); \
     if (c >= n_steps) break; \
     const int it = c / KC, kc = c - it * KC; \
     int blk, jlo, jhi; \
-    bool valid; \
-    PJ_ITEM(it, blk, jlo, jhi, valid); \
-    if (kc == 0) { \
-_Pragma("unroll") \
-      for (int j = 0; j < 4; ++j) \
-_Pragma("unroll") \
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f; \
-    } \
+    const bool valid = item_of(it, blk, jlo, jhi); \
+    if (kc == 0) sp_clear(acc, 4); \
     if (valid) { \
- \
       const int c2 = c + 2, it2 = c2 / KC, kc2 = c2 - it2 * KC; \
       int blk2, jlo2, jhi2; \
-      bool valid2; \
-      PJ_ITEM(it2, blk2, jlo2, jhi2, valid2); \
-      if (PJ_ABL != 3 && PJ_ABL != 4 && c2 < n_steps && valid2) { \
+      const bool valid2 = item_of(it2, blk2, jlo2, jhi2); \
+      if (c2 < n_steps && valid2) { \
         if (kc2 == 0) { if (it2 & 1) ap1 = row_ptr(blk2); else ap0 = row_ptr(blk2); } \
         load_chunk((it2 & 1) ? ap1 : ap0, kc2, fill); \
       } \
       mult_chunk(c & 1, cur, jlo, jhi); \
     } \
-    if (PJ_ABL != 2 && PJ_ABL != 4 && c + 1 < n_steps) { \
+    if (c + 1 < n_steps) { \
       store_w((c + 1) & 1); \
       if (c + 2 < n_steps) load_w((kc + 2) % KC); \
     } \
     if (valid && kc == KC - 1) { \
- \
       const long m0 = (long)blk * 32; \
       const int rows_left = (int)(g.M - m0) - 4 * half; \
       long orow[16]; \
 _Pragma("unroll") \
       for (int r = 0; r < 16; ++r) { \
-        const int lr = (r & 3) + 8 * (r >> 2); \
+        const int lr = sp_acc_row(r); \
         const long m = m0 + 4 * half + lr; \
         orow[r] = (g.c_idx && lr < rows_left) ? (long)g.c_idx[m] : m; \
       } \
@@ -581,10 +474,8 @@ _Pragma("unroll") \
         if ((j >> 1) < jlo || (j >> 1) >= jhi) continue; \
 _Pragma("unroll") \
         for (int r = 0; r < 16; ++r) { \
-          const int lr = (r & 3) + 8 * (r >> 2); \
-          float v = acc[j][r] + bj[j]; \
-          v = g.act == SBR_ACT_NONE ? v : (g.act == SBR_ACT_RELU ? sbr_relu(v) : sbr_act(v, g.act)); \
-          if (lr < rows_left) g.C[orow[r] * g.ldc + j * 32 + l31] = v; \
+          const float v = sp_bias_act(acc[j][r], bj[j], g.act); \
+          if (sp_acc_row(r) < rows_left) g.C[orow[r] * g.ldc + j * 32 + l31] = v; \
         } \
       } \
     } \
@@ -615,12 +506,8 @@ extern "C" int sbr_gemm_split_proj_f32(const float* A, long lda, const int* a_id
   if (grid > 256) grid = 256;                                    // matrix-pipe time to it (see the work-item note in the kernel)
   const size_t lds = 2 * PJ_BUF;
   static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev)) {
-    if (hipFuncSetAttribute((const void*)gemm_split_proj_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      sbr_set_error("sbr_gemm_split_proj_f32: cannot raise the dynamic LDS limit");
-      return SBR_ERR_HIP;
-    }
-  }
+  const int rc = sp_raise_lds((const void*)gemm_split_proj_kernel, lds, &attr_dev, "sbr_gemm_split_proj_f32: cannot raise the dynamic LDS limit");
+  if (rc != SBR_OK) return rc;
   gemm_split_proj_kernel<<<grid, 64 * SP_WAVES, lds, (hipStream_t)stream>>>(g, n_blocks);
   SBR_CHECK_LAUNCH("sbr_gemm_split_proj_f32");
   return SBR_OK;

@@ -20,33 +20,25 @@
 //
 // Work: one workgroup of 8 waves per CU owns a 128 x 128 output tile (column block j of N) over one K range z; it walks the range
 // in chunks of 32 rows (two MFMA k steps).  Both operands of a chunk are 6 planes of 8 KB (48 KB); two plane sets alternate: while
-// chunk c is multiplied, chunk c + 1 is split and written into the other set and the raw values of chunks c + 2 .. c + 4 are in
-// flight (TS_NBUF = 3 raw buffers of 16 registers rotate; 4 measured slower); ONE barrier per chunk.  Waves 0-3 take k step 0 of every chunk, waves 4-7
-// k step 1; within a group each wave owns a 64 x 64 quarter of the tile (4 accumulator tiles, 12 fragment reads per 24 MFMAs).
-// The two groups' sums are added through LDS at the end in a fixed order and ONE slab per workgroup is stored (16 bytes per lane,
-// all eight waves): 256 slabs of 64 KB
-// for a 128 x 128 product, 42 x 6 for 128 x 768 — the ring kernel left 512 / 1536 partial tiles for the slab reducer.
-// Row pointers of the range (gathered or not; the pointer of a zero row past the end of K) are staged in LDS once.
+// chunk c is multiplied, chunk c + 1 (raw buffer (c + 1) % 3) is split and written into the other set, and the raw values of chunks
+// c + 2, c + 3 and, once requested behind the split, c + 4 are in flight: three raw buffers of 16 registers rotate (a fourth
+// measured slower); ONE barrier per chunk.  The plane sets rotate with period 2 and the raw buffers with period 3, so the loop
+// is unrolled by 6.  Waves 0-3 take k step 0 of every chunk, waves 4-7 k step 1; within a group each wave owns a 64 x 64 quarter
+// of the tile (4 accumulator tiles, 12 fragment reads per 24 MFMAs).  The two groups' sums are added through LDS at the end in
+// a fixed order and ONE slab per workgroup is stored (16 bytes per lane, all eight waves): 256 slabs of 64 KB for a 128 x 128
+// product, 42 x 6 for 128 x 768 — the ring kernel left 512 / 1536 partial tiles for the slab reducer.
+// Row pointers of the range (gathered or not; the pointer of a zero row past the end of K) are staged in LDS once, instead of
+// SALU arithmetic and scalar index loads one step ahead (measured slower, 29.8 / 73.5 us against 26.4 / 64.4 us: the scalar loads
+// share lgkmcnt with the LDS traffic).
 // Column blocks of the same K range run on the same XCD (its L2 then serves the re-reads of dZ).
 #include "gemm_split_common.h"
 
-#ifndef TS_ABL
-#define TS_ABL 0                  // lab (timing only): 1 no global loads in the loop, 2 no split / plane stores in the loop, 3 = 1 + 2, 4 no loop at all (set-up, prologue and epilogue only)
-#endif
-#ifndef TS_SALU
-#define TS_SALU 0                 // 0: row pointer lists staged in LDS; 1 (experiment, measured SLOWER: 29.8 / 73.5 us against 26.4 / 64.4 us on the
-                                  // same box): row pointers by SALU arithmetic + scalar index loads one step ahead — the set-up loses its
-                                  // memory round trip (7.6 instead of 8.7 us without any chunk), but the scalar loads share lgkmcnt with the
-                                  // LDS traffic: every fragment / barrier wait of the next step also waits for them
-#endif
 #define TS_KC 32                  // rows per chunk
 #define TS_PL (4 * 2 * 64 * 16)   // one bf16 plane of one operand of a chunk: [4 tiles of 32 columns][2 k steps][64 lanes][16 B] = 8 KB
 #define TS_OP (3 * TS_PL)         // the three planes of an operand
 #define TS_BUF (2 * TS_OP)        // a plane set: A then B (48 KB)
-#ifndef TS_NBUF
-#define TS_NBUF 3                 // raw chunk buffers (3 or 4): chunks c + 2 .. c + TS_NBUF + 1 are in flight while chunk c is multiplied
-#endif
-#define TS_PAD (TS_NBUF == 4 ? 8 : 9)   // chunks of zero-row padding behind a range: 3 (5) of the rounded-up loop + 5 (4) of prefetch
+#define TS_PAD 9                  // chunks of zero-row padding behind a range: up to 5 steps of the trip count rounded up to 6, whose last
+                                  // step requests the chunk 4 ahead of it
 #define TS_MAXROWS (2048 + TS_PAD * TS_KC)   // rows of a K range + padding (the two row-pointer lists are staged in LDS: 37 KB)
 
 struct TnSplitArgs {
@@ -83,7 +75,6 @@ __device__ __forceinline__ void ts_body(const TnSplitArgs& g, const int bid, con
   const int n_chunks = cb + (z < cr ? 1 : 0);                      // >= 1 (host: nz <= chunks), <= TS_MAXROWS / 32 - TS_PAD
   const long row0 = (long)c_begin * TS_KC;
 
-#if !TS_SALU
   // ---- row pointers of the range (operand B: of column block j), the zero row for rows past the end
   unsigned long long* ptrs = reinterpret_cast<unsigned long long*>(smem + 2 * TS_BUF);            // [2][TS_MAXROWS]
   {
@@ -115,7 +106,6 @@ __device__ __forceinline__ void ts_body(const TnSplitArgs& g, const int bid, con
     }
   }
   __syncthreads();
-#endif
 
   // ---- loader role: waves 0-3 operand A, waves 4-7 operand B; wave & 3 = the group of 8 rows of the chunk; a thread owns the
   // columns 2 lane and 2 lane + 1 of its operand's 128
@@ -123,51 +113,7 @@ __device__ __forceinline__ void ts_body(const TnSplitArgs& g, const int bid, con
   // destination of the split values: fragment (tile = half [+ 2 for the odd column], k step = rg >> 1), lane position l31 + 32 (rg & 1)
   const int st_off = op * TS_OP + ((((half) * 2 + (rg >> 1)) * 64) + l31 + 32 * (rg & 1)) * 16;
 
-  sp_f32x2 r0[8], r1[8], r2[8], r3[8];
-#if TS_SALU
-  // Row pointers without LDS or VALU: the wave's eight rows of a chunk are wave-uniform, so their pointers are SALU arithmetic on
-  // SGPRs — base + row * ld for a plain operand, base + idx[row] * ld with the indices of the NEXT chunk to request fetched by
-  // scalar loads one step ahead (through the constant address space: the index lists are read-only for the launch); rows past
-  // the end of the range or of K get the zero row (s_cselect). No pointer list is staged, the set-up needs no memory round trip.
-  typedef const __attribute__((address_space(4))) int* ts_cidx;
-  const float* obase = op ? g.B + (long)j * 128 : g.A + (long)mi * 128;
-  const long old_ = op ? g.ldb : g.lda;
-  const int* gidx = op ? g.b_idx : g.a_idx;
-  const bool has_idx = gidx != nullptr;
-  typedef int ts_i8 __attribute__((ext_vector_type(8), aligned(4)));
-  typedef const __attribute__((address_space(4))) ts_i8* ts_cidx8;
-  const ts_cidx sidx = (ts_cidx)gidx + row0;                        // first entry of the range in the index list
-  const long rows_left = (long)g.K - row0;
-  const int valid_rows = (int)(rows_left < (long)n_chunks * TS_KC ? rows_left : (long)n_chunks * TS_KC);      // >= 1
-  int nid[8];
-  // the eight table rows of the wave's row group of chunk C: one s_load_dwordx8 (a group that reaches past the end of the range:
-  // clamped single loads — the last chunk of the last range only; plain operands: the row numbers themselves)
-#define TS_IDX(C, ids) do { \
-    const int r0_ = (C) * TS_KC + rg * 8; \
-    if (!has_idx) { \
-_Pragma("unroll") \
-      for (int q_ = 0; q_ < 8; ++q_) ids[q_] = (int)row0 + r0_ + q_; \
-    } else if (r0_ + 8 <= valid_rows) { \
-      const ts_i8 v_ = *(ts_cidx8)(sidx + r0_); \
-_Pragma("unroll") \
-      for (int q_ = 0; q_ < 8; ++q_) ids[q_] = v_[q_]; \
-    } else { \
-_Pragma("unroll") \
-      for (int q_ = 0; q_ < 8; ++q_) ids[q_] = sidx[r0_ + q_ < valid_rows ? r0_ + q_ : valid_rows - 1]; \
-    } \
-  } while (0)
-#define TS_LOADI(C, raw, ids) do { \
-_Pragma("unroll") \
-    for (int q_ = 0; q_ < 8; ++q_) { \
-      const int r_ = (C) * TS_KC + rg * 8 + q_; \
-      const bool in_ = r_ < valid_rows; \
-      const float* b_ = in_ ? obase : (const float*)ts_zero_row; \
-      const long o_ = in_ ? (long)ids[q_] * old_ : 0; \
-      raw[q_] = ((ts_gptr)(b_ + o_))[lane]; \
-    } \
-  } while (0)
-#define TS_LOAD(C, raw) do { TS_LOADI(C, raw, nid); TS_IDX((C) + 1, nid); } while (0)
-#else
+  sp_f32x2 r0[8], r1[8], r2[8];
   const unsigned char* optr = smem + 2 * TS_BUF + (op * TS_MAXROWS + rg * 8) * 8;
 #define TS_LOAD(C, raw) do { \
     const sp_lds_u32x4* ip_ = (const sp_lds_u32x4*)(optr + (C) * (TS_KC * 8)); \
@@ -180,7 +126,6 @@ _Pragma("unroll") \
     raw[q] = pa_[lane]; \
     raw[q + 1] = pb_[lane]; \
   } while (0)
-#endif
 #define TS_STORE(buf, raw) do { \
 _Pragma("unroll") \
     for (int h_ = 0; h_ < 2; ++h_) { \
@@ -198,10 +143,7 @@ _Pragma("unroll") \
   const int fa_off = ((mh * 2 + ks) * 64 + lane) * 16;                        // A fragment of tile mh (+ 2 tiles for mh + 2)
   const int fb_off = TS_OP + ((nh * 2 + ks) * 64 + lane) * 16;
   sp_f32x16 acc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[i][q] = 0.f;
+  sp_clear(acc, 4);
 #define TS_MULT(buf) do { \
     const unsigned char* f_ = smem + (buf) * TS_BUF; \
     sp_u32x4 a_[2][3], b_[2][3]; \
@@ -221,79 +163,46 @@ _Pragma("unroll") \
     acc[3] = sp_mfma(a_[1][pa], b_[1][pb], acc[3]); \
   } while (0)
 
-  // ---- prologue: chunks 0 .. 3 in flight, chunk 0 split into set 0, chunk 4 requested
-#if TS_SALU
-  {
-    int i0[8], i1[8];                                              // two index chunks per round of scalar loads
-    TS_IDX(0, i0); TS_IDX(1, i1);
-    TS_LOADI(0, r0, i0);
-    TS_LOADI(1, r1, i1);
-    TS_IDX(2, i0); TS_IDX(3, i1);
-    TS_LOADI(2, r2, i0);
-    if (TS_NBUF == 4) { TS_LOADI(3, r3, i1); TS_IDX(4, nid); } else { _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) nid[q_] = i1[q_]; }
-  }
-  TS_STORE(0, r0);
-  TS_LOAD(TS_NBUF, r0);
-#else
+  // ---- prologue: chunks 0 .. 2 requested (r0, r1, r2), chunk 0 split into set 0, chunk 3 requested into its buffer (r0)
   TS_LOAD(0, r0);
   TS_LOAD(1, r1);
   TS_LOAD(2, r2);
-  if (TS_NBUF == 4) TS_LOAD(3, r3);
   TS_STORE(0, r0);
-  TS_LOAD(TS_NBUF, r0);
-#endif
+  TS_LOAD(3, r0);
   __syncthreads();
 
-  // step c: multiply set c & 1; split chunk c + 1 (raw buffer (c + 1) % 4) into the other set; request chunk c + 5 into that buffer.
-  // The loop body has NO branch: the trip count is rounded up to the period of the two rotations (4) and chunks past the end of the
-  // range are chunks of the zero row (the pointer list is padded) — they cost up to three steps of MFMAs on zeros. With a branch
-  // around the loads or the step, hipcc's wait-count pass can no longer tell how many loads are behind the one it needs and
-  // waits vmcnt(0) in front of every split, i.e. for the prefetch of the next two chunks.
-  // The two waves of a SIMD (w and w + 4: one of each k-step group) take the two halves of a step in opposite order, so that one
-  // issues MFMAs while the other one splits and writes (TS_SKEW=0: both multiply first).
-#ifndef TS_SKEW
-#define TS_SKEW 0
-#endif
-#ifndef TS_SGB
-#define TS_SGB 4                  // VALU instructions the scheduler is asked to place behind every MFMA of a step (0: its own order)
-#endif
+  // step c: multiply set c & 1; split chunk c + 1 (raw buffer (c + 1) % 3) into the other set; request chunk c + 4 into that buffer
+  // (chunks c + 2 and c + 3 are already in flight in the other two). Both waves of a SIMD multiply first and split second.
+  // The loop body has NO branch: the trip count is rounded up to the period of the two rotations (6 = lcm of 2 plane sets and 3 raw
+  // buffers) and chunks past the end of the range are chunks of the zero row (the pointer list is padded by TS_PAD) — they cost up
+  // to five steps of MFMAs on zeros. With a branch around the loads or the step, hipcc's wait-count pass can no longer tell how many
+  // loads are behind the one it needs and waits vmcnt(0) in front of every split, i.e. for the prefetch of the next two chunks.
+  // TS_PIPE asks the scheduler for four VALU instructions (of the split) behind every MFMA of a step.
+  // The TS_* statements stay macros: the same text as lambdas or with sp_mac6x2 / sp_split8_store compiles to a different
+  // instruction stream (other register allocation and wait counts) in this loop, whose schedule is what the kernel's time depends on.
 #define TS_PIPE() do { \
-    if (TS_SGB > 0) { \
 _Pragma("unroll") \
-      for (int i_ = 0; i_ < 24; ++i_) { \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); \
-        __builtin_amdgcn_sched_group_barrier(0x002, TS_SGB, 0); \
-      } \
+    for (int i_ = 0; i_ < 24; ++i_) { \
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); \
+      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0); \
     } \
   } while (0)
 #define TS_STEP(CC, nxt) do { \
     const int c_ = (CC); \
-    if (TS_SKEW && ks == 1) { \
-      if (TS_ABL != 2 && TS_ABL != 3) TS_STORE((c_ + 1) & 1, nxt); \
-      TS_MULT(c_ & 1); \
-    } else { \
-      TS_MULT(c_ & 1); \
-      if (TS_ABL != 2 && TS_ABL != 3) TS_STORE((c_ + 1) & 1, nxt); \
-    } \
-    if (TS_ABL != 1 && TS_ABL != 3) TS_LOAD(c_ + TS_NBUF + 1, nxt); \
+    TS_MULT(c_ & 1); \
+    TS_STORE((c_ + 1) & 1, nxt); \
+    TS_LOAD(c_ + 4, nxt); \
     TS_PIPE(); \
     __syncthreads(); \
   } while (0)
 #pragma unroll 1
-  for (int c0 = 0; c0 < (TS_ABL == 4 ? 0 : n_chunks); c0 += (TS_NBUF == 4 ? 4 : 6)) {
-    if (TS_NBUF == 4) {
-      TS_STEP(c0, r1);
-      TS_STEP(c0 + 1, r2);
-      TS_STEP(c0 + 2, r3);
-      TS_STEP(c0 + 3, r0);
-    } else {
-      TS_STEP(c0, r1);
-      TS_STEP(c0 + 1, r2);
-      TS_STEP(c0 + 2, r0);
-      TS_STEP(c0 + 3, r1);
-      TS_STEP(c0 + 4, r2);
-      TS_STEP(c0 + 5, r0);
-    }
+  for (int c0 = 0; c0 < n_chunks; c0 += 6) {
+    TS_STEP(c0, r1);
+    TS_STEP(c0 + 1, r2);
+    TS_STEP(c0 + 2, r0);
+    TS_STEP(c0 + 3, r1);
+    TS_STEP(c0 + 4, r2);
+    TS_STEP(c0 + 5, r0);
   }
 
   // ---- epilogue: both k-step groups write their quarter tiles into a row-major 128 x 128 image each (the plane sets and the
@@ -311,7 +220,7 @@ _Pragma("unroll") \
         sp_f32x2 v;
         v[0] = acc[x * 2][q];
         v[1] = acc[x * 2 + 1][q];
-        *reinterpret_cast<sp_f32x2*>(w + (2 * ((q & 3) + 8 * (q >> 2)) + x) * 128) = v;
+        *reinterpret_cast<sp_f32x2*>(w + (2 * sp_acc_row(q) + x) * 128) = v;
       }
   }
   __syncthreads();
@@ -364,22 +273,15 @@ int sbr_tn_split_launch(const float* A, long lda, const int* a_idx, const float*
   TnSplitArgs g;
   g.A = A; g.lda = lda; g.a_idx = a_idx; g.B = B; g.ldb = ldb; g.b_idx = b_idx; g.slab = slab; g.N = N; g.K = K;
   g.M = M; g.nz = nz; g.nj = N / 128; g.nm = M / 128; g.chunks = sbr_cdiv(K, TS_KC);
-  const size_t lds = TS_SALU ? 2 * 128 * 128 * sizeof(float) : 2 * TS_BUF + 2 * TS_MAXROWS * sizeof(unsigned long long);   // TS_SALU: the epilogue images (128 KB)
+  const size_t lds = 2 * TS_BUF + 2 * TS_MAXROWS * sizeof(unsigned long long);
   const int grid = sbr_cdiv(nz * g.nj * g.nm, 8) * 8;
-#define TS_LAUNCH(WIDE)                                                                                                   \
-  do {                                                                                                                     \
-    static int attr_dev = -1;                                                                                          \
-    if (sbr_attr_stale(&attr_dev)) {                                                                                                       \
-      if (hipFuncSetAttribute((const void*)gemm_split_tn_kernel<WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        sbr_set_error("sbr_gemm_tn_f32: cannot raise the dynamic LDS limit of the bf16-split kernel");                     \
-        return SBR_ERR_HIP;                                                                                                \
-      }                                                                                                                    \
-    }                                                                                                                      \
-    gemm_split_tn_kernel<WIDE><<<grid, 512, lds, s>>>(g);                                                                  \
-  } while (0)
-  if (g.nj * g.nm > 1) TS_LAUNCH(true);
-  else TS_LAUNCH(false);
-#undef TS_LAUNCH
+  static int attr_dev[2] = {-1, -1};                               // one per instantiation
+  const bool wide = g.nj * g.nm > 1;
+  const void* kernel = wide ? (const void*)gemm_split_tn_kernel<true> : (const void*)gemm_split_tn_kernel<false>;
+  const int rc = sp_raise_lds(kernel, lds, &attr_dev[wide], "sbr_gemm_tn_f32: cannot raise the dynamic LDS limit of the bf16-split kernel");
+  if (rc != SBR_OK) return rc;
+  if (wide) gemm_split_tn_kernel<true><<<grid, 512, lds, s>>>(g);
+  else gemm_split_tn_kernel<false><<<grid, 512, lds, s>>>(g);
   SBR_CHECK_LAUNCH("sbr_gemm_tn_f32 (bf16 split)");
   *splits_out = nz;
   return SBR_OK;

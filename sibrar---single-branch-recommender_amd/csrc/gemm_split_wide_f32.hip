@@ -103,22 +103,12 @@ __global__ __launch_bounds__(64 * SW_WAVES, 1) void gemm_split_wide_kernel(WideA
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int f = wave * 2 + i;
-      sp_u32x4 p0, p1, p2;
-      sp_split8(wraw[i][0], wraw[i][1], p0, p1, p2);
-      const int off = buf * SW_BUF + (f * 64 + lane) * 16;
-      *(sp_lds_u32x4*)(smem + off) = p0;
-      *(sp_lds_u32x4*)(smem + SW_PL + off) = p1;
-      *(sp_lds_u32x4*)(smem + 2 * SW_PL + off) = p2;
+      sp_split8_store(smem + buf * SW_BUF + (f * 64 + lane) * 16, SW_PL, wraw[i][0], wraw[i][1]);
     }
   };
   // chunk kc of the wave's row: per k step the 8 floats k = 32 kc + 16 s + 8 half .. + 7
   auto load_chunk = [&](const float* arow, int kc, float4 (&raw)[2][2]) __attribute__((always_inline)) {
-    const float* p = arow + kc * SW_KC + half * 8;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      raw[s][0] = *reinterpret_cast<const float4*>(p + s * 16);
-      raw[s][1] = *reinterpret_cast<const float4*>(p + s * 16 + 4);
-    }
+    sp_load_ksteps(arow + kc * SW_KC + half * 8, raw, 2);
   };
   auto row_ptr = [&](int grp) -> const float* {
     long m = ((long)grp * SW_WAVES + wave) * 32 + l31;
@@ -142,22 +132,16 @@ __global__ __launch_bounds__(64 * SW_WAVES, 1) void gemm_split_wide_kernel(WideA
       for (int p = 0; p < 3; ++p) w[set][p] = *(const sp_lds_u32x4*)(wfrag + p * SW_PL + ((j * 2 + s) * 64) * 16);
     };
     fetch(0, 0, 0);
-    sp_u32x4 a0, a1, a2;
-    sp_split8(raw[0][0], raw[0][1], a0, a1, a2);
+    sp_u32x4 a[3];
+    sp_split8(raw[0][0], raw[0][1], a[0], a[1], a[2]);
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int j = u & 7, set = u & 1;
       if (u + 1 < 16) fetch(set ^ 1, (u + 1) >> 3, (u + 1) & 7);
       __builtin_amdgcn_sched_barrier(0);                         // the reads of unit u + 1 stay in front of the MFMAs of unit u
-      // smallest terms first
-      acc[j] = sp_mfma(a2, w[set][0], acc[j]);
-      acc[j] = sp_mfma(a0, w[set][2], acc[j]);
-      acc[j] = sp_mfma(a1, w[set][1], acc[j]);
-      acc[j] = sp_mfma(a1, w[set][0], acc[j]);
-      acc[j] = sp_mfma(a0, w[set][1], acc[j]);
-      acc[j] = sp_mfma(a0, w[set][0], acc[j]);
+      sp_mac6(a, w[set], acc[j]);
       if (u == 7) {
-        sp_split8(raw[1][0], raw[1][1], a0, a1, a2);             // the operands of k step 1 (behind the last MFMAs of k step 0)
+        sp_split8(raw[1][0], raw[1][1], a[0], a[1], a[2]);            // the operands of k step 1 (behind the last MFMAs of k step 0)
         if (next_row) load_chunk(next_row, next_kc, raw);        // both k steps are split: the A chunk of the next step takes the registers
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -180,16 +164,15 @@ __global__ __launch_bounds__(64 * SW_WAVES, 1) void gemm_split_wide_kernel(WideA
   }
   __syncthreads();
 
+  // A macro, not a lambda: as a lambda the step compiles to another schedule around the sched_barriers of mult_chunk (234 instead
+  // of 255 VGPRs, more waits).
 #define SW_STEP(CC) do { \
     const int c = (CC); \
     if (c >= n_steps) break; \
     const int q = c / KC, kc = c - q * KC; \
     if (kc == 0) { \
       item_of(q, grp_c, cb_c); \
-_Pragma("unroll") \
-      for (int j = 0; j < 8; ++j) \
-_Pragma("unroll") \
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f; \
+      sp_clear(acc, 8); \
     } \
     const float* nrow = nullptr; \
     int nkc = 0; \
@@ -216,17 +199,13 @@ _Pragma("unroll") \
       for (int j = 0; j < 8; ++j) bj[j] = g.bias ? g.bias[(long)cb_c * SW_N + j * 32 + l31] : 0.f; \
 _Pragma("unroll") \
       for (int r = 0; r < 16; ++r) { \
-        const int lr = (r & 3) + 8 * (r >> 2); \
+        const int lr = sp_acc_row(r); \
         if (lr < rows_left) { \
           const long m = m0 + 4 * half + lr; \
           const long orow = g.c_idx ? (long)g.c_idx[m] : m; \
           float* cp = g.C + orow * g.ldc + (long)cb_c * SW_N + l31; \
 _Pragma("unroll") \
-          for (int j = 0; j < 8; ++j) { \
-            float v = acc[j][r] + bj[j]; \
-            v = g.act == SBR_ACT_NONE ? v : (g.act == SBR_ACT_RELU ? sbr_relu(v) : sbr_act(v, g.act)); \
-            cp[j * 32] = v; \
-          } \
+          for (int j = 0; j < 8; ++j) cp[j * 32] = sp_bias_act(acc[j][r], bj[j], g.act); \
         } \
       } \
     } \
@@ -239,8 +218,6 @@ _Pragma("unroll") \
   }
 }
 
-static bool sw_al16(const void* p, long ld) { return (((uintptr_t)p) & 15) == 0 && (ld & 3) == 0; }
-
 // 1 when sbr_gemm_split_wide_f32 takes this product: N a multiple of 256, K a multiple of 32 of at least 64
 extern "C" int sbr_gemm_split_wide_supported(long M, int N, int K) { return M >= 1 && N >= SW_N && N % SW_N == 0 && K >= 2 * SW_KC && K % SW_KC == 0; }
 
@@ -252,7 +229,7 @@ extern "C" int sbr_gemm_split_wide_f32(int mode, const float* A, long lda, const
   if (M == 0) return SBR_OK;
   SBR_REQUIRE(sbr_gemm_split_wide_supported(M, N, K), "sbr_gemm_split_wide_f32: shape %ld x %d x %d not supported (N = 256 i, K = 32 j >= 64)", M, N, K);
   SBR_REQUIRE(A && W && C, "sbr_gemm_split_wide_f32: null operand");
-  SBR_REQUIRE(sw_al16(A, lda) && (mode == 1 || sw_al16(W, ldw)), "sbr_gemm_split_wide_f32: operands must be 16-byte aligned");
+  SBR_REQUIRE(sp_al16(A, lda) && (mode == 1 || sp_al16(W, ldw)), "sbr_gemm_split_wide_f32: operands must be 16-byte aligned");
   WideArgs g;
   g.A = A; g.lda = lda; g.a_idx = a_idx; g.W = W; g.ldw = ldw; g.bias = bias; g.C = C; g.ldc = ldc; g.c_idx = c_idx;
   g.M = M; g.N = N; g.K = K; g.act = act; g.w_kn = mode;
@@ -261,12 +238,8 @@ extern "C" int sbr_gemm_split_wide_f32(int mode, const float* A, long lda, const
   if (grid > 256) grid = 256;
   const size_t lds = 2 * SW_BUF;
   static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev)) {
-    if (hipFuncSetAttribute((const void*)gemm_split_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      sbr_set_error("sbr_gemm_split_wide_f32: cannot raise the dynamic LDS limit");
-      return SBR_ERR_HIP;
-    }
-  }
+  const int rc = sp_raise_lds((const void*)gemm_split_wide_kernel, lds, &attr_dev, "sbr_gemm_split_wide_f32: cannot raise the dynamic LDS limit");
+  if (rc != SBR_OK) return rc;
   gemm_split_wide_kernel<<<grid, 64 * SW_WAVES, lds, (hipStream_t)stream>>>(g, n_groups, n_cb);
   SBR_CHECK_LAUNCH("sbr_gemm_split_wide_f32");
   return SBR_OK;

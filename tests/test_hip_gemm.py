@@ -637,6 +637,11 @@ def test_split_proj():
     run('proj', 0, 64, 128, 512)
     # more blocks than the grid's waves take in one pass (256 workgroups x 8 waves x 32 rows)
     run('proj', 0, 256 * 8 * 32 + 45, 128, 256, gather=True, bias=True, act=1, fams=('ints', 'rand6'))
+    # half-item mode of the last round, rem > S && 2 * rem <= 3 * S at the capped grid (256 workgroups: S = 1,024 blocks of 32 rows, one
+    # round = 2 S): both sides of each term — rem = 1,024 (rem > S fails), 1,025 and 1,536 (both hold), 1,537 (2 * rem <= 3 * S fails);
+    # every last block is ragged
+    for blocks in (1024, 1025, 1536, 1537):
+        run('proj', 0, 32 * blocks - 3, 128, 256, gather=True, bias=True, act=1, fams=('ints', 'rand6'))
     M = 40
     Ab, Wb, Cb = _Buf(M, 256, ld=260, fill=1.0), _Buf(128, 256, ld=260, fill=1.0), _Buf(M, 128, ld=131)
     for A, W in ((_Buf(M, 256, ld=260, off=1, fill=1.0), Wb), (_Buf(M, 256, ld=259, fill=1.0), Wb), (Ab, _Buf(128, 256, ld=260, off=2, fill=1.0))):
@@ -665,7 +670,7 @@ def test_split_wide(mode):
         A = _Buf(M, 64, ld=68, off=1, fill=1.0)
         call('sbr_gemm_split_wide_f32', mode, A.ptr, A.ld, None, Wb.ptr, Wb.ld, None, Cb.ptr, Cb.ld, None, M, 256, 64, 0, stream())
     if mode == 0:
-        with pytest.raises(_err(), match='16-byte aligned'):       # mode == 1 || sw_al16(W, ldw)
+        with pytest.raises(_err(), match='16-byte aligned'):       # mode == 1 || sp_al16(W, ldw)
             W = _Buf(256, 64, ld=67, fill=1.0)
             call('sbr_gemm_split_wide_f32', 0, Ab.ptr, Ab.ld, None, W.ptr, W.ld, None, Cb.ptr, Cb.ld, None, M, 256, 64, 0, stream())
     else:
