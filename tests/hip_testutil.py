@@ -11,6 +11,7 @@ DEV = 'cuda'
 U32 = 2.0 ** -24
 NAN = float('nan')
 GUARD = 64                                   # guard elements in front of and behind a view (a multiple of 4: keeps the alignment)
+INT_GUARD = {torch.int32: -0x5A5A5A5B, torch.uint8: 0xA5}            # what an integer _Buf holds where a float one holds NaN
 EXP_ULP = 4 * U32                            # allowed relative error of one expf / logf / tanhf call (2 ulp)
 SELU_A, SELU_S = 1.6732632423543772848170429916717, 1.0507009873554804934193349852946
 SELU_AF, SELU_SF = float(np.float32(SELU_A)), float(np.float32(SELU_S))
@@ -62,12 +63,13 @@ def _p(t):
 
 class _Buf:
     """A [rows, cols] fp32 view with row stride ld >= cols inside a NaN-filled flat buffer; ``off`` elements (4 bytes each) shift the
-    base pointer off the allocation's 16-byte boundary."""
+    base pointer off the allocation's 16-byte boundary. An integer ``dtype`` (int32, uint8) is filled with its INT_GUARD pattern."""
 
     def __init__(self, rows, cols, ld=None, off=0, data=None, fill=None, dtype=torch.float32):
         self.rows, self.cols, self.ld, self.off = rows, cols, ld or cols, off
         assert self.ld >= cols
-        self.flat = torch.full((GUARD + off + rows * self.ld + GUARD,), NAN, device=DEV, dtype=dtype)
+        self.guard = NAN if dtype.is_floating_point else INT_GUARD[dtype]
+        self.flat = torch.full((GUARD + off + rows * self.ld + GUARD,), self.guard, device=DEV, dtype=dtype)
         self.t = self._view(self.flat)
         assert (self.t.data_ptr() - self.flat.data_ptr()) == (GUARD + off) * self.flat.element_size()
         if data is not None:
@@ -94,7 +96,8 @@ class _Buf:
             mv[:] = True
         else:
             mv[written_rows] = True
-        assert bool(torch.isnan(host[~may]).all()), f'{what}: {int((~torch.isnan(host[~may])).sum())} elements outside the addressed rows / columns were written'
+        kept = torch.isnan(host[~may]) if host.dtype.is_floating_point else host[~may] == self.guard
+        assert bool(kept.all()), f'{what}: {int((~kept).sum())} elements outside the addressed rows / columns were written'
         return self._view(host)
 
 
