@@ -362,19 +362,12 @@ def test_fused_evaluation_on_a_20k_user_world():
 
 
 # ---- d) BASELINE configs at their own shapes ------------------------------------------------------------------------------------------
-def test_c3_step_at_full_shapes_against_the_cpu_oracle():
-    """BASELINE configs[2] (Onion18 shape): 13,610 items with a 1024-d dense modality, an 853-tag bag and the CSR interactions
-    modality (5,192 columns), C = 512, five hidden layers [512, 512, 512, 256, 256], D = 128, pairwise InfoNCE (tau 0.1),
-    BPR, batch 256 x 11 -> 5,632 rows through the shared network. One fused step against the CPU oracle on the same parameters,
-    batch and modality draw: rec loss, reg loss, every parameter gradient and the BatchNorm running statistics after the step."""
+def c3_step_against_the_cpu_oracle(ds, cfg, deterministic=False):
+    """One fused step of a c3-shaped model (CSR interactions, a tag bag and a dense modality through the shared network, pairwise InfoNCE,
+    BPR) against the CPU oracle on the same parameters, batch of 256 x (1 + negatives) and modality draw: rec loss, reg loss, every
+    parameter gradient and the BatchNorm running statistics after the step. ``deterministic``: the step runs with the mode on and must
+    count no arrival-order launch. -> what the callers go on with (the dataset, the model, its initial state, the entry points called)."""
     from oracle import losses_ref, model_ref
-    ds = S().SyntheticDataset(5192, 13610, 326_000, item_dense={'audio': 1024}, item_tags={'genres': (853, 5)}, seed=0,
-                              n_negative_samples=10)
-    cfg = {'shared_common_dim': 128, 'user': {'feature_name': 'user_embedding', 'embedding_dim': -1},
-           'item': {'features': [{'feature_name': 'interactions'}, {'feature_name': 'genres'}, {'feature_name': 'audio'}],
-                    'single_branch_hidden_layers': [512, 512, 512, 256, 256], 'preference_hidden_layers': [],
-                    'common_modality_dim': 512, 'embedding_regularization_type': 'pairwise_single',
-                    'regularization_temperature': 0.1, 'regularization_weight': 1e-4}}
     torch.manual_seed(42)
     np.random.seed(42)
     net = S().SingleBranchNet(S().SingleBranchNetConfig.from_dict(cfg), ds).to(DEV).train()
@@ -384,7 +377,7 @@ def test_c3_step_at_full_shapes_against_the_cpu_oracle():
         if v.dtype.is_floating_point and 'running' not in k:
             v.requires_grad_(True)
     opt = S().FusedOptimizer(net, 'adamw', lr=1e-3, weight_decay=0.)
-    lossf = S().RecBayesianPersonalizedRankingLoss(n_items=ds.n_items, aggregator='mean', train_neg_strategy='uniform_recbole', neg_train=10)
+    lossf = S().RecBayesianPersonalizedRankingLoss(n_items=ds.n_items, aggregator='mean', train_neg_strategy='uniform_recbole', neg_train=ds.n_negative_samples)
     fused = S().FusedTrainStep(net, lossf, opt)
     seen = []
     def _record(*a, **k):                                      # stands in for the optimizer launch (which also resets the gradient)
@@ -398,13 +391,17 @@ def test_c3_step_at_full_shapes_against_the_cpu_oracle():
     import importlib
     _lib = importlib.import_module(S().ops.__name__.rsplit('.', 1)[0] + '._lib')
     _lib.CALL_LOG = []
-    total, rec, reg = fused.step(u, i, labels, draws)
-    names, _lib.CALL_LOG = [n_ for n_, _ in _lib.CALL_LOG], None
+    prev = S().ops.set_deterministic(True) if deterministic else None
+    S().ops.nondeterministic_launches(reset=True)
+    try:
+        total, rec, reg = fused.step(u, i, labels, draws)
+        if deterministic:
+            assert S().ops.nondeterministic_launches() == 0, 'an arrival-order launch ran in a deterministic c3 step'
+    finally:
+        names, _lib.CALL_LOG = [n_ for n_, _ in _lib.CALL_LOG], None
+        if deterministic:
+            S().ops.set_deterministic(prev)
     after = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
-    # 5,632 rows: the 256 -> 128 output layer on the bf16-split projector kernel, the weight gradients on the bf16-split dW kernel; the
-    # 512- and 256-wide forward / input-gradient products stay on the fp32 ring kernel at this batch (22 x 2 tiles of 256 x 256 do not
-    # fill the chip: ops._wide_ok) and move to the wide bf16-split kernel from ~22k rows on
-    assert 'sbr_gemm_split_proj_f32' in names and names.count('sbr_gemm_tn_f32_slabs') >= 6, names
     pos, order = draws[1]
     mods = np.array(order)[pos].reshape(tuple(i.shape) + (2,))
     ut = {'user_embedding': model_ref.RefTable('categorical', np.arange(ds.n_users), n_categories=ds.n_users)}
@@ -429,6 +426,27 @@ def test_c3_step_at_full_shapes_against_the_cpu_oracle():
     # tolerances); a running mean that absorbs a bias in front of the BatchNorm drifts with that bias and is left out
     _same_running_stats(after, sd, sd_before, rtol=5e-4, atol=1e-6, norm_rtol=5e-4)
     fused.close()
+    return SimpleNamespace(ds=ds, cfg=cfg, net=net, sd0=sd_before, lossf=lossf, names=names, grads=grads, seen=seen[0], scale=sc,
+                           batch=(u, i, labels), mods=mods, rec=rl.detach(), reg=rr.detach())
+
+
+def test_c3_step_at_full_shapes_against_the_cpu_oracle():
+    """BASELINE configs[2] (Onion18 shape): 13,610 items with a 1024-d dense modality, an 853-tag bag and the CSR interactions
+    modality (5,192 columns), C = 512, five hidden layers [512, 512, 512, 256, 256], D = 128, pairwise InfoNCE (tau 0.1),
+    BPR, batch 256 x 11 -> 5,632 rows through the shared network. One fused step against the CPU oracle on the same parameters,
+    batch and modality draw: rec loss, reg loss, every parameter gradient and the BatchNorm running statistics after the step."""
+    ds = S().SyntheticDataset(5192, 13610, 326_000, item_dense={'audio': 1024}, item_tags={'genres': (853, 5)}, seed=0,
+                              n_negative_samples=10)
+    cfg = {'shared_common_dim': 128, 'user': {'feature_name': 'user_embedding', 'embedding_dim': -1},
+           'item': {'features': [{'feature_name': 'interactions'}, {'feature_name': 'genres'}, {'feature_name': 'audio'}],
+                    'single_branch_hidden_layers': [512, 512, 512, 256, 256], 'preference_hidden_layers': [],
+                    'common_modality_dim': 512, 'embedding_regularization_type': 'pairwise_single',
+                    'regularization_temperature': 0.1, 'regularization_weight': 1e-4}}
+    names = c3_step_against_the_cpu_oracle(ds, cfg).names
+    # 5,632 rows: the 256 -> 128 output layer on the bf16-split projector kernel, the weight gradients on the bf16-split dW kernel; the
+    # 512- and 256-wide forward / input-gradient products stay on the fp32 ring kernel at this batch (22 x 2 tiles of 256 x 256 do not
+    # fill the chip: ops._wide_ok) and move to the wide bf16-split kernel from ~22k rows on
+    assert 'sbr_gemm_split_proj_f32' in names and names.count('sbr_gemm_tn_f32_slabs') >= 6, names
 
 
 def _same_running_stats(gpu, ref, before, rtol, **tol):

@@ -194,12 +194,9 @@ def _scatter_cases():
     return cases
 
 
-@pytest.mark.parametrize('n,D,xo,xw,off,use_ii,order', _scatter_cases())
-def test_scatter_add_rows(n, D, xo, xw, off, use_ii, order):
-    """dW[rows[j], :] += dOut[ii(j), :] into a zeroed table: per element |err| <= m u sum|terms| with m the number of sources of that
-    table row (m - 1 float atomic additions in any order; the first lands on +0 exactly). Rows that no source names stay +0 bit for bit.
-    Gradient rows of zeros, of -0.0, with a zero first half and with a zero second half are mixed in (the D = 128 kernel skips all-zero
-    rows by a ballot over both halves). One table row is named by 1,200 sources where n allows."""
+def _scatter_add_rows_run(n, D, xo, xw, off, use_ii, order, fill):
+    """one sbr_scatter_add_rows call of a case of _scatter_cases into a table filled with ``fill`` -> (dW on the host, float64 sum of the
+    sources per table row, sum of their magnitudes, sources per table row)"""
     n_table = 53
     rows = _orders(n, n_table, n * 31 + D, hot=11)[order]
     rng = np.random.default_rng(n + D)
@@ -213,7 +210,7 @@ def test_scatter_add_rows(n, D, xo, xw, off, use_ii, order):
         g[torch.as_tensor(kind == 3), D // 2:] = 0.0                             # zero second half
     ii = rng.permutation(n_src)[:n] if use_ii else None
     dOut = _Buf(n_src, D, D + xo, off, data=g)
-    dW = _Buf(n_table, D, D + xw, off, fill=0.0)
+    dW = _Buf(n_table, D, D + xw, off, fill=fill)
     rows_d, ii_d = _i32(rows), (_i32(ii) if use_ii else None)
     call('sbr_scatter_add_rows', dOut.ptr, dOut.ld, _p(ii_d), _p(rows_d), dW.ptr, dW.ld, n, D, stream())
     got = dW.check_untouched(None, 'scatter_add_rows')
@@ -222,9 +219,35 @@ def test_scatter_add_rows(n, D, xo, xw, off, use_ii, order):
     ref = torch.zeros(n_table, D, dtype=torch.float64).index_add_(0, rt, src.double())
     mag = torch.zeros(n_table, D, dtype=torch.float64).index_add_(0, rt, src.double().abs())
     m = torch.bincount(rt, minlength=n_table).double()[:, None]
+    return got, ref, mag, m
+
+
+@pytest.mark.parametrize('n,D,xo,xw,off,use_ii,order', _scatter_cases())
+def test_scatter_add_rows(n, D, xo, xw, off, use_ii, order):
+    """dW[rows[j], :] += dOut[ii(j), :] into a zeroed table: per element |err| <= m u sum|terms| with m the number of sources of that
+    table row (m - 1 float atomic additions in any order; the first lands on +0 exactly). Rows that no source names stay +0 bit for bit.
+    Gradient rows of zeros, of -0.0, with a zero first half and with a zero second half are mixed in (the D = 128 kernel skips all-zero
+    rows by a ballot over both halves). One table row is named by 1,200 sources where n allows."""
+    got, ref, mag, m = _scatter_add_rows_run(n, D, xo, xw, off, use_ii, order, 0.0)
     _assert_bound(got, ref, m * U32 * mag, f'scatter_add_rows n={n} D={D}')
     unnamed = m[:, 0] == 0
     assert bool((_bits(got[unnamed]) == 0).all()), 'a table row that no source names was written'
+
+
+@pytest.mark.parametrize('n,D,xo,xw,off,use_ii,order', [(4097, 128, 0, 0, 0, True, 'random'),             # rows128 kernel
+                                                        (4095, 128, 0, 0, 0, True, 'random'),             # pow2 kernel at D = 128
+                                                        (1505, 64, 3, 5, 1, True, 'sorted'),              # pow2 kernel, strided
+                                                        (1777, 100, 2, 1, 2, True, 'reversed'),           # grid-stride kernel
+                                                        (5, 64, 0, 0, 0, False, 'random')])               # rows nobody names
+def test_scatter_add_rows_adds_to_what_the_table_holds(n, D, xo, xw, off, use_ii, order):
+    """The same cases, one per kernel, with dW prefilled with 0.5: the kernels ADD (a kernel that stored its sum would pass every test on
+    a zeroed table). m atomic additions onto the existing value: |err| <= (m + 1) u (|dW| + sum|terms|), the bound of
+    test_scatter_add_rows_sorted; rows that no source names keep 0.5 bit for bit."""
+    got, ref, mag, m = _scatter_add_rows_run(n, D, xo, xw, off, use_ii, order, 0.5)
+    _assert_bound(got, ref + 0.5, (m + 1) * U32 * (mag + 0.5), f'scatter_add_rows onto 0.5, n={n} D={D}')
+    unnamed = m[:, 0] == 0
+    assert bool(unnamed.any()) or n != 5
+    _assert_bits(got[unnamed], torch.full_like(got[unnamed], 0.5), 'a table row that no source names was written')
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
