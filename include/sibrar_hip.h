@@ -683,6 +683,31 @@ long sbr_spd_inverse_f32_workspace(int n);
  * division per element. diag: n floats of scratch (the diagonal is read before it is overwritten). New (additive to ABI 4). */
 int sbr_ease_weights_f32(float* P, int n, long ld, float* diag, void* stream);
 
+/* ---- P3alpha on 0/1 data (csrc/p3alpha.hip) --------------------------------------------------------------------------------------
+ * The users x items block of the reference's P^3 (algorithms/graph_algs.py:35-65) is (D_u^-1 X)(D_i^-1 X^T)(D_u^-1 X); its last two
+ * factors are the item-item model W [m, m], dense fp32 rows with leading dimension ld >= m — algorithms/graph_algs.py:35-59 (the
+ * degree sums, `P = D @ A`, `P ** 3`) without the (U + I) x (U + I) matrices. X [n, m] and X^T in the forms sbr_knn_topk takes (binary
+ * CSR, indices ascending and unique); n, m <= 2^24, so every degree converts to fp32 exactly. Degrees are indptr differences;
+ * inv(d) = 1.0f / (float)d, one correctly rounded division. For a row i of [r0, r1) the accumulator of column j starts at +0.0f and
+ * receives inv(d_v) for the users v of item i that hold item j, in ascending v, by plain fp32 additions (one owner, no atomics); the
+ * stored value is acc * inv(d_i): one multiplication, not fused with an addition. A row of an item nobody holds is zeros. Every
+ * element [0, m) of an owned row is written, zeros included; only the rows of [r0, r1) are written. tile_cols: columns per tile of
+ * LDS accumulators (4 bytes each; each of the workgroup's 16 waves owns a strip of ceil(tile / 16) of them and walks the users by
+ * itself, so the order does not depend on the tiling); 0 = min(max(m, 64), 32768), the default of sbr_gram_dense; a request over
+ * 160 KiB of LDS is an error. The same bits on every run, valid in deterministic mode. New (additive to ABI 4). */
+int sbr_p3_walk_dense(const long* indptr, const int* indices, const long* t_indptr, const int* t_indices, int n, int m, int r0, int r1,
+                      int tile_cols, float* W, long ld, void* stream);
+/* out[b, j] = (inv(d_u) * sum_i W[i, j]) ^ alpha for u = rows[b] (rows NULL: u = b; duplicates allowed) and 0 <= j < m — the last
+ * factor D_u^-1 X of P^3 and `P3.power(self.alpha)`, algorithms/graph_algs.py:59-68, one user chunk at a time (the reference's
+ * users x items pred_mtx is never built). X's CSR as above; W [m, m] fp32 with leading dimension ldw; out [B, m] with leading
+ * dimension ldo. A thread owns column j: its accumulator starts at +0.0f and receives W[i, j] over the user's items i in ascending
+ * order by plain fp32 additions, is multiplied once by inv(d_u) and then raised by powf(., alpha); the power is skipped when
+ * alpha == 1.0f (the result is then the product bit for bit) and for a zero, which stays +0. A user without items gives a zero row.
+ * alpha must be positive and finite; m <= 2^24. No atomics: the same bits on every run, valid in deterministic mode. New (additive to
+ * ABI 4). */
+int sbr_p3_score_rows(const long* indptr, const int* indices, const long* rows, long B, const float* W, long ldw, int m, float alpha,
+                      float* out, long ldo, void* stream);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

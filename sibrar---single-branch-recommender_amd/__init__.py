@@ -23,6 +23,7 @@ from .ecf import ECF, ecf_tag_matrix                                            
 from .knn import (ItemKNN, KNNAlgorithm, SimilarityFunctionEnum, SparseMatrixBasedRecommenderAlgorithm,   # noqa: F401
                   UserKNN)
 from .ease import EASE                                                                      # noqa: F401
+from .p3alpha import P3alpha                                                                # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
                      RecSampledSoftmaxLoss, RecommenderSystemLoss, RecommenderSystemLossesEnum)
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
@@ -49,9 +50,10 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
     ops.set_deterministic(deterministic)
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
-# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ease -> class
+# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ease / .p3alpha -> class
 # (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
-              'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ease': EASE}
+              'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ease': EASE,
+              'p3alpha': P3alpha}

@@ -1297,6 +1297,47 @@ def ease_weights_(P: torch.Tensor) -> torch.Tensor:
     return P
 
 
+# ---- P3alpha (csrc/p3alpha.hip) ----------------------------------------------------------------------------------------------------
+def p3_walk_dense(csr, rows=None, tile_cols: int = 0, out=None) -> torch.Tensor:
+    """The item-item matrix ``W = D_i^-1 X^T D_u^-1 X`` of the three-step random walk on a binary resident ``features.DeviceCSR`` X
+    [n, m] as dense float32 [m, m] (algorithms/graph_algs.py:35-59), in the fixed order of ``sbr_p3_walk_dense``: the same bits on every
+    run. ``rows``, ``out`` and ``tile_cols`` as in ``gram_dense``."""
+    if csr.data is not None:
+        raise ValueError('p3_walk_dense: the walk is stated for 0/1 data only (degrees are entry counts); this matrix has values')
+    _need_cuda(csr.indptr, out)
+    n, m = csr.shape
+    r0, r1 = (0, m) if rows is None else (int(rows[0]), int(rows[1]))
+    if out is None:
+        out = (torch.empty if (r0, r1) == (0, m) else torch.zeros)((m, m), device=csr.indptr.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (m, m) or (m > 1 and out.stride(1) != 1):
+        raise ValueError(f'p3_walk_dense: out must be a float32 [{m}, {m}] view with unit column stride, got {out.dtype} {tuple(out.shape)} '
+                         f'strides {out.stride()}')
+    t_indptr, t_indices, _ = csr.transposed()
+    call('sbr_p3_walk_dense', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, int(tile_cols), ptr(out),
+         out.stride(0) if m > 1 else max(m, 1), stream())
+    return out
+
+
+def p3_score_rows(csr, rows: Optional[torch.Tensor], W: torch.Tensor, alpha: float) -> torch.Tensor:
+    """``((D_u^-1 X)[rows] @ W) ** alpha`` as dense float32 rows [len(rows), m] (algorithms/graph_algs.py:59-68) with X a binary resident
+    ``features.DeviceCSR`` [n, m] and ``W`` the contiguous float32 [m, m] result of ``p3_walk_dense``. ``rows=None``: every row. Fixed
+    summation order (ascending item of the user): the same bits on every run."""
+    if csr.data is not None:
+        raise ValueError('p3_score_rows: the walk is stated for 0/1 data only (degrees are entry counts); this matrix has values')
+    n, m = csr.shape
+    if W.dtype != torch.float32 or W.dim() != 2 or tuple(W.shape) != (m, m) or not W.is_contiguous():
+        raise ValueError(f'p3_score_rows: W must be a contiguous float32 [{m}, {m}] matrix, got {W.dtype} {tuple(W.shape)} strides {W.stride()}')
+    if not float(alpha) > 0:
+        raise ValueError(f'p3_score_rows: alpha={alpha!r} must be positive')
+    _need_cuda(csr.indptr, rows, W)
+    if rows is not None:
+        rows = rows.long().contiguous()
+    B = n if rows is None else rows.numel()
+    out = torch.empty(B, m, device=csr.indptr.device, dtype=torch.float32)
+    call('sbr_p3_score_rows', ptr(csr.indptr), ptr(csr.indices), ptr(rows), B, ptr(W), max(m, 1), m, float(alpha), ptr(out), max(m, 1), stream())
+    return out
+
+
 class BiasScoreFn(Function):
     """out[b, n] = base[b, n] + user_bias[u[b]] + item_bias[i[b, n]] + global_bias (sgd_alg.py:186-194, 110-119); every term
     optional (None). Bias tables are 1-D float views of the [n, 1] embedding weights. u None: row b; i None: column n."""
