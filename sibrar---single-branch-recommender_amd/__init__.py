@@ -20,8 +20,8 @@ from .protomf import IProtoMF, PrototypeWrapper, UIProtoMF, UProtoMF            
 from .protomfs import IProtoMFs, UIProtoMFs, UIProtoMFsCombine, UProtoMFs                   # noqa: F401
 from .acf import ACF                                                                        # noqa: F401
 from .ecf import ECF, ecf_tag_matrix                                                        # noqa: F401
-from .knn import (ItemKNN, KNNAlgorithm, SimilarityFunctionEnum, SparseMatrixBasedRecommenderAlgorithm,   # noqa: F401
-                  UserKNN)
+from .matrix_models import ResidentMatrixAlgorithm, SparseMatrixBasedRecommenderAlgorithm   # noqa: F401
+from .knn import ItemKNN, KNNAlgorithm, SimilarityFunctionEnum, UserKNN                     # noqa: F401
 from .ease import EASE                                                                      # noqa: F401
 from .p3alpha import P3alpha                                                                # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401

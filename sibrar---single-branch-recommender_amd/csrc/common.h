@@ -98,6 +98,29 @@ static inline bool sbr_attr_stale(int* slot) {
   return false;
 }
 
+// Host prologue of the kernels that run one workgroup per row and keep a tile of four-byte cells in dynamic LDS (sbr_knn_topk,
+// sbr_gram_dense, sbr_p3_walk_dense), after the entry point's shape and range checks: `tile_cols` columns per tile, 0 for the default (all
+// `cols` of them, clamped to [64, SBR_ROW_TILE_DEFAULT]); `fixed`: the kernel's static LDS bytes. -> the tile width when there is
+// something to launch, with the kernel's dynamic LDS limit raised on this device (`attr_dev`: the kernel's slot of sbr_attr_stale);
+// 0 for an empty row range (`n_rows` == 0), before the operands are looked at; otherwise minus the error code, with the message set.
+#define SBR_ROW_TILE_DEFAULT 32768     // four-byte cells of one tile: 128 KiB
+#define SBR_ROW_TILE_LDS_MAX 163840    // 160 KiB per CU, all of which one workgroup may use
+static inline int sbr_row_tile(const char* who, const void* kernel, int* attr_dev, int cols, int tile_cols, long fixed, int n_rows,
+                               bool operands) {
+  if (tile_cols < 0) { sbr_set_error("%s: negative tile_cols %d", who, tile_cols); return -SBR_ERR_ARG; }
+  const int tw = tile_cols > 0 ? tile_cols : (cols < SBR_ROW_TILE_DEFAULT ? (cols > 64 ? cols : 64) : SBR_ROW_TILE_DEFAULT);
+  const long lds = 4L * tw + fixed;
+  if (lds > SBR_ROW_TILE_LDS_MAX) { sbr_set_error("%s: tile_cols=%d asks for %ld bytes of LDS, over 160 KiB", who, tw, lds); return -SBR_ERR_ARG; }
+  if (n_rows == 0) return 0;
+  if (!operands) { sbr_set_error("%s: null operand", who); return -SBR_ERR_ARG; }
+  if (sbr_attr_stale(attr_dev) &&
+      hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SBR_ROW_TILE_LDS_MAX - fixed)) != hipSuccess) {
+    *attr_dev = -1;
+    sbr_set_error("%s: cannot raise the dynamic LDS limit", who);
+    return -SBR_ERR_HIP;
+  }
+  return tw;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Column reductions over an [n, D] row-major matrix with D % 4 == 0 (column sums of bias gradients, BatchNorm statistics).

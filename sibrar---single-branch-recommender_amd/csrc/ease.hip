@@ -12,8 +12,6 @@ typedef float ease_f32x16 __attribute__((ext_vector_type(16)));
 // ---- Gram matrix ------------------------------------------------------------------------------------------------------------------
 #define GRAM_THREADS 1024
 #define GRAM_WAVES (GRAM_THREADS / 64)
-#define GRAM_TILE_DEFAULT 32768      // as sbr_knn_topk: u32 counters of one tile, 128 KiB
-#define GRAM_LDS_MAX 163840          // 160 KiB per CU
 #define GRAM_N_MAX (1 << 24)         // a count is at most the number of rows of X: converted to fp32 exactly
 
 // One workgroup per row i of G. (indptr, indices) is X^T (row i: the users of item i), (t_indptr, t_indices) is X (a user's items):
@@ -46,23 +44,13 @@ extern "C" int sbr_gram_dense(const long* indptr, const int* indices, const long
               "than 2^24 entries has no exact fp32 count", n, m);
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= m, "sbr_gram_dense: row range [%d, %d) outside [0, %d]", r0, r1, m);
   SBR_REQUIRE(ld >= m, "sbr_gram_dense: leading dimension %ld below m=%d", ld, m);
-  SBR_REQUIRE(tile_cols >= 0, "sbr_gram_dense: negative tile_cols %d", tile_cols);
-  const int tw = tile_cols > 0 ? tile_cols : (m < GRAM_TILE_DEFAULT ? (m > 64 ? m : 64) : GRAM_TILE_DEFAULT);
-  const long lds = 4L * tw;
-  SBR_REQUIRE(lds <= GRAM_LDS_MAX, "sbr_gram_dense: tile_cols=%d asks for %ld bytes of LDS, over 160 KiB", tw, lds);
-  if (r1 == r0) return SBR_OK;
-  SBR_REQUIRE(indptr && indices && t_indptr && t_indices && G, "sbr_gram_dense: null operand");
   static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev)) {
-    if (hipFuncSetAttribute((const void*)gram_dense_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GRAM_LDS_MAX) != hipSuccess) {
-      attr_dev = -1;
-      sbr_set_error("sbr_gram_dense: cannot raise the dynamic LDS limit");
-      return SBR_ERR_HIP;
-    }
-  }
+  const int tw = sbr_row_tile("sbr_gram_dense", (const void*)gram_dense_kernel, &attr_dev, m, tile_cols, 0, r1 - r0,
+                              indptr && indices && t_indptr && t_indices && G);
+  if (tw <= 0) return -tw;
   // the kernel owns X^T's row i: the roles of the matrix and its transpose are those of sbr_knn_topk on X^T
-  gram_dense_kernel<<<(unsigned)(r1 - r0), GRAM_THREADS, (size_t)lds, (hipStream_t)stream>>>(t_indptr, t_indices, indptr, indices, m, r0,
-                                                                                      diag_add, tw, G, ld);
+  gram_dense_kernel<<<(unsigned)(r1 - r0), GRAM_THREADS, 4 * (size_t)tw, (hipStream_t)stream>>>(t_indptr, t_indices, indptr, indices, m, r0,
+                                                                                         diag_add, tw, G, ld);
   SBR_CHECK_LAUNCH("sbr_gram_dense");
   return SBR_OK;
 }

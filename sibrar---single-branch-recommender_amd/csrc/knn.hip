@@ -11,8 +11,6 @@
 #define KNN_THREADS 1024
 #define KNN_WAVES (KNN_THREADS / 64)
 #define KNN_K_MAX 256                // the limit of sbr_topk_rows
-#define KNN_TILE_DEFAULT 32768       // u32 counters of one tile: 128 KiB
-#define KNN_LDS_MAX 163840           // 160 KiB per CU, all of which one workgroup may use
 #define KNN_M_MAX (1 << 24)          // counts and row sizes are converted to fp32 exactly
 
 #define KNN_COSINE 0
@@ -239,25 +237,15 @@ extern "C" int sbr_knn_topk(const long* indptr, const int* indices, const long* 
   SBR_REQUIRE(alpha >= 0.f && beta >= 0.f, "sbr_knn_topk: negative alpha / beta (%g, %g)", (double)alpha, (double)beta);
   SBR_REQUIRE(n >= 0 && m >= 0 && m <= KNN_M_MAX, "sbr_knn_topk: shape [%d, %d] outside [0, 2^31) x [0, 2^24]", n, m);
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= n, "sbr_knn_topk: row range [%d, %d) outside [0, %d]", r0, r1, n);
-  SBR_REQUIRE(tile_cols >= 0, "sbr_knn_topk: negative tile_cols %d", tile_cols);
   const long fixed = 2L * KNN_K_MAX * 8 + 256 * 4 + 64;         // the kernel's static LDS: two lists, the histogram, the scalars
-  int tw = tile_cols > 0 ? tile_cols : (n < KNN_TILE_DEFAULT ? (n > 64 ? n : 64) : KNN_TILE_DEFAULT);
-  const long lds = 4L * tw;
-  SBR_REQUIRE(lds + fixed <= KNN_LDS_MAX, "sbr_knn_topk: tile_cols=%d asks for %ld bytes of LDS, over 160 KiB", tw, lds + fixed);
-  if (r1 == r0) return SBR_OK;
-  SBR_REQUIRE(indptr && indices && t_indptr && t_indices && nbr_idx && nbr_val && nbr_len, "sbr_knn_topk: null operand");
   static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev)) {
-    if (hipFuncSetAttribute((const void*)knn_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KNN_LDS_MAX - fixed)) != hipSuccess) {
-      attr_dev = -1;
-      sbr_set_error("sbr_knn_topk: cannot raise the dynamic LDS limit");
-      return SBR_ERR_HIP;
-    }
-  }
+  const int tw = sbr_row_tile("sbr_knn_topk", (const void*)knn_topk_kernel, &attr_dev, n, tile_cols, fixed, r1 - r0,
+                              indptr && indices && t_indptr && t_indices && nbr_idx && nbr_val && nbr_len);
+  if (tw <= 0) return -tw;
   int kpad = 2;
   while (kpad < k) kpad <<= 1;
-  knn_topk_kernel<<<(unsigned)(r1 - r0), KNN_THREADS, (size_t)lds, (hipStream_t)stream>>>(indptr, indices, t_indptr, t_indices, n, r0, sim, alpha,
-                                                                                   beta, shrinkage, k, kpad, tw, nbr_idx, nbr_val, nbr_len);
+  knn_topk_kernel<<<(unsigned)(r1 - r0), KNN_THREADS, 4 * (size_t)tw, (hipStream_t)stream>>>(indptr, indices, t_indptr, t_indices, n, r0, sim,
+                                                                                      alpha, beta, shrinkage, k, kpad, tw, nbr_idx, nbr_val, nbr_len);
   SBR_CHECK_LAUNCH("sbr_knn_topk");
   return SBR_OK;
 }

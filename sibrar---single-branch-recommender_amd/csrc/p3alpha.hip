@@ -9,8 +9,6 @@
 
 #define P3_THREADS 1024
 #define P3_WAVES (P3_THREADS / 64)
-#define P3_TILE_DEFAULT 32768        // as sbr_gram_dense: fp32 accumulators of one tile, 128 KiB
-#define P3_LDS_MAX 163840            // 160 KiB per CU
 #define P3_DIM_MAX (1 << 24)         // a degree is at most a dimension of X: converted to fp32 exactly
 
 // inv(d) of the header: one correctly rounded fp32 division of an exactly converted degree
@@ -84,23 +82,13 @@ extern "C" int sbr_p3_walk_dense(const long* indptr, const int* indices, const l
               "degree over 2^24 has no exact fp32 form", n, m);
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= m, "sbr_p3_walk_dense: row range [%d, %d) outside [0, %d]", r0, r1, m);
   SBR_REQUIRE(ld >= m, "sbr_p3_walk_dense: leading dimension %ld below m=%d", ld, m);
-  SBR_REQUIRE(tile_cols >= 0, "sbr_p3_walk_dense: negative tile_cols %d", tile_cols);
-  const int tw = tile_cols > 0 ? tile_cols : (m < P3_TILE_DEFAULT ? (m > 64 ? m : 64) : P3_TILE_DEFAULT);
-  const long lds = 4L * tw;
-  SBR_REQUIRE(lds <= P3_LDS_MAX, "sbr_p3_walk_dense: tile_cols=%d asks for %ld bytes of LDS, over 160 KiB", tw, lds);
-  if (r1 == r0) return SBR_OK;
-  SBR_REQUIRE(indptr && indices && t_indptr && t_indices && W, "sbr_p3_walk_dense: null operand");
   static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev)) {
-    if (hipFuncSetAttribute((const void*)p3_walk_dense_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, P3_LDS_MAX) != hipSuccess) {
-      attr_dev = -1;
-      sbr_set_error("sbr_p3_walk_dense: cannot raise the dynamic LDS limit");
-      return SBR_ERR_HIP;
-    }
-  }
+  const int tw = sbr_row_tile("sbr_p3_walk_dense", (const void*)p3_walk_dense_kernel, &attr_dev, m, tile_cols, 0, r1 - r0,
+                              indptr && indices && t_indptr && t_indices && W);
+  if (tw <= 0) return -tw;
   const int strip = (tw + P3_WAVES - 1) / P3_WAVES;
-  p3_walk_dense_kernel<<<(unsigned)(r1 - r0), P3_THREADS, (size_t)lds, (hipStream_t)stream>>>(indptr, indices, t_indptr, t_indices, m, r0, tw,
-                                                                                        strip, W, ld);
+  p3_walk_dense_kernel<<<(unsigned)(r1 - r0), P3_THREADS, 4 * (size_t)tw, (hipStream_t)stream>>>(indptr, indices, t_indptr, t_indices, m, r0, tw,
+                                                                                           strip, W, ld);
   SBR_CHECK_LAUNCH("sbr_p3_walk_dense");
   return SBR_OK;
 }

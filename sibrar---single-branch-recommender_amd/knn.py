@@ -17,8 +17,7 @@ leaves); ``model.npz`` holds the lists, not ``pred_mtx``, so a loaded model need
 from __future__ import annotations
 
 import logging
-import os
-from abc import ABC, abstractmethod
+from abc import ABC
 from enum import Enum
 
 import numpy as np
@@ -27,6 +26,7 @@ import torch
 
 from . import ops
 from .features import DeviceCSR
+from .matrix_models import ResidentMatrixAlgorithm, SparseMatrixBasedRecommenderAlgorithm, _binary_csr      # noqa: F401
 
 
 class SimilarityFunctionEnum(Enum):
@@ -37,53 +37,6 @@ class SimilarityFunctionEnum(Enum):
     asymmetric_cosine = 'asymmetric_cosine'
     tversky = 'tversky'
     sorensen_dice = 'sorensen_dice'
-
-
-class SparseMatrixBasedRecommenderAlgorithm(ABC):
-    """algorithms/base_classes.py:54-84 — algorithms trained from the sparse user x item matrix by ``fit(matrix)``; no Trainer. ``eval()`` /
-    ``train()`` exist so that the evaluation loop's ``alg.eval()`` works; there is no mode to switch."""
-
-    def __init__(self):
-        self.name = 'SparseMatrixBasedRecommenderAlgorithm'
-        logging.info(f'Built {self.name} module')
-
-    @abstractmethod
-    def fit(self, matrix: sp.spmatrix, **kwargs):
-        """:param matrix: user x item sparse matrix"""
-
-    @abstractmethod
-    def predict(self, u_idxs: torch.Tensor, i_idxs: torch.Tensor) -> torch.Tensor:
-        """u_idxs [batch_size], i_idxs [batch_size, n] -> scores [batch_size, n]"""
-
-    @abstractmethod
-    def save_model_to_path(self, path: str):
-        pass
-
-    @abstractmethod
-    def load_model_from_path(self, path: str):
-        pass
-
-    @staticmethod
-    @abstractmethod
-    def build_from_conf(conf: dict, dataset):
-        pass
-
-    def eval(self):
-        return self
-
-    def train(self, mode: bool = True):
-        return self
-
-
-def _binary_csr(matrix) -> sp.csr_matrix:
-    m = sp.csr_matrix(matrix).copy()
-    m.sum_duplicates()
-    m.eliminate_zeros()
-    m.sort_indices()
-    if m.nnz and bool((m.data != 1).any()):
-        raise ValueError('KNN similarities are stated for 0/1 interaction data only (utilities/similarities.py:11-15): the matrix has '
-                         'entries other than 1 (after sum_duplicates / eliminate_zeros)')
-    return m
 
 
 def _lists_to_csr(idx: torch.Tensor, val: torch.Tensor, length: torch.Tensor, transpose: bool):
@@ -100,12 +53,14 @@ def _lists_to_csr(idx: torch.Tensor, val: torch.Tensor, length: torch.Tensor, tr
     return indptr, cols[order].to(torch.int32).contiguous(), data[order].contiguous(), (n, n)
 
 
-class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm, ABC):
+class KNNAlgorithm(ResidentMatrixAlgorithm, ABC):
     """algorithms/knn_algs.py:13-76. ``kwargs``: ``alpha`` (asymmetric_cosine, tversky), ``beta`` (tversky), ``device``."""
     ENTITY = None            # 'user' | 'item': whose rows are compared
+    KEY, WHAT, STORES = 'nbr_idx', 'neighbour lists', 'the neighbour lists'
+    BINARY_ONLY = 'KNN similarities are stated for 0/1 interaction data only (utilities/similarities.py:11-15)'
 
     def __init__(self, sim_func_enum: SimilarityFunctionEnum = SimilarityFunctionEnum.cosine, k: int = 100, shrinkage: float = .0, **kwargs):
-        super().__init__()
+        super().__init__(kwargs.get('device'))
         if isinstance(sim_func_enum, str):
             sim_func_enum = SimilarityFunctionEnum[sim_func_enum]
         if sim_func_enum == SimilarityFunctionEnum.dense_cosine:
@@ -123,34 +78,24 @@ class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm, ABC):
             self.beta = float(kwargs['beta'])
         self.k = int(k)
         self.shrinkage = float(shrinkage)
-        self.device = torch.device(kwargs.get('device') or 'cuda')
         self.nbr_idx = self.nbr_val = self.nbr_len = None      # the model: int32 [n, k], float32 [n, k], int32 [n]
-        self.n_users = self.n_items = None
-        self._entity = None                                     # DeviceCSR of the compared rows (users x items, or items x users)
         self._operands = None                                   # (X, Y) of ops.csr_rows_times_csr
         self.name = 'KNNAlgorithm'
         logging.info(f'Built {self.name} module \n- sim_func: {self.sim_func_enum.name} \n- k: {self.k} \n- shrinkage: {self.shrinkage} \n')
 
     def to(self, device):
-        self.device = torch.device(device)
         self._operands = None
-        if self._entity is not None:
-            self._entity = self._entity.to(self.device)
-        return self
+        return super().to(device)
 
-    # ---- fitting ----------------------------------------------------------------------------------------------------------------
-    def attach(self, matrix: sp.spmatrix):
-        """Make the user x item matrix resident without fitting: what a model loaded from ``model.npz`` needs before it can score."""
-        m = _binary_csr(matrix)
-        self.n_users, self.n_items = m.shape
-        self._entity = DeviceCSR(m if self.ENTITY == 'user' else sp.csr_matrix(m.T)).to(self.device)
+    def _resident(self, m):
+        """the compared rows: users x items, or items x users"""
         self._operands = None
-        return self
+        return DeviceCSR(m if self.ENTITY == 'user' else sp.csr_matrix(m.T))
 
     def fit(self, matrix: sp.spmatrix, **kwargs):
         """:param matrix: user x item sparse matrix"""
         self.attach(matrix)
-        self.nbr_idx, self.nbr_val, self.nbr_len = ops.knn_topk(self._entity, self.sim_func_enum.name, self.k, self.shrinkage, self.alpha,
+        self.nbr_idx, self.nbr_val, self.nbr_len = ops.knn_topk(self._matrix, self.sim_func_enum.name, self.k, self.shrinkage, self.alpha,
                                                                 self.beta)
         return self
 
@@ -159,74 +104,38 @@ class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm, ABC):
         self._need_fit()
         return _lists_to_csr(self.nbr_idx.to(self.device), self.nbr_val.to(self.device), self.nbr_len.to(self.device), False)
 
-    def _need_fit(self):
-        if self.nbr_idx is None:
-            raise RuntimeError(f'{self.name}: no neighbour lists, run fit(matrix) or load_model_from_path(path)')
-
     def _ops(self):
+        """(X, Y) of ``ops.csr_rows_times_csr``, of a fitted model with its matrix resident"""
         if self._operands is None:
-            self._need_fit()
-            if self._entity is None:
-                raise RuntimeError(f'{self.name}: the lists were loaded from model.npz, which does not hold the interactions: call '
-                                   f'attach(matrix) with the user x item matrix first')
             n = self.n_users if self.ENTITY == 'user' else self.n_items
             if tuple(self.nbr_idx.shape) != (n, self.k) or int(self.nbr_len.numel()) != n:
                 raise ValueError(f'{self.name}: lists of shape {tuple(self.nbr_idx.shape)} do not fit the {n} {self.ENTITY}s of the matrix')
             lists = (self.nbr_idx.to(self.device), self.nbr_val.to(self.device), self.nbr_len.to(self.device))
             if self.ENTITY == 'user':           # sim_mtx @ matrix
-                self._operands = (_lists_to_csr(*lists, False), self._entity)
-            else:                               # matrix @ sim_mtx.T; the entity matrix is items x users: its transpose is the matrix
-                t_indptr, t_indices, _ = self._entity.transposed()
+                self._operands = (_lists_to_csr(*lists, False), self._matrix)
+            else:                               # matrix @ sim_mtx.T; the resident matrix is items x users: its transpose is the matrix
+                t_indptr, t_indices, _ = self._matrix.transposed()
                 self._operands = ((t_indptr, t_indices, None, (self.n_users, self.n_items)), _lists_to_csr(*lists, True))
         return self._operands
 
-    # ---- scoring: the hooks of evaluate_recommender_algorithm ----------------------------------------------------------------------------
-    def get_user_representations(self, u_idxs: torch.Tensor):
-        return torch.as_tensor(u_idxs).long().to(self.device)
-
-    def get_item_representations(self, i_idxs: torch.Tensor):
-        return (torch.as_tensor(i_idxs).long().to(self.device),)
-
-    def combine_user_item_representations(self, u_repr, i_repr) -> torch.Tensor:
-        """-> float32 [len(u_repr), len(items)]: the users' score rows, restricted to the named item columns"""
+    def _score_rows(self, u):
         x, y = self._ops()
-        rows = ops.csr_rows_times_csr(x, u_repr, y)
-        items = i_repr[0]
-        if items.dim() == 1 and items.numel() == self.n_items and bool((items == torch.arange(self.n_items, device=items.device)).all()):
-            return rows
-        return rows[:, items] if items.dim() == 1 else torch.gather(rows, 1, items)
+        return ops.csr_rows_times_csr(x, u, y)
 
-    @torch.no_grad()
-    def predict(self, u_idxs: torch.Tensor, i_idxs: torch.Tensor) -> torch.Tensor:
-        """algorithms/base_classes.py:73-84: ``pred_mtx[u_idxs[:, None], i_idxs]``"""
-        u = self.get_user_representations(u_idxs)
-        x, y = self._ops()
-        return torch.gather(ops.csr_rows_times_csr(x, u, y), 1, torch.as_tensor(i_idxs).long().to(self.device))
+    def _npz_fields(self):
+        return dict(nbr_idx=self.nbr_idx.cpu().numpy(), nbr_val=self.nbr_val.cpu().numpy(), nbr_len=self.nbr_len.cpu().numpy(),
+                    k=np.array(self.k), sim_func=np.array(self.sim_func_enum.name))
 
-    # ---- persistence -------------------------------------------------------------------------------------------------------------------
-    def save_model_to_path(self, path: str):
-        self._need_fit()
-        np.savez(os.path.join(path, 'model.npz'), nbr_idx=self.nbr_idx.cpu().numpy(), nbr_val=self.nbr_val.cpu().numpy(),
-                 nbr_len=self.nbr_len.cpu().numpy(), name=np.array(self.name), k=np.array(self.k), sim_func=np.array(self.sim_func_enum.name))
-        print('Model Saved')
-
-    def load_model_from_path(self, path: str, matrix: sp.spmatrix = None):
-        with np.load(os.path.join(path, 'model.npz'), allow_pickle=False) as f:
-            if 'pred_mtx' in f.files or 'nbr_idx' not in f.files:
-                raise ValueError(f'{os.path.join(path, "model.npz")} is not a model of this package (it holds {f.files}): the reference '
-                                 f'stores its pickled prediction matrix `pred_mtx`, this package the neighbour lists; fit the model again')
-            name, k, sim = str(f['name']), int(f['k']), str(f['sim_func'])
-            if (name, k, sim) != (self.name, self.k, self.sim_func_enum.name):
-                raise ValueError(f'model.npz holds a {name} (k={k}, {sim}), this model is a {self.name} (k={self.k}, {self.sim_func_enum.name})')
-            idx, val, length = f['nbr_idx'], f['nbr_val'], f['nbr_len']
+    def _read_npz(self, f):
+        k, sim = int(f['k']), str(f['sim_func'])
+        if (k, sim) != (self.k, self.sim_func_enum.name):
+            raise ValueError(f'model.npz holds a {self.name} (k={k}, {sim}), this model is a {self.name} (k={self.k}, {self.sim_func_enum.name})')
+        idx, val, length = f['nbr_idx'], f['nbr_val'], f['nbr_len']
         if idx.shape != val.shape or idx.ndim != 2 or idx.shape[1] != k or length.shape != (idx.shape[0],):
             raise ValueError(f'model.npz: inconsistent list shapes {idx.shape}, {val.shape}, {length.shape}')
         self.nbr_idx, self.nbr_val = torch.from_numpy(idx.astype(np.int32)), torch.from_numpy(val.astype(np.float32))
         self.nbr_len = torch.from_numpy(length.astype(np.int32))
         self._operands = None
-        if matrix is not None:
-            self.attach(matrix)
-        print('Model Loaded')
 
     @staticmethod
     def build_from_conf(conf: dict, dataset=None):

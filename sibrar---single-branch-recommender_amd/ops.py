@@ -1234,6 +1234,19 @@ def csr_rows_times_csr(x, rows: Optional[torch.Tensor], y, tile_cols: int = 0) -
 _SPD_WS = {}
 
 
+def _item_item_out(who, csr, rows, out):
+    """``(r0, r1, out, ld)`` of a dense float32 [m, m] result over the items of ``csr``: the row range ``rows`` (None: every row), ``out``
+    checked, or allocated (zeroed where the range leaves rows unwritten), and its leading dimension"""
+    m = csr.shape[1]
+    r0, r1 = (0, m) if rows is None else (int(rows[0]), int(rows[1]))
+    if out is None:
+        out = (torch.empty if (r0, r1) == (0, m) else torch.zeros)((m, m), device=csr.indptr.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (m, m) or (m > 1 and out.stride(1) != 1):
+        raise ValueError(f'{who}: out must be a float32 [{m}, {m}] view with unit column stride, got {out.dtype} {tuple(out.shape)} '
+                         f'strides {out.stride()}')
+    return r0, r1, out, out.stride(0) if m > 1 else max(m, 1)
+
+
 def gram_dense(csr, diag_add: float = 0., rows=None, tile_cols: int = 0, out=None) -> torch.Tensor:
     """``X^T X + diag_add * I`` of a binary resident ``features.DeviceCSR`` X [n, m] as dense float32 [m, m], counted exactly
     (algorithms/linear_algs.py:150-153). ``rows=(r0, r1)`` computes that row range only (the other rows of a new result are zero, those
@@ -1242,15 +1255,10 @@ def gram_dense(csr, diag_add: float = 0., rows=None, tile_cols: int = 0, out=Non
     if csr.data is not None:
         raise ValueError('gram_dense: the counts are integers for 0/1 data only; this matrix has values')
     n, m = csr.shape
-    r0, r1 = (0, m) if rows is None else (int(rows[0]), int(rows[1]))
-    if out is None:
-        out = (torch.empty if (r0, r1) == (0, m) else torch.zeros)((m, m), device=csr.indptr.device, dtype=torch.float32)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (m, m) or (m > 1 and out.stride(1) != 1):
-        raise ValueError(f'gram_dense: out must be a float32 [{m}, {m}] view with unit column stride, got {out.dtype} {tuple(out.shape)} '
-                         f'strides {out.stride()}')
+    r0, r1, out, ld = _item_item_out('gram_dense', csr, rows, out)
     t_indptr, t_indices, _ = csr.transposed()
     call('sbr_gram_dense', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, float(diag_add), int(tile_cols),
-         ptr(out), out.stride(0) if m > 1 else max(m, 1), stream())
+         ptr(out), ld, stream())
     return out
 
 
@@ -1306,15 +1314,10 @@ def p3_walk_dense(csr, rows=None, tile_cols: int = 0, out=None) -> torch.Tensor:
         raise ValueError('p3_walk_dense: the walk is stated for 0/1 data only (degrees are entry counts); this matrix has values')
     _need_cuda(csr.indptr, out)
     n, m = csr.shape
-    r0, r1 = (0, m) if rows is None else (int(rows[0]), int(rows[1]))
-    if out is None:
-        out = (torch.empty if (r0, r1) == (0, m) else torch.zeros)((m, m), device=csr.indptr.device, dtype=torch.float32)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (m, m) or (m > 1 and out.stride(1) != 1):
-        raise ValueError(f'p3_walk_dense: out must be a float32 [{m}, {m}] view with unit column stride, got {out.dtype} {tuple(out.shape)} '
-                         f'strides {out.stride()}')
+    r0, r1, out, ld = _item_item_out('p3_walk_dense', csr, rows, out)
     t_indptr, t_indices, _ = csr.transposed()
-    call('sbr_p3_walk_dense', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, int(tile_cols), ptr(out),
-         out.stride(0) if m > 1 else max(m, 1), stream())
+    call('sbr_p3_walk_dense', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, int(tile_cols), ptr(out), ld,
+         stream())
     return out
 
 

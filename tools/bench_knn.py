@@ -42,7 +42,7 @@ def median_ms(fn, reps):
 for alg in ('uknn', 'iknn'):
     m = S.ALGORITHMS[alg](S.SimilarityFunctionEnum.cosine, k=100).to(dev)
     m.attach(inter)
-    fit = median_ms(lambda: S.ops.knn_topk(m._entity, 'cosine', 100), args.reps)
+    fit = median_ms(lambda: S.ops.knn_topk(m._matrix, 'cosine', 100), args.reps)
     m.fit(inter)
     x, y = m._ops()
     users = torch.randperm(n_users, generator=torch.Generator().manual_seed(1))[:4096].to(dev)
