@@ -568,6 +568,11 @@ int sbr_rank_metrics(const int* topk_idx, int kmax, const long* u_idx, const lon
  * list with an error). Output sorted by (score desc, item
  * index asc); indices are global (item_offset + column). u_idx: exclusion-CSR row of every scored row (NULL: identity).
  * excl_nnz: number of entries of `excl_indices` (an upper bound of the exclusions of the scored rows).
+ * PRECONDITION: the lengths of the scored rows' parts inside [item_offset, item_offset + I), summed over all Bu scored rows, must not
+ * exceed excl_nnz; a row that u_idx names more than once counts once per repetition. The event buffer is sized from excl_nnz: past
+ * the bound a user group's slice of the stream is left unwritten and the kernel reads events that were never built. The CSR's total
+ * (what the Python layer `ops` passes) satisfies it whenever the entries of u_idx are distinct; a user list with repetitions may
+ * exceed it, and such a caller has to pass a CSR (or an excl_nnz together with an event buffer) sized for the repeated rows.
  * Exclusions reach the kernel as an EVENT STREAM built from the CSR rows (csrc/score_topk_f16_n.hip) in the caller-owned buffer
  * `events` (sbr_score_topk_f16_events_bytes(Bu, excl_nnz) bytes; NULL without exclusions): build_events != 0 builds it first (three
  * small launches), 0 means the buffer holds the stream an earlier call with the same (u_idx, CSR, item_offset, I, D) built — the

@@ -1577,6 +1577,10 @@ def _score_topk_fused(entry: str, route: str, u: torch.Tensor, i_op: torch.Tenso
     val = torch.empty(Bu, k, device=u.device, dtype=torch.float32)
     idx = torch.empty(Bu, k, device=u.device, dtype=torch.int32)
     nnz = 0 if excl_indices is None else int(excl_indices.numel())
+    if nnz == 0:
+        # an empty CSR masks nothing: pass none (its empty index tensor has a NULL data pointer, which the C entries refuse next to a
+        # non-NULL indptr: "exclusion CSR must be given whole or not at all")
+        excl_indptr = excl_indices = None
     ws = torch.empty(max(int(getattr(lib(), entry + '_workspace')(Bu, I, k)), 8), device=u.device, dtype=torch.uint8)
     ev, build = _scorer_events(exclusions, (route, Bu, I, D, int(item_offset), nnz), Bu, nnz, u.device)
     _timed((entry[len('sbr_'):], Bu, I, D, k),
