@@ -713,6 +713,39 @@ int sbr_p3_walk_dense(const long* indptr, const int* indices, const long* t_indp
 int sbr_p3_score_rows(const long* indptr, const int* indices, const long* rows, long B, const float* W, long ldw, int m, float alpha,
                       float* out, long ldo, void* stream);
 
+/* ---- implicit-feedback ALS (csrc/als.hip) ------------------------------------------------------------------------------------------
+ * One half-sweep of algorithms/mf_algs.py:69-142 (Hu, Koren and Volinsky 2008) recomputes every row of one factor matrix X from the
+ * other one, Y [n_y, f] fp32 with leading dimension ldy, 1 <= f <= 128. The confidence of an observed entry is c = alpha * r, of every
+ * other entry 1; the preference is 1 for observed entries and 0 elsewhere. For row r with observed columns S:
+ *   A_r = (Y^T Y + reg I) + sum_{i in S} (alpha r_i - 1) y_i y_i^T,   b_r = sum_{i in S} alpha r_i y_i,   x_r = A_r^-1 b_r.
+ *
+ * G = Y^T Y + reg I as fp32 [f, f] with leading dimension ldg. Rows of Y are taken in slabs of 512: within a slab G[i][j] starts at
+ * +0 and receives fmaf(Y[k][i], Y[k][j], .) in ascending k; the slabs' partial sums are then added in ascending slab order from +0 by
+ * plain fp32 additions and reg is added to the diagonal last (one addition). G is symmetric bit for bit. No float atomics: the same
+ * bits on every run, valid in deterministic mode, whatever the deterministic switch says. Only the f x f view of G is written.
+ * workspace: sbr_als_gram_f32_workspace(n_y, f) bytes (the slabs' partial sums). reg must be positive and finite. n_y = 0 gives
+ * reg I. New (additive to ABI 4). */
+int sbr_als_gram_f32(const float* Y, long n_y, long ldy, int f, float reg, float* G, long ldg, void* workspace, long workspace_bytes,
+                     void* stream);
+/* bytes of `workspace` for sbr_als_gram_f32: ceil(n_y / 512) partial sums [f, f] of fp32. New (additive to ABI 4). */
+long sbr_als_gram_f32_workspace(long n_y, int f);
+/* X[r, 0:f] = A_r^-1 b_r for the rows r of [r0, r1) of a CSR matrix (indptr int64, indices int32 ascending and unique within a row and
+ * below n_y, data fp32 or NULL = all ones). G: the contiguous fp32 [f, f] result of sbr_als_gram_f32 on the same Y. One workgroup owns
+ * a row. c_i = alpha * r_i (one fp32 product). An element A_r[i][j], j <= i, starts at G[i][j] and receives
+ * fmaf((c_k - 1) * y_k[i], y_k[j], .) over the row's entries k in ascending CSR order; b_r[i] starts at +0 and receives
+ * fmaf(c_k, y_k[i], .) in the same order (each element has one owner; the rows of Y are staged through LDS 24 at a time). A_r, with
+ * b_r as one more row, is then factored in LDS by an unpivoted Cholesky by columns: for p ascending, q = A[p][p] - sum_{k<p} L[p][k]^2
+ * and s_i = A[i][p] - sum_{k<p} L[i][k] L[p][k] as fmaf chains in ascending k, L[p][p] = sqrtf(q), L[i][p] = s_i / L[p][p] (the row of
+ * b_r gives z = L^-1 b_r on the way); L^T x = z follows by columns, p descending: x[p] = z[p] / L[p][p], z[i] = fmaf(-L[p][i], x[p],
+ * z[i]) for i < p. An empty row writes +0.0f in every one of its f elements. Only X[r0:r1, 0:f] is written (leading dimension ldx).
+ * info: one device int32, zero on entry; a row that meets a pivot q that is <= 0 or not finite sets it to 1 + r unless it already holds
+ * a smaller non-zero value, so that it names the first such row (an error return, not a fault: the kernel finishes; that row's output
+ * is unspecified). The bits of a row do not depend on [r0, r1) or on the run; valid in deterministic mode (integer atomics on info
+ * only). alpha must be positive and finite, ldx >= f, ldy >= f, 0 <= r0 <= r1 <= 2^31 - 2; an empty range returns at once.
+ * New (additive to ABI 4). */
+int sbr_als_solve_rows_f32(const long* indptr, const int* indices, const float* data, long r0, long r1, const float* Y, long n_y, long ldy,
+                           int f, const float* G, float alpha, float* X, long ldx, int* info, void* stream);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

@@ -7,6 +7,9 @@ skeleton are written here once. ``model.npz`` holds the model, not ``pred_mtx``,
 (``attach``). ``DenseItemModel`` adds what the models share whose model is one dense float32 [n_items, n_items] tensor (EASE, P3alpha).
 
 A model writes: its constructor, ``fit``, ``_score_rows``, the class-level names below and ``build_from_conf``.
+
+``FactorModel`` is the other kind: the model is two factor matrices (ALS), nothing stays resident after ``fit``, and the hooks hand out
+plain tensors.
 """
 from __future__ import annotations
 
@@ -161,6 +164,75 @@ class ResidentMatrixAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
             self._read_npz(f)
         if matrix is not None:
             self.attach(matrix)
+        print('Model Loaded')
+
+
+class FactorModel(SparseMatrixBasedRecommenderAlgorithm):
+    """The model is two float32 factor matrices, ``users_factors`` [n_users, f] and ``items_factors`` [n_items, f], and the score their dot
+    product (algorithms/mf_algs.py: ALS, SVD). Nothing of the interaction matrix is needed to score, so a loaded model needs no ``attach``,
+    and both sides of the evaluation hooks are plain tensors: the fused scorers serve such a model. ``model.npz`` holds the reference's two
+    fields and ``name``; a file written by the reference (no ``name``) loads as is. ``kwargs`` of every model: ``device``.
+
+    A model writes: its constructor, ``fit`` and ``build_from_conf``."""
+
+    def __init__(self, device=None):
+        super().__init__()
+        self.device = torch.device(device or 'cuda')
+        self.users_factors = self.items_factors = None
+
+    def to(self, device):
+        self.device = torch.device(device)
+        if self.users_factors is not None:
+            self.users_factors, self.items_factors = self.users_factors.to(self.device), self.items_factors.to(self.device)
+        return self
+
+    def _need_fit(self):
+        if self.users_factors is None or self.items_factors is None:
+            raise RuntimeError(f'{self.name}: no factors, run fit(matrix) or load_model_from_path(path)')
+
+    # ---- scoring: the hooks of evaluate_recommender_algorithm ----------------------------------------------------------------------------
+    def get_user_representations(self, u_idxs: torch.Tensor) -> torch.Tensor:
+        self._need_fit()
+        return self.users_factors[torch.as_tensor(u_idxs).long().to(self.users_factors.device)]
+
+    def get_item_representations(self, i_idxs: torch.Tensor) -> torch.Tensor:
+        self._need_fit()
+        return self.items_factors[torch.as_tensor(i_idxs).long().to(self.items_factors.device)]
+
+    @torch.no_grad()
+    def combine_user_item_representations(self, u_repr, i_repr) -> torch.Tensor:
+        """[B, f] x [I, f] -> [B, I] (evaluation), [B, f] x [B, N, f] -> [B, N] (one dot product per slot)"""
+        from . import ops
+        return ops.score(u_repr, i_repr)
+
+    @torch.no_grad()
+    def predict(self, u_idxs: torch.Tensor, i_idxs: torch.Tensor) -> torch.Tensor:
+        """algorithms/mf_algs.py:117-125: the dot products of the users' rows with the named items' rows, [batch_size, n]; taken from the
+        users' full score rows, so that a score has the same bits here and in the evaluation"""
+        self._need_fit()
+        rows = self.combine_user_item_representations(self.get_user_representations(u_idxs), self.items_factors)
+        return torch.gather(rows, 1, torch.as_tensor(i_idxs).long().to(rows.device))
+
+    # ---- persistence -------------------------------------------------------------------------------------------------------------------
+    def save_model_to_path(self, path: str):
+        self._need_fit()
+        np.savez(os.path.join(path, 'model.npz'), users_factors=self.users_factors.cpu().numpy(), items_factors=self.items_factors.cpu().numpy(),
+                 name=np.array(self.name))
+        print('Model Saved')
+
+    def load_model_from_path(self, path: str):
+        with np.load(os.path.join(path, 'model.npz'), allow_pickle=False) as f:
+            if 'pred_mtx' in f.files or 'users_factors' not in f.files or 'items_factors' not in f.files:
+                raise ValueError(f'{os.path.join(path, "model.npz")} is not a model of this package (it holds {f.files}): the reference '
+                                 f'stores its pickled prediction matrix `pred_mtx`, this package the two factor matrices; fit the model again')
+            name = str(f['name']) if 'name' in f.files else self.name           # the reference's files carry no name
+            if name != self.name:
+                raise ValueError(f'model.npz holds a {name}, this model is a {self.name}')
+            u, i = f['users_factors'], f['items_factors']
+            if u.ndim != 2 or i.ndim != 2 or u.shape[1] != i.shape[1]:
+                raise ValueError(f'model.npz: factor matrices of shapes {u.shape} and {i.shape} do not belong together')
+            self.users_factors = torch.from_numpy(u.astype(np.float32)).to(self.device)
+            self.items_factors = torch.from_numpy(i.astype(np.float32)).to(self.device)
         print('Model Loaded')
 
 

@@ -1341,6 +1341,66 @@ def p3_score_rows(csr, rows: Optional[torch.Tensor], W: torch.Tensor, alpha: flo
     return out
 
 
+# ---- implicit-feedback ALS (csrc/als.hip) -------------------------------------------------------------------------------------------
+ALS_MAX_FACTORS = 128
+_ALS_WS = {}
+
+
+def _als_factors(Y, who):
+    if Y.dtype != torch.float32 or Y.dim() != 2 or (Y.shape[1] > 1 and Y.stride(1) != 1) or (Y.shape[0] > 1 and Y.stride(0) < Y.shape[1]):
+        raise ValueError(f'{who}: Y must be a float32 [n, f] view with unit column stride, got {Y.dtype} {tuple(Y.shape)} strides {Y.stride()}')
+    n, f = int(Y.shape[0]), int(Y.shape[1])
+    return n, f, (int(Y.stride(0)) if n > 1 else max(f, 1))
+
+
+def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
+    """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a
+    half-sweep shares (``sbr_als_gram_f32``: row slabs added in slab order, the same bits on every run)."""
+    _need_cuda(Y)
+    n, f, ldy = _als_factors(Y, 'als_gram')
+    need = (int(lib().sbr_als_gram_f32_workspace(n, f)) + 3) // 4 if 1 <= f <= ALS_MAX_FACTORS else 0
+    ws = _ALS_WS.get(Y.device)
+    if need and (ws is None or ws.numel() < need):
+        ws = _grow(_ALS_WS, Y.device, need, lambda k: torch.empty(k, device=Y.device, dtype=torch.float32))
+    G = torch.empty(f, f, device=Y.device, dtype=torch.float32)
+    call('sbr_als_gram_f32', ptr(Y), n, ldy, f, float(reg), ptr(G), max(f, 1), ptr(ws) if need else None, 4 * ws.numel() if need else 0, stream())
+    return G
+
+
+def als_solve_rows(csr, Y: torch.Tensor, G: torch.Tensor, alpha: float, out=None, rows=None) -> torch.Tensor:
+    """One ALS half-sweep over the rows ``rows=(r0, r1)`` (None: every row) of the resident ``features.DeviceCSR`` ``csr`` [n, n_y]:
+    ``out[r] = (G + sum_i (alpha r_i - 1) y_i y_i^T)^-1 sum_i alpha r_i y_i`` over the entries i of row r, with ``G = als_gram(Y, reg)``
+    (``sbr_als_solve_rows_f32``: one workgroup per row, Cholesky in LDS). ``out``: a float32 [n, f] view with unit column stride to
+    write into (the rows outside the range keep what they hold; those of a new result are zero). Raises ``SibrarHipError`` naming the
+    first row whose system is not positive definite in float32. Reads one int32 back: synchronises with the stream."""
+    _need_cuda(csr.indptr, Y, G, out)
+    n, n_y = csr.shape
+    ny, f, ldy = _als_factors(Y, 'als_solve_rows')
+    if ny != n_y:
+        raise ValueError(f'als_solve_rows: Y has {ny} rows, the matrix {n_y} columns')
+    if G.dtype != torch.float32 or tuple(G.shape) != (f, f):
+        raise ValueError(f'als_solve_rows: G must be float32 [{f}, {f}], got {G.dtype} {tuple(G.shape)}')
+    G = G.contiguous()
+    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 <= r1 <= n:
+        raise ValueError(f'als_solve_rows: row range [{r0}, {r1}) outside [0, {n}]')
+    if out is None:
+        out = (torch.empty if (r0, r1) == (0, n) else torch.zeros)((n, f), device=Y.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, f) or (f > 1 and out.stride(1) != 1) or (n > 1 and out.stride(0) < f):
+        raise ValueError(f'als_solve_rows: out must be a float32 [{n}, {f}] view with unit column stride, got {out.dtype} {tuple(out.shape)} '
+                         f'strides {out.stride()}')
+    info = torch.zeros(1, device=Y.device, dtype=torch.int32)
+    call('sbr_als_solve_rows_f32', ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), r0, r1, ptr(Y), n_y, ldy, f, ptr(G), float(alpha),
+         ptr(out), int(out.stride(0)) if n > 1 else max(f, 1), ptr(info), stream())
+    bad = int(info.item())
+    if bad:
+        from ._lib import SibrarHipError
+        raise SibrarHipError(f'als_solve_rows: the system of row {bad - 1} is not positive definite in float32 (a pivot of its Cholesky '
+                             f'factorisation is not positive); the fp32 factorisation needs `regularization` well above f * 2^-24 * ||A|| '
+                             f'(f = {f}, alpha = {float(alpha):g}): raise `regularization` or lower `factors`')
+    return out
+
+
 class BiasScoreFn(Function):
     """out[b, n] = base[b, n] + user_bias[u[b]] + item_bias[i[b, n]] + global_bias (sgd_alg.py:186-194, 110-119); every term
     optional (None). Bias tables are 1-D float views of the [n, 1] embedding weights. u None: row b; i None: column n."""
