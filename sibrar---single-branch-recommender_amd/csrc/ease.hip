@@ -5,7 +5,7 @@
 // No float atomics anywhere: the counts are integers (LDS integer atomics), every float has one owner per launch and a fixed
 // operation order, so all three give the same bits on every run and are valid in deterministic mode.
 #include "common.h"
-#include "cooc_count.h"
+#include "csr_walk.h"
 
 typedef float ease_f32x16 __attribute__((ext_vector_type(16)));
 

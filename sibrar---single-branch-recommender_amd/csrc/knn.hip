@@ -6,7 +6,7 @@
 // No float atomics anywhere: the counts are integers (LDS integer atomics: exact, order-free), every float has one owner and a fixed
 // operation order, so both entries give the same bits on every run and are valid in deterministic mode.
 #include "common.h"
-#include "cooc_count.h"
+#include "csr_walk.h"
 
 #define KNN_THREADS 1024
 #define KNN_WAVES (KNN_THREADS / 64)
@@ -287,14 +287,7 @@ __global__ __launch_bounds__(64 * CXC_WAVES) void csr_rows_times_csr_kernel(cons
       my_x = x_data ? x_data[p0 + lane] : 1.f;
       my_base = y_indptr[j];
       my_len = (int)(y_indptr[j + 1] - my_base);
-      if (my_len > CXC_SCAN_MAX) {                          // first entry of Y's row with column >= cb
-        int lo = 0, hi = my_len;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (y_indices[my_base + mid] < cb) lo = mid + 1; else hi = mid;
-        }
-        my_beg = lo;
-      }
+      if (my_len > CXC_SCAN_MAX) my_beg = sbr_csr_lower_bound(y_indices + my_base, 0, my_len, cb);
     }
     for (int e = 0; e < n_e; ++e) {
       const float xv = __shfl(my_x, e, 64);

@@ -6,6 +6,7 @@
 // thread in the score rows) and receives its terms in the order stated above by plain fp32 additions, so both give the same bits on
 // every run and are valid in deterministic mode. include/sibrar_hip.h states the same order; tests/p3alpha_ref.py restates it in numpy.
 #include "common.h"
+#include "csr_walk.h"
 
 #define P3_THREADS 1024
 #define P3_WAVES (P3_THREADS / 64)
@@ -48,22 +49,12 @@ __global__ __launch_bounds__(P3_THREADS) void p3_walk_dense_kernel(const long* _
           my_lo = indptr[v];
           my_end = indptr[v + 1];
           my_inv = p3_inv(my_end - my_lo);
-          if (c0 > 0) {                                           // first entry of the user's list with column >= c0
-            long hi = my_end;
-            while (my_lo < hi) {
-              const long mid = (my_lo + hi) >> 1;
-              if (indices[mid] < c0) my_lo = mid + 1; else hi = mid;
-            }
-          }
+          if (c0 > 0) my_lo = sbr_csr_lower_bound(indices, my_lo, my_end, c0);
         }
         for (int e = 0; e < n_e; ++e) {
           const float iv = __shfl(my_inv, e, 64);
           const long end = __shfl(my_end, e, 64);
-          for (long q = __shfl(my_lo, e, 64) + lane; q < end; q += 64) {
-            const unsigned int x = (unsigned int)(indices[q] - c0);
-            if (x >= (unsigned int)s_width) break;                // sorted: the rest of the list belongs to later strips
-            acc[x] = acc[x] + iv;
-          }
+          sbr_csr_walk_window(indices, __shfl(my_lo, e, 64), end, c0, s_width, lane, [&](unsigned int x, long) { acc[x] = acc[x] + iv; });
           // the next user may name the same accumulator from another lane: keep the LDS accesses of two users in program order
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
           __builtin_amdgcn_wave_barrier();

@@ -297,12 +297,17 @@ def _grow(table, key, need, make):
     return ws
 
 
+def _device_ws(table, key, n_elems, dtype, floor=0):
+    """The grow-only scratch of ``table`` for the device ``key``, with at least ``n_elems`` elements (``floor``: of a first allocation)"""
+    ws = table.get(key)
+    if ws is None or ws.numel() < n_elems:
+        ws = _grow(table, key, max(n_elems, floor), lambda n: torch.empty(n, device=key, dtype=dtype))
+    return ws
+
+
 def _tn_workspace(device, nbytes):
     """Grow-only scratch for the split-K slabs (one per device; reused by every dW product of a step)."""
-    ws = _TN_WS.get(device)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _grow(_TN_WS, device, max((nbytes + 3) // 4, 1 << 20), lambda n: torch.empty(n, device=device, dtype=torch.float32))
-    return ws
+    return _device_ws(_TN_WS, device, (nbytes + 3) // 4, torch.float32, 1 << 20)
 
 
 def matmul_tn(dz, x, a_idx=None, b_idx=None, n_rows=None, out=None):
@@ -1174,6 +1179,52 @@ def csr_rows_times_dense(csr, rows: torch.Tensor, dense: torch.Tensor) -> torch.
     return SparseLinearActFn.apply(csr, rows, dense.t(), None, 0)
 
 
+# ---- operands of the fit-matrix entries (knn.hip, ease.hip, p3alpha.hip, als.hip) -------------------------------------------------------
+def _row_range(rows, n):
+    """``(r0, r1, whole)`` of ``rows=(r0, r1)`` among ``n`` rows (None: every row)"""
+    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    return r0, r1, (r0, r1) == (0, n)
+
+
+def _binary_csr_rows(who, csr, rows, n_rows, why):
+    """The call shape of the entries that walk a binary resident ``features.DeviceCSR`` and its transpose over ``rows=(r0, r1)`` of
+    ``n_rows``: refuses a matrix with values (``why``: the entry's reason) -> the eight leading arguments, ``whole`` of ``_row_range``"""
+    if csr.data is not None:
+        raise ValueError(f'{who}: {why}; this matrix has values')
+    r0, r1, whole = _row_range(rows, n_rows)
+    t_indptr, t_indices, _ = csr.transposed()
+    return (ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), *csr.shape, r0, r1), whole
+
+
+def _f32_rows_view(who, name, t, shape=None, square=False):
+    """``(n_rows, n_cols, ld)`` of a float32 matrix view with unit column stride and rows at least a row apart (a dimension of size <= 1
+    has no stride to check); ``shape``: the shape it must have; ``square``: any square one, refused in the words of the SPD entries"""
+    ok = t.dim() == 2 and (shape is None or tuple(t.shape) == tuple(shape)) and (not square or t.shape[0] == t.shape[1]) \
+        and (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+    if square:
+        if t.dtype != torch.float32:
+            raise ValueError(f'{who}: float32 only, got {t.dtype}')
+        if not ok:
+            raise ValueError(f'{who}: a square row-major view is needed, got shape {tuple(t.shape)} strides {t.stride()}')
+    elif t.dtype != torch.float32 or not ok:
+        raise ValueError(f'{who}: {name} must be a float32 {list(shape) if shape else "[n, f]"} view with unit column stride, got {t.dtype} '
+                         f'{tuple(t.shape)} strides {t.stride()}')
+    n, c = int(t.shape[0]), int(t.shape[1])
+    return n, c, (int(t.stride(0)) if n > 1 else max(c, 1))
+
+
+def _rows_out(who, out, shape, whole, device):
+    """``(out, ld)`` of a dense float32 result written by row range: ``out`` checked, or allocated (zeroed unless every row is written)"""
+    if out is None:
+        out = (torch.empty if whole else torch.zeros)(shape, device=device, dtype=torch.float32)
+    return out, _f32_rows_view(who, 'out', out, shape)[2]
+
+
+def _row_list(rows, n):
+    """``(rows as contiguous int64 or None, B)`` of a list of row indices (None: every one of the ``n`` rows)"""
+    return (None, n) if rows is None else (rows.long().contiguous(), rows.numel())
+
+
 # ---- neighbourhood models (csrc/knn.hip) ------------------------------------------------------------------------------------------
 KNN_SIM_CODES = {'cosine': 0, 'jaccard': 1, 'asymmetric_cosine': 2, 'sorensen_dice': 3, 'tversky': 4}
 KNN_MAX_K = 256
@@ -1188,19 +1239,13 @@ def knn_topk(csr, sim, k: int, shrinkage: float = 0., alpha=None, beta=None, row
     if not isinstance(code, int) or code not in KNN_SIM_CODES.values():
         raise ValueError(f'knn_topk: unknown similarity {sim!r} (one of {sorted(KNN_SIM_CODES)})')
     _need_cuda(csr.indptr)
-    if csr.data is not None:
-        raise ValueError('knn_topk: the similarities are stated for 0/1 data only (utilities/similarities.py:11-15); this matrix has values')
-    n, m = csr.shape
-    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
-    dev = csr.indptr.device
-    whole = (r0, r1) == (0, n)
+    n, dev = csr.shape[0], csr.indptr.device
+    args, whole = _binary_csr_rows('knn_topk', csr, rows, n, 'the similarities are stated for 0/1 data only (utilities/similarities.py:11-15)')
     idx = (torch.empty if whole else partial(torch.full, fill_value=-1))((n, k), device=dev, dtype=torch.int32)
     val = (torch.empty if whole else torch.zeros)((n, k), device=dev, dtype=torch.float32)
     length = (torch.empty if whole else torch.zeros)((n,), device=dev, dtype=torch.int32)
-    t_indptr, t_indices, _ = csr.transposed()
-    call('sbr_knn_topk', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, code,
-         float(0. if alpha is None else alpha), float(0. if beta is None else beta), float(shrinkage), int(k), int(tile_cols),
-         ptr(idx), ptr(val), ptr(length), stream())
+    call('sbr_knn_topk', *args, code, float(0. if alpha is None else alpha), float(0. if beta is None else beta), float(shrinkage), int(k),
+         int(tile_cols), ptr(idx), ptr(val), ptr(length), stream())
     return idx, val, length
 
 
@@ -1221,9 +1266,7 @@ def csr_rows_times_csr(x, rows: Optional[torch.Tensor], y, tile_cols: int = 0) -
     if xs[1] != ys[0]:
         raise ValueError(f'csr_rows_times_csr: shapes {tuple(xs)} and {tuple(ys)} do not chain')
     _need_cuda(xp, yp, rows)
-    if rows is not None:
-        rows = rows.long().contiguous()
-    B = xs[0] if rows is None else rows.numel()
+    rows, B = _row_list(rows, xs[0])
     out = torch.empty(B, ys[1], device=xp.device, dtype=torch.float32)
     call('sbr_csr_rows_times_csr', ptr(xp), ptr(xi), ptr(xd), ptr(rows), B, ptr(yp), ptr(yi), ptr(yd), int(ys[1]), int(tile_cols), ptr(out),
          out.stride(0) if B else ys[1], stream())
@@ -1234,48 +1277,20 @@ def csr_rows_times_csr(x, rows: Optional[torch.Tensor], y, tile_cols: int = 0) -
 _SPD_WS = {}
 
 
-def _item_item_out(who, csr, rows, out):
-    """``(r0, r1, out, ld)`` of a dense float32 [m, m] result over the items of ``csr``: the row range ``rows`` (None: every row), ``out``
-    checked, or allocated (zeroed where the range leaves rows unwritten), and its leading dimension"""
-    m = csr.shape[1]
-    r0, r1 = (0, m) if rows is None else (int(rows[0]), int(rows[1]))
-    if out is None:
-        out = (torch.empty if (r0, r1) == (0, m) else torch.zeros)((m, m), device=csr.indptr.device, dtype=torch.float32)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (m, m) or (m > 1 and out.stride(1) != 1):
-        raise ValueError(f'{who}: out must be a float32 [{m}, {m}] view with unit column stride, got {out.dtype} {tuple(out.shape)} '
-                         f'strides {out.stride()}')
-    return r0, r1, out, out.stride(0) if m > 1 else max(m, 1)
-
-
 def gram_dense(csr, diag_add: float = 0., rows=None, tile_cols: int = 0, out=None) -> torch.Tensor:
     """``X^T X + diag_add * I`` of a binary resident ``features.DeviceCSR`` X [n, m] as dense float32 [m, m], counted exactly
     (algorithms/linear_algs.py:150-153). ``rows=(r0, r1)`` computes that row range only (the other rows of a new result are zero, those
     of ``out`` keep what they hold); ``out``: a float32 [m, m] view with unit column stride to write into; ``tile_cols`` as in the header."""
     _need_cuda(csr.indptr, out)
-    if csr.data is not None:
-        raise ValueError('gram_dense: the counts are integers for 0/1 data only; this matrix has values')
-    n, m = csr.shape
-    r0, r1, out, ld = _item_item_out('gram_dense', csr, rows, out)
-    t_indptr, t_indices, _ = csr.transposed()
-    call('sbr_gram_dense', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, float(diag_add), int(tile_cols),
-         ptr(out), ld, stream())
+    m = csr.shape[1]
+    args, whole = _binary_csr_rows('gram_dense', csr, rows, m, 'the counts are integers for 0/1 data only')
+    out, ld = _rows_out('gram_dense', out, (m, m), whole, csr.indptr.device)
+    call('sbr_gram_dense', *args, float(diag_add), int(tile_cols), ptr(out), ld, stream())
     return out
 
 
-def _square_f32_view(A, who):
-    if A.dtype != torch.float32:
-        raise ValueError(f'{who}: float32 only, got {A.dtype}')
-    if A.dim() != 2 or A.shape[0] != A.shape[1] or (A.shape[0] > 1 and (A.stride(1) != 1 or A.stride(0) < A.shape[0])):
-        raise ValueError(f'{who}: a square row-major view is needed, got shape {tuple(A.shape)} strides {A.stride()}')
-    return A.shape[0], (A.stride(0) if A.shape[0] > 1 else 1)
-
-
 def _spd_workspace(device, n):
-    need = (int(lib().sbr_spd_inverse_f32_workspace(n)) + 3) // 4
-    ws = _SPD_WS.get(device)
-    if ws is None or ws.numel() < need:
-        ws = _grow(_SPD_WS, device, need, lambda k: torch.empty(k, device=device, dtype=torch.float32))
-    return ws
+    return _device_ws(_SPD_WS, device, (int(lib().sbr_spd_inverse_f32_workspace(n)) + 3) // 4, torch.float32)
 
 
 def spd_inverse_(A: torch.Tensor) -> torch.Tensor:
@@ -1284,7 +1299,7 @@ def spd_inverse_(A: torch.Tensor) -> torch.Tensor:
     operation order: the same bits on every run. Raises ``ValueError`` naming the pivot when one is not positive (A then holds no
     inverse). Reads one int32 back: synchronises with the stream."""
     _need_cuda(A)
-    n, ld = _square_f32_view(A, 'spd_inverse_')
+    n, _, ld = _f32_rows_view('spd_inverse_', 'A', A, square=True)
     if n == 0:
         return A
     ws = _spd_workspace(A.device, n)
@@ -1299,7 +1314,7 @@ def spd_inverse_(A: torch.Tensor) -> torch.Tensor:
 def ease_weights_(P: torch.Tensor) -> torch.Tensor:
     """``B = P / (-diag(P))`` (column j divided by ``-P[j, j]``) with a zero diagonal, in place — algorithms/linear_algs.py:157-158."""
     _need_cuda(P)
-    n, ld = _square_f32_view(P, 'ease_weights_')
+    n, _, ld = _f32_rows_view('ease_weights_', 'P', P, square=True)
     if n:
         call('sbr_ease_weights_f32', ptr(P), n, ld, ptr(_spd_workspace(P.device, n)), stream())
     return P
@@ -1310,14 +1325,11 @@ def p3_walk_dense(csr, rows=None, tile_cols: int = 0, out=None) -> torch.Tensor:
     """The item-item matrix ``W = D_i^-1 X^T D_u^-1 X`` of the three-step random walk on a binary resident ``features.DeviceCSR`` X
     [n, m] as dense float32 [m, m] (algorithms/graph_algs.py:35-59), in the fixed order of ``sbr_p3_walk_dense``: the same bits on every
     run. ``rows``, ``out`` and ``tile_cols`` as in ``gram_dense``."""
-    if csr.data is not None:
-        raise ValueError('p3_walk_dense: the walk is stated for 0/1 data only (degrees are entry counts); this matrix has values')
+    m = csr.shape[1]
+    args, whole = _binary_csr_rows('p3_walk_dense', csr, rows, m, 'the walk is stated for 0/1 data only (degrees are entry counts)')
     _need_cuda(csr.indptr, out)
-    n, m = csr.shape
-    r0, r1, out, ld = _item_item_out('p3_walk_dense', csr, rows, out)
-    t_indptr, t_indices, _ = csr.transposed()
-    call('sbr_p3_walk_dense', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n, m, r0, r1, int(tile_cols), ptr(out), ld,
-         stream())
+    out, ld = _rows_out('p3_walk_dense', out, (m, m), whole, csr.indptr.device)
+    call('sbr_p3_walk_dense', *args, int(tile_cols), ptr(out), ld, stream())
     return out
 
 
@@ -1333,9 +1345,7 @@ def p3_score_rows(csr, rows: Optional[torch.Tensor], W: torch.Tensor, alpha: flo
     if not float(alpha) > 0:
         raise ValueError(f'p3_score_rows: alpha={alpha!r} must be positive')
     _need_cuda(csr.indptr, rows, W)
-    if rows is not None:
-        rows = rows.long().contiguous()
-    B = n if rows is None else rows.numel()
+    rows, B = _row_list(rows, n)
     out = torch.empty(B, m, device=csr.indptr.device, dtype=torch.float32)
     call('sbr_p3_score_rows', ptr(csr.indptr), ptr(csr.indices), ptr(rows), B, ptr(W), max(m, 1), m, float(alpha), ptr(out), max(m, 1), stream())
     return out
@@ -1346,24 +1356,15 @@ ALS_MAX_FACTORS = 128
 _ALS_WS = {}
 
 
-def _als_factors(Y, who):
-    if Y.dtype != torch.float32 or Y.dim() != 2 or (Y.shape[1] > 1 and Y.stride(1) != 1) or (Y.shape[0] > 1 and Y.stride(0) < Y.shape[1]):
-        raise ValueError(f'{who}: Y must be a float32 [n, f] view with unit column stride, got {Y.dtype} {tuple(Y.shape)} strides {Y.stride()}')
-    n, f = int(Y.shape[0]), int(Y.shape[1])
-    return n, f, (int(Y.stride(0)) if n > 1 else max(f, 1))
-
-
 def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
     """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a
     half-sweep shares (``sbr_als_gram_f32``: row slabs added in slab order, the same bits on every run)."""
     _need_cuda(Y)
-    n, f, ldy = _als_factors(Y, 'als_gram')
+    n, f, ldy = _f32_rows_view('als_gram', 'Y', Y)
     need = (int(lib().sbr_als_gram_f32_workspace(n, f)) + 3) // 4 if 1 <= f <= ALS_MAX_FACTORS else 0
-    ws = _ALS_WS.get(Y.device)
-    if need and (ws is None or ws.numel() < need):
-        ws = _grow(_ALS_WS, Y.device, need, lambda k: torch.empty(k, device=Y.device, dtype=torch.float32))
+    ws = _device_ws(_ALS_WS, Y.device, need, torch.float32) if need else None
     G = torch.empty(f, f, device=Y.device, dtype=torch.float32)
-    call('sbr_als_gram_f32', ptr(Y), n, ldy, f, float(reg), ptr(G), max(f, 1), ptr(ws) if need else None, 4 * ws.numel() if need else 0, stream())
+    call('sbr_als_gram_f32', ptr(Y), n, ldy, f, float(reg), ptr(G), max(f, 1), ptr(ws), 4 * ws.numel() if need else 0, stream())
     return G
 
 
@@ -1375,23 +1376,19 @@ def als_solve_rows(csr, Y: torch.Tensor, G: torch.Tensor, alpha: float, out=None
     first row whose system is not positive definite in float32. Reads one int32 back: synchronises with the stream."""
     _need_cuda(csr.indptr, Y, G, out)
     n, n_y = csr.shape
-    ny, f, ldy = _als_factors(Y, 'als_solve_rows')
+    ny, f, ldy = _f32_rows_view('als_solve_rows', 'Y', Y)
     if ny != n_y:
         raise ValueError(f'als_solve_rows: Y has {ny} rows, the matrix {n_y} columns')
     if G.dtype != torch.float32 or tuple(G.shape) != (f, f):
         raise ValueError(f'als_solve_rows: G must be float32 [{f}, {f}], got {G.dtype} {tuple(G.shape)}')
     G = G.contiguous()
-    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    r0, r1, whole = _row_range(rows, n)
     if not 0 <= r0 <= r1 <= n:
         raise ValueError(f'als_solve_rows: row range [{r0}, {r1}) outside [0, {n}]')
-    if out is None:
-        out = (torch.empty if (r0, r1) == (0, n) else torch.zeros)((n, f), device=Y.device, dtype=torch.float32)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (n, f) or (f > 1 and out.stride(1) != 1) or (n > 1 and out.stride(0) < f):
-        raise ValueError(f'als_solve_rows: out must be a float32 [{n}, {f}] view with unit column stride, got {out.dtype} {tuple(out.shape)} '
-                         f'strides {out.stride()}')
+    out, ldo = _rows_out('als_solve_rows', out, (n, f), whole, Y.device)
     info = torch.zeros(1, device=Y.device, dtype=torch.int32)
     call('sbr_als_solve_rows_f32', ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), r0, r1, ptr(Y), n_y, ldy, f, ptr(G), float(alpha),
-         ptr(out), int(out.stride(0)) if n > 1 else max(f, 1), ptr(info), stream())
+         ptr(out), ldo, ptr(info), stream())
     bad = int(info.item())
     if bad:
         from ._lib import SibrarHipError
@@ -1501,11 +1498,7 @@ def infonce_uses_gemm(G: int, N: int) -> bool:
 
 def _infonce_ws(device, N, D):
     from ._lib import lib
-    need = lib().sbr_infonce_gemm_workspace(N, D)
-    ws = _INFONCE_WS.get(device)
-    if ws is None or ws.numel() < need:
-        ws = _grow(_INFONCE_WS, device, need, lambda n: torch.empty(n, device=device, dtype=torch.uint8))
-    return ws
+    return _device_ws(_INFONCE_WS, device, lib().sbr_infonce_gemm_workspace(N, D), torch.uint8)
 
 
 def infonce_fwd(a_ptr, b_ptr, ld, G, N, D, tau, scale, loss_out, device):

@@ -170,6 +170,45 @@ def predict(alg, s, x):
     return s @ x if alg == 'uknn' else x @ s.T
 
 
+def csr_rows_times_csr_ordered(x, rows, y):
+    """float32 [len(rows), y.shape[1]]: the order oracle of sbr_csr_rows_times_csr. A cell's float32 accumulator receives x[p] * y[col(p), c]
+    over the entries p of X's row in ascending column of X, one np.float32 addition each (a cell without an entry of Y's row receives
+    nothing). Equal in bits to the kernel's acc = fmaf(x, y, acc) when every product is exact in float32: fmaf then is the exact product
+    followed by one rounded addition. ordered_product_operands() gives such operands (X holds powers of two)."""
+    x, y = sp.csr_matrix(x), sp.csr_matrix(y)
+    assert x.has_sorted_indices and y.has_sorted_indices and x.dtype == y.dtype == np.float32
+    out = np.zeros((len(rows), y.shape[1]), dtype=np.float32)
+    for b, r in enumerate(rows):
+        for p in range(x.indptr[r], x.indptr[r + 1]):
+            lo, hi = y.indptr[x.indices[p]], y.indptr[x.indices[p] + 1]
+            cols = y.indices[lo:hi]                                            # distinct: one addition per cell
+            out[b, cols] = out[b, cols] + x.data[p] * y.data[lo:hi]
+    return out
+
+
+def ordered_product_operands(n_cols):
+    """(x, rows, y) for the order pin of sbr_csr_rows_times_csr. X [6, 130]: rows of 0, 1, 63, 64, 65 and 130 entries (the edges of the
+    64-entry staging loop) with values 2^-3 ... 2^3, so every product is exact; ``rows`` names them out of order, one twice. Y
+    [130, n_cols] float32 in [-4, 4]: rows of 0, 5, 128 and 129 entries in turn (either side of the scan limit of 128; a Y of fewer than
+    130 columns has no such rows: 0, 5, n_cols / 2 and n_cols entries then), the 5-entry rows with columns 15 and 16 on the two sides
+    of a strip edge."""
+    rng = np.random.default_rng(1000 + n_cols)
+    x = np.zeros((6, 130), dtype=np.float32)
+    for r, cnt in enumerate((0, 1, 63, 64, 65, 130)):
+        x[r, rng.choice(130, cnt, replace=False)] = 2.0 ** rng.integers(-3, 4, cnt)
+    y = np.zeros((130, n_cols), dtype=np.float32)
+    for j in range(130):
+        cnt = ((0, 5, 128, 129) if n_cols >= 130 else (0, 5, n_cols // 2, n_cols))[j % 4]
+        cols = rng.choice(n_cols, cnt, replace=False)
+        if cnt == 5:
+            cols = np.concatenate(([15, 16], np.setdiff1d(cols, [15, 16])[:3]))
+        y[j, cols] = rng.uniform(0.001, 4., cnt) * rng.choice([-1., 1.], cnt)
+    x, y = sp.csr_matrix(x), sp.csr_matrix(y)
+    x.sort_indices()
+    y.sort_indices()
+    return x, np.array([5, 0, 3, 1, 2, 4, 3], dtype=np.int64), y
+
+
 def entity_matrix(alg, x):
     """the matrix whose rows are compared: users x items for 'uknn', items x users for 'iknn'"""
     x = dense01(x)

@@ -255,6 +255,32 @@ def test_csr_rows_times_csr(x_values, y_values, wide, tile_cols):
     _assert_bits(outs[2], outs[0], 'repeat')
 
 
+@functools.lru_cache(maxsize=None)
+def ordered_product(n_cols, y_values):
+    x, rows, y = R.ordered_product_operands(n_cols)
+    if not y_values:
+        y = abs(y).sign().astype(np.float32)
+    return x, rows, y, R.csr_rows_times_csr_ordered(x, rows, y)
+
+
+@pytest.mark.parametrize('tile_cols', [64, 0])
+@pytest.mark.parametrize('y_values', [False, True])
+@pytest.mark.parametrize('n_cols', [70, 134])
+def test_csr_rows_times_csr_summation_order(n_cols, y_values, tile_cols):
+    """Bit equality with the order oracle of knn_ref (exact: X holds powers of two). tile_cols = 64: strips of 16 columns, the last one
+    of 6; X rows of 0, 1, 63, 64, 65 and 130 entries; Y rows of up to 129 entries at n_cols = 134 (scanned up to 128, entered by a
+    lower bound above), which a Y of 70 columns cannot hold: there every row is scanned, with entries on both sides of the strip edges."""
+    x, rows, y, ref = ordered_product(n_cols, y_values)
+    xp, xi = _csr_dev(x)
+    yp, yi = _csr_dev(y)
+    xd = torch.from_numpy(x.data).to(DEV)
+    yd = torch.from_numpy(y.data).to(DEV) if y_values else None
+    out = _Buf(len(rows), n_cols, ld=n_cols + 3, off=1)
+    call('sbr_csr_rows_times_csr', _p(xp), _p(xi), _p(xd), _p(_i64(rows)), len(rows), _p(yp), _p(yi), _p(yd), n_cols, tile_cols, out.ptr,
+         n_cols + 3, _L().stream())
+    _assert_bits(out.check_untouched().contiguous().cpu(), torch.from_numpy(ref), f'n_cols={n_cols} y_values={y_values} tile_cols={tile_cols}')
+
+
 def test_ops_csr_rows_times_csr_all_rows_and_errors():
     Sm = S()
     feats = __import__('importlib').import_module(Sm.ops.__name__.rsplit('.', 1)[0] + '.features')

@@ -56,6 +56,36 @@ def test_the_rule_rejects_a_wrong_neighbour():
         R.check_case_against_fixture(case, ARRAYS, idx, val, length, None, lambda v, c: 1e-12 * v)
 
 
+@pytest.mark.parametrize('n_cols', [70, 134])
+def test_ordered_product_oracle_is_exact_and_meets_float64(n_cols):
+    x, rows, y = R.ordered_product_operands(n_cols)
+    assert [x.indptr[r + 1] - x.indptr[r] for r in range(6)] == [0, 1, 63, 64, 65, 130] and len(set(rows.tolist())) < len(rows)
+    want = {0, 5, 128, 129} if n_cols >= 130 else {0, 5, n_cols // 2, n_cols}
+    assert set(np.diff(y.indptr).tolist()) == want and np.abs(y.data).max() <= 4
+    assert set(np.log2(x.data).tolist()) <= set(range(-3, 4))
+    # the precondition of exactness: no product of an X value and a Y value rounds, underflows or overflows in float32
+    for v in np.unique(x.data):
+        prod = v * y.data
+        assert prod.dtype == np.float32 and np.array_equal(prod.astype(np.float64), float(v) * y.data.astype(np.float64))
+        assert np.all(np.abs(prod) >= np.finfo(np.float32).tiny) and np.all(np.isfinite(prod))
+    for yy in (y, abs(y).sign().astype(np.float32)):                                   # y_data given, and NULL (ones)
+        got = R.csr_rows_times_csr_ordered(x, rows, yy).astype(np.float64)
+        xs, ys = x[rows].astype(np.float64), yy.astype(np.float64)
+        terms = np.asarray(((xs != 0).astype(np.float64) @ (ys != 0).astype(np.float64)).todense())
+        assert np.all(np.abs(got - np.asarray((xs @ ys).todense())) <= R.gamma(terms) * np.asarray((abs(xs) @ abs(ys)).todense()))
+        assert np.array_equal(got[1], np.zeros(n_cols)) and np.array_equal(got[2], got[6])   # the empty row; the repeated row
+
+
+def test_ordered_product_oracle_is_order_sensitive():
+    """one row, one column, terms 1, 2^-24, 2^-24: ascending (1 + 2^-24) + 2^-24 = 1 (two ties to even), descending 2^-23 + 1"""
+    xv, yv = np.float32([1., 2. ** -3, 2. ** -3]), np.float32([1., 2. ** -21, 2. ** -21])
+    fwd = R.csr_rows_times_csr_ordered(sp.csr_matrix(xv[None, :]), [0], sp.csr_matrix(yv[:, None]))
+    rev = R.csr_rows_times_csr_ordered(sp.csr_matrix(xv[None, ::-1]), [0], sp.csr_matrix(yv[::-1, None]))
+    assert fwd[0, 0] == np.float32(1.) and rev[0, 0] == np.float32(1. + 2. ** -23)
+    assert fwd.view(np.int32)[0, 0] != rev.view(np.int32)[0, 0]
+    assert abs(float(rev[0, 0]) - (1 + 2. ** -23)) <= R.gamma(3) * (1 + 2. ** -23)
+
+
 def test_value_bound_is_the_stated_count():
     x = ARRAYS['inter']
     for sim, n_round in (('cosine', 4), ('jaccard', 1), ('sorensen_dice', 1), ('tversky', 5)):
