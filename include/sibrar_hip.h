@@ -746,6 +746,69 @@ long sbr_als_gram_f32_workspace(long n_y, int f);
 int sbr_als_solve_rows_f32(const long* indptr, const int* indices, const float* data, long r0, long r1, const float* Y, long n_y, long ldy,
                            int f, const float* G, float alpha, float* X, long ldx, int* info, void* stream);
 
+/* ---- truncated SVD by block subspace iteration (csrc/svd.hip) ----------------------------------------------------------------------
+ * algorithms/mf_algs.py:14-66 calls ARPACK (scipy's svds); here a block V [n_items, b], b <= 128, is iterated: Y = X V, U = orth(Y),
+ * Z = X^T U, (V, s, W) = orth(Z), U <- U W, where orth(Y) = Y W diag(1 / s) with Y^T Y = W diag(lam) W^T, lam descending, and
+ * s = sqrt(max(lam, tiny)). Every entry below has one owner per output element and a stated order: the same bits on every run, valid in
+ * deterministic mode, whatever the deterministic switch says.
+ *
+ * G = Y^T Y as fp32 [f, f]: sbr_als_gram_f32's two launches (slabs of 512 rows, fmaf in ascending row order from +0, the slabs' partial
+ * sums added in ascending slab order) with nothing added to the diagonal; G is symmetric bit for bit; the workspace is
+ * sbr_als_gram_f32_workspace(n_y, f) bytes. New (additive to ABI 4). */
+int sbr_gram_f32(const float* Y, long n_y, long ldy, int f, float* G, long ldg, void* workspace, long workspace_bytes, void* stream);
+/* A = W diag(lam) W^T for a symmetric fp32 A [n, n], 1 <= n <= 128 (leading dimension lda; the lower triangle of the n x n view is read
+ * and mirrored, nothing else): W fp32 [n, n] with leading dimension ldw holds the eigenvectors as columns, lam [n] the eigenvalues in
+ * descending order. Parallel cyclic Jacobi by one workgroup. The elements are converted to double, the whole iteration is in double
+ * and the results are rounded to fp32 once, at the end: an fp32 iteration leaves errors of 1e-6 at n = 128 (about a thousand rotations
+ * per column), forty times the rounding of the results. The matrix is in LDS (8 N (N + 1) bytes), the accumulated rotations in
+ * `workspace`, transposed: both in double do not fit 160 KiB.
+ *   pair ordering: with N = n rounded up to even (an odd n adds one index that is a bye: the pair that holds it is left alone), a sweep
+ *     is the N - 1 steps r = 0 .. N - 2 of the round robin in which index N - 1 stays and the others move round: step r rotates the
+ *     N / 2 disjoint pairs {r, N - 1} and {(r + k) mod (N - 1), (r - k) mod (N - 1)}, k = 1 .. N / 2 - 1, each as (p, q) with p < q, all at
+ *     once (A <- J^T A J, W <- W J with J the product of the step's rotations);
+ *   rotation: a pair is left alone when |a_pq| <= 2^-40 * (sqrt(|a_pp|) * sqrt(|a_qq|)), the relative test that keeps a graded matrix
+ *     accurate; otherwise tau = (a_qq - a_pp) / (2 a_pq), t = sign(tau) / (|tau| + sqrt(1 + tau^2)) (sign(0) = +1),
+ *     c = 1 / sqrt(1 + t^2), s = t c; column p becomes c x_p - s x_q, column q becomes s x_p + c x_q, rows p and q likewise;
+ *     a_pp <- a_pp - t a_pq, a_qq <- a_qq + t a_pq, a_pq <- 0 exactly. Each 2 x 2 block of A (the rows of one pair, the columns of
+ *     another: rows first, then columns) has one owner, which also writes its mirror image: A stays symmetric bit for bit;
+ *   the iteration stops after a sweep without a rotation; the sweep cap is 30 (EIG_MAX_SWEEPS in csrc/svd.hip);
+ *   order: lam descending, equal values by ascending index of their position on the diagonal, the eigenvectors permuted along;
+ *   length and sign: every eigenvector is divided by its length (the sum of squares in ascending index) and multiplied by -1 if the
+ *     component of largest magnitude of the rounded result (the lowest index on a tie) is negative.
+ * info: one device int32, zero on entry: it is left alone on success and set to 31 (the sweeps run plus one) when the cap was reached
+ * with rotations still happening (an error return, not a fault: the kernel always finishes and writes W and lam as they then are).
+ * workspace: sbr_sym_eig_f32_workspace(n) bytes at an 8-byte boundary. No atomics: the same bits on every run. n outside [1, 128] is
+ * refused before any launch. New (additive to ABI 4). */
+int sbr_sym_eig_f32(const float* A, int n, long lda, float* W, long ldw, float* lam, int* info, void* workspace, long workspace_bytes,
+                    void* stream);
+/* bytes of `workspace` for sbr_sym_eig_f32: N x N doubles, N = n rounded up to even (0 for an n outside [1, 128]). New (additive to
+ * ABI 4). */
+long sbr_sym_eig_f32_workspace(int n);
+/* out[r, 0:c] = sum_k data_k D[col_k, 0:c] over the entries k of row r in ascending CSR order, for the rows r of [r0, r1) of a CSR
+ * matrix (indptr int64, indices int32 ascending and unique within a row and below n_d, data fp32 or NULL = all ones); D fp32 [n_d, c]
+ * with leading dimension ldd, out with leading dimension ldo, 1 <= c <= 128. Every element has one owner: it starts at +0.0f and
+ * receives fmaf(data_k, D[col_k][j], .) in that order, so an empty row writes +0.0f, and the bits of a row do not depend on [r0, r1).
+ * Only out[r0:r1, 0:c] is written. No atomics. 0 <= r0 <= r1 <= 2^31 - 2; an empty range returns at once. (sbr_csr_project_fwd is
+ * the training path's product: int32 row lists, a bias, an activation.) New (additive to ABI 4). */
+int sbr_csr_times_dense_f32(const long* indptr, const int* indices, const float* data, long r0, long r1, const float* D, long n_d,
+                            long ldd, int c, float* out, long ldo, void* stream);
+/* out = Y W diag(1 / s) for Y fp32 [n, b], W fp32 [b, b], 1 <= b <= 128 (leading dimensions ldy, ldw, ldo; out may be Y itself: a
+ * workgroup reads its 32 rows before it writes them). out[r][j] starts at +0.0f, receives fmaf(Y[r][k], W[k][j], .) in ascending k and
+ * is multiplied once by 1.0f / s[j], with s[j] = sqrtf(max(lam[j], tiny)), tiny = max(lam[0] * 2^-46, FLT_MIN): a direction whose
+ * eigenvalue drowned in the rounding of lam[0] is scaled by about 1 / (2^-23 sqrt(lam[0])) at the most instead of by 1 / 0. s [b] is
+ * written too. lam NULL: the plain product Y W, s is not touched. An fp32 fmaf chain of its own, not the `ops` GEMM: that one picks
+ * its kernel by shape (the bf16-split kernels from 4,096 rows at N = K = 128), which would tie the bits to n. New (additive to
+ * ABI 4). */
+int sbr_rotate_cols_f32(const float* Y, long n, long ldy, int b, const float* W, long ldw, const float* lam, float* s, float* out, long ldo,
+                        void* stream);
+/* res[j] = ||Y[:, j] - s[j] U[:, j]||_2 for j < f <= 128 over n rows: d = fmaf(-s[j], U[r][j], Y[r][j]), its square added by fmaf in
+ * ascending row order within slabs of 256 rows from +0, the slabs' sums added in ascending slab order, one sqrtf. workspace:
+ * sbr_col_residual_f32_workspace(n, f) bytes. New (additive to ABI 4). */
+int sbr_col_residual_f32(const float* Y, long ldy, const float* U, long ldu, const float* s, long n, int f, float* res, void* workspace,
+                         long workspace_bytes, void* stream);
+/* bytes of `workspace` for sbr_col_residual_f32: ceil(n / 256) partial sums [f] of fp32. New (additive to ABI 4). */
+long sbr_col_residual_f32_workspace(long n, int f);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

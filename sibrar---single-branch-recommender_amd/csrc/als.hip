@@ -1,6 +1,7 @@
 // Implicit-feedback ALS (algorithms/mf_algs.py:69-142; Hu, Koren and Volinsky, ICDM 2008): one half-sweep recomputes every row of a factor
 // matrix X from the other one, Y [n_y, f], 1 <= f <= 128. With c = alpha * r for an observed entry, c = 1 elsewhere and preference 1 / 0:
 //   sbr_als_gram_f32        G = Y^T Y + reg I                                     (shared by every row of the half-sweep)
+//   sbr_gram_f32            G = Y^T Y                                             (the same kernels; the truncated SVD's, csrc/svd.hip)
 //   sbr_als_solve_rows_f32  A_r = G + sum_{i in S} (alpha r_i - 1) y_i y_i^T,  b_r = sum_{i in S} alpha r_i y_i,  x_r = A_r^-1 b_r
 // No float atomics: every element of G, A_r and b_r has one owner and receives its terms in a stated order (include/sibrar_hip.h), the
 // factorisation and the two substitutions are fixed sequences, so both entry points give the same bits on every run, for every split of
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(256) void als_gram_reduce_kernel(const float* __res
   const int i = e / f, j = e - i * f;
   float s = 0.f;
   for (int b = 0; b < n_slabs; ++b) s = s + ws[(long)b * f * f + e];
-  if (i == j) s = s + reg;
+  if (i == j && reg != 0.f) s = s + reg;                             // sbr_gram_f32 (reg = 0): nothing is added
   G[(long)i * ldg + j] = s;
 }
 
@@ -89,24 +90,35 @@ extern "C" long sbr_als_gram_f32_workspace(long n_y, int f) {
   return ((n_y + ALS_G_SLAB - 1) / ALS_G_SLAB) * (long)f * f * 4;
 }
 
-extern "C" int sbr_als_gram_f32(const float* Y, long n_y, long ldy, int f, float reg, float* G, long ldg, void* workspace, long workspace_bytes,
-                                void* stream) {
-  SBR_REQUIRE(f >= 1 && f <= ALS_F_MAX, "sbr_als_gram_f32: f=%d outside [1, %d]", f, ALS_F_MAX);
-  SBR_REQUIRE(als_pos_finite(reg), "sbr_als_gram_f32: reg=%g is not positive and finite", (double)reg);
-  SBR_REQUIRE(n_y >= 0 && n_y <= 2147483647L * ALS_G_SLAB, "sbr_als_gram_f32: n_y=%ld out of range", n_y);
-  SBR_REQUIRE(ldy >= f && ldg >= f, "sbr_als_gram_f32: leading dimension below f=%d (ldy=%ld, ldg=%ld)", f, ldy, ldg);
-  SBR_REQUIRE(G && (Y || n_y == 0), "sbr_als_gram_f32: null operand");
+// the two launches of both Gram entries; `reg` = 0: the plain Gram matrix
+static int als_gram_launch(const char* who, const float* Y, long n_y, long ldy, int f, float reg, float* G, long ldg, void* workspace,
+                           long workspace_bytes, void* stream) {
+  SBR_REQUIRE(f >= 1 && f <= ALS_F_MAX, "%s: f=%d outside [1, %d]", who, f, ALS_F_MAX);
+  SBR_REQUIRE(reg == 0.f || als_pos_finite(reg), "%s: reg=%g is not positive and finite", who, (double)reg);
+  SBR_REQUIRE(n_y >= 0 && n_y <= 2147483647L * ALS_G_SLAB, "%s: n_y=%ld out of range", who, n_y);
+  SBR_REQUIRE(ldy >= f && ldg >= f, "%s: leading dimension below f=%d (ldy=%ld, ldg=%ld)", who, f, ldy, ldg);
+  SBR_REQUIRE(G && (Y || n_y == 0), "%s: null operand", who);
   const long need = sbr_als_gram_f32_workspace(n_y, f);
-  SBR_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "sbr_als_gram_f32: workspace of %ld bytes, %ld needed", workspace_bytes,
-              need);
+  SBR_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "%s: workspace of %ld bytes, %ld needed", who, workspace_bytes, need);
   const int n_slabs = (int)((n_y + ALS_G_SLAB - 1) / ALS_G_SLAB);
   if (n_slabs > 0) {
     als_gram_slab_kernel<<<(unsigned)n_slabs, ALS_G_THREADS, 0, (hipStream_t)stream>>>(Y, n_y, ldy, f, (float*)workspace);
-    SBR_CHECK_LAUNCH("sbr_als_gram_f32");
+    SBR_CHECK_LAUNCH(who);
   }
   als_gram_reduce_kernel<<<(unsigned)sbr_cdiv(f * f, 256), 256, 0, (hipStream_t)stream>>>((const float*)workspace, n_slabs, f, reg, G, ldg);
-  SBR_CHECK_LAUNCH("sbr_als_gram_f32");
+  SBR_CHECK_LAUNCH(who);
   return SBR_OK;
+}
+
+extern "C" int sbr_als_gram_f32(const float* Y, long n_y, long ldy, int f, float reg, float* G, long ldg, void* workspace, long workspace_bytes,
+                                void* stream) {
+  SBR_REQUIRE(f < 1 || f > ALS_F_MAX || als_pos_finite(reg), "sbr_als_gram_f32: reg=%g is not positive and finite", (double)reg);
+  return als_gram_launch("sbr_als_gram_f32", Y, n_y, ldy, f, reg, G, ldg, workspace, workspace_bytes, stream);
+}
+
+// G = Y^T Y for the truncated SVD (csrc/svd.hip): the same two launches with nothing added to the diagonal, the same workspace query
+extern "C" int sbr_gram_f32(const float* Y, long n_y, long ldy, int f, float* G, long ldg, void* workspace, long workspace_bytes, void* stream) {
+  return als_gram_launch("sbr_gram_f32", Y, n_y, ldy, f, 0.f, G, ldg, workspace, workspace_bytes, stream);
 }
 
 // ---- x_r = A_r^-1 b_r, one workgroup per row -------------------------------------------------------------------------------------------

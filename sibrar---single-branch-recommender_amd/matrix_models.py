@@ -8,7 +8,7 @@ skeleton are written here once. ``model.npz`` holds the model, not ``pred_mtx``,
 
 A model writes: its constructor, ``fit``, ``_score_rows``, the class-level names below and ``build_from_conf``.
 
-``FactorModel`` is the other kind: the model is two factor matrices (ALS), nothing stays resident after ``fit``, and the hooks hand out
+``FactorModel`` is the other kind: the model is two factor matrices (ALS, SVD), nothing stays resident after ``fit``, and the hooks hand out
 plain tensors.
 """
 from __future__ import annotations

@@ -1398,6 +1398,104 @@ def als_solve_rows(csr, Y: torch.Tensor, G: torch.Tensor, alpha: float, out=None
     return out
 
 
+# ---- truncated SVD by block subspace iteration (csrc/svd.hip) -----------------------------------------------------------------------
+SVD_MAX_BLOCK = 128
+_EIG_WS = {}
+
+
+def _block_width(who, c):
+    if not 1 <= c <= SVD_MAX_BLOCK:
+        raise ValueError(f'{who}: {c} columns, outside [1, {SVD_MAX_BLOCK}]')
+
+
+def gram(Y: torch.Tensor) -> torch.Tensor:
+    """``Y^T Y`` as float32 [f, f] for ``Y`` [n, f], f <= 128 (``sbr_gram_f32``: ``als_gram``'s kernels with nothing added to the
+    diagonal; symmetric bit for bit, the same bits on every run)."""
+    _need_cuda(Y)
+    n, f, ldy = _f32_rows_view('gram', 'Y', Y)
+    _block_width('gram', f)
+    need = (int(lib().sbr_als_gram_f32_workspace(n, f)) + 3) // 4
+    ws = _device_ws(_ALS_WS, Y.device, need, torch.float32) if need else None
+    G = torch.empty(f, f, device=Y.device, dtype=torch.float32)
+    call('sbr_gram_f32', ptr(Y), n, ldy, f, ptr(G), f, ptr(ws), 4 * ws.numel() if need else 0, stream())
+    return G
+
+
+def sym_eig(A: torch.Tensor, info: Optional[torch.Tensor] = None):
+    """``(lam [n] descending, W [n, n])`` with ``A = W diag(lam) W^T`` for a symmetric float32 ``A`` [n, n] (a square row-major view,
+    its lower triangle is read), 1 <= n <= 128, by the one-workgroup Jacobi of ``sbr_sym_eig_f32`` (iterated in double, rounded once); every eigenvector's component of
+    largest magnitude is positive. The same bits on every run. Raises ``SibrarHipError`` when the sweep cap was reached with rotations
+    still happening. ``info``: the device int32 [1] the kernel reports into instead of a fresh zero (tests: a word that is set on entry
+    stands for a run that did not converge). Reads one int32 back: synchronises with the stream."""
+    _need_cuda(A, info)
+    n, _, lda = _f32_rows_view('sym_eig', 'A', A, square=True)
+    _block_width('sym_eig', n)
+    if info is None:
+        info = torch.zeros(1, device=A.device, dtype=torch.int32)
+    elif info.dtype != torch.int32 or info.numel() != 1:
+        raise ValueError(f'sym_eig: info must be one int32, got {info.dtype} {tuple(info.shape)}')
+    W = torch.empty(n, n, device=A.device, dtype=torch.float32)
+    lam = torch.empty(n, device=A.device, dtype=torch.float32)
+    ws = _device_ws(_EIG_WS, A.device, int(lib().sbr_sym_eig_f32_workspace(n)) // 8, torch.float64)
+    call('sbr_sym_eig_f32', ptr(A), n, lda, ptr(W), n, ptr(lam), ptr(info), ptr(ws), 8 * ws.numel(), stream())
+    bad = int(info.item())
+    if bad:
+        from ._lib import SibrarHipError
+        raise SibrarHipError(f'sym_eig: the Jacobi iteration on the [{n}, {n}] matrix still rotated in sweep {bad - 1}, its last (info = '
+                             f'{bad}): the matrix holds non-finite values, or is no symmetric matrix of float32 numbers')
+    return lam, W
+
+
+def csr_times_dense(csr, D: torch.Tensor, out=None, rows=None) -> torch.Tensor:
+    """``X @ D`` as float32 [n, c] for the resident ``features.DeviceCSR`` (or a namespace with ``shape``, ``indptr``, ``indices``,
+    ``data``) X [n, n_d] and ``D`` [n_d, c], c <= 128, over the rows ``rows=(r0, r1)`` (None: every row) — ``sbr_csr_times_dense_f32``:
+    one fmaf chain per element in ascending CSR order, the same bits for every split of the rows. ``out``: a float32 [n, c] view with
+    unit column stride to write into (the rows outside the range keep what they hold; those of a new result are zero)."""
+    _need_cuda(csr.indptr, D, out)
+    n, n_d = csr.shape
+    nd, c, ldd = _f32_rows_view('csr_times_dense', 'D', D)
+    if nd != n_d:
+        raise ValueError(f'csr_times_dense: D has {nd} rows, the matrix {n_d} columns')
+    _block_width('csr_times_dense', c)
+    r0, r1, whole = _row_range(rows, n)
+    if not 0 <= r0 <= r1 <= n:
+        raise ValueError(f'csr_times_dense: row range [{r0}, {r1}) outside [0, {n}]')
+    out, ldo = _rows_out('csr_times_dense', out, (n, c), whole, D.device)
+    call('sbr_csr_times_dense_f32', ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), r0, r1, ptr(D), n_d, ldd, c, ptr(out), ldo, stream())
+    return out
+
+
+def rotate_cols(Y: torch.Tensor, W: torch.Tensor, lam: Optional[torch.Tensor] = None, out=None):
+    """``Y W diag(1 / s)`` with ``s = sqrt(max(lam, tiny))`` -> ``(out [n, b], s [b])``, or the plain ``Y W`` -> ``out`` when ``lam``
+    is None (``sbr_rotate_cols_f32``: an fp32 fmaf chain per element in ascending k). ``Y`` [n, b] and ``out`` are float32 views with
+    unit column stride; ``out`` may be ``Y`` itself. ``W`` float32 [b, b], ``lam`` float32 [b], as ``sym_eig`` returns them."""
+    _need_cuda(Y, W, lam, out)
+    n, b, ldy = _f32_rows_view('rotate_cols', 'Y', Y)
+    _block_width('rotate_cols', b)
+    ldw = _f32_rows_view('rotate_cols', 'W', W, (b, b))[2]
+    if lam is not None and (lam.dtype != torch.float32 or tuple(lam.shape) != (b,) or not lam.is_contiguous()):
+        raise ValueError(f'rotate_cols: lam must be a contiguous float32 [{b}], got {lam.dtype} {tuple(lam.shape)}')
+    out, ldo = _rows_out('rotate_cols', out, (n, b), True, Y.device)
+    s = None if lam is None else torch.empty(b, device=Y.device, dtype=torch.float32)
+    call('sbr_rotate_cols_f32', ptr(Y), n, ldy, b, ptr(W), ldw, ptr(lam), ptr(s), ptr(out), ldo, stream())
+    return out if lam is None else (out, s)
+
+
+def col_residual(Y: torch.Tensor, U: torch.Tensor, s: torch.Tensor, f: int) -> torch.Tensor:
+    """``||Y[:, j] - s[j] U[:, j]||_2`` for j < f as float32 [f] (``sbr_col_residual_f32``, fixed order); ``Y`` and ``U`` float32
+    [n, >= f] views with unit column stride, ``s`` a contiguous float32 vector of at least f elements."""
+    _need_cuda(Y, U, s)
+    n, cy, ldy = _f32_rows_view('col_residual', 'Y', Y)
+    nu, cu, ldu = _f32_rows_view('col_residual', 'U', U)
+    if nu != n or not 1 <= f <= min(cy, cu, SVD_MAX_BLOCK) or s.dtype != torch.float32 or s.dim() != 1 or s.numel() < f or not s.is_contiguous():
+        raise ValueError(f'col_residual: f={f} columns of Y {tuple(Y.shape)}, U {tuple(U.shape)} and s {s.dtype} {tuple(s.shape)} are asked for')
+    need = (int(lib().sbr_col_residual_f32_workspace(n, f)) + 3) // 4
+    ws = _device_ws(_ALS_WS, Y.device, need, torch.float32) if need else None
+    res = torch.empty(f, device=Y.device, dtype=torch.float32)
+    call('sbr_col_residual_f32', ptr(Y), ldy, ptr(U), ldu, ptr(s), n, f, ptr(res), ptr(ws), 4 * ws.numel() if need else 0, stream())
+    return res
+
+
 class BiasScoreFn(Function):
     """out[b, n] = base[b, n] + user_bias[u[b]] + item_bias[i[b, n]] + global_bias (sgd_alg.py:186-194, 110-119); every term
     optional (None). Bias tables are 1-D float views of the [n, 1] embedding weights. u None: row b; i None: column n."""
