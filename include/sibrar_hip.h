@@ -809,6 +809,60 @@ int sbr_col_residual_f32(const float* Y, long ldy, const float* U, long ldu, con
 /* bytes of `workspace` for sbr_col_residual_f32: ceil(n / 256) partial sums [f] of fp32. New (additive to ABI 4). */
 long sbr_col_residual_f32_workspace(long n, int f);
 
+/* ---- RBMF: representative rows by maxvol, and the ridge solve (csrc/rbmf.hip) --------------------------------------------------------
+ * algorithms/mf_algs.py:168-186 picks `indxs, _ = maxvolpy.maxvol.maxvol(u)` from the left singular vectors u [n, r] and solves
+ * X = matrix C^T inv(C C^T + lam I) with C = matrix[indxs]. maxvol (Goreinov, Oseledets, Savostyanov, Tyrtyshnikov, Zamarashkin 2010):
+ * start from the pivot rows of a row-pivoted LU of u, form B = u inv(u[idx]), and while the largest |B_ij| exceeds tol put row i in
+ * place of basis row j. Both loops are chains of launches: a launch leaves one candidate per slab of `slab_rows` rows (0: 256; at most
+ * 1,024) for the arg-max of the next, whose workgroups all reduce every candidate again and so agree; no cooperative launch, and no
+ * workgroup waits for another. Every arg-max takes the largest magnitude, then the lowest row, then the lowest column; a NaN never
+ * wins. fp32, no float atomics, one owner and one stated order per element: the same bits on every run and for every slab_rows, valid
+ * in deterministic mode, whatever the deterministic switch says.
+ *
+ * bytes of `workspace` of both chains: 4 (6 ceil(n / slab) + n + 4) — two generations of per-slab candidates, a state word per row
+ * and the largest pivot so far; 0 for an n outside [1, 2^31 - 2] or a slab_rows outside [0, 1024]. The LU chain owns it from its
+ * step 0 to its last step, a swap chain from its step 0 on. New (additive to ABI 4). */
+long sbr_maxvol_f32_workspace(long n, int slab_rows);
+/* Step k of the row-pivoted LU of A fp32 [n, r] (leading dimension lda), in place, 1 <= r <= 128, n >= r (mf_algs.py:168-186: the
+ * start of maxvol). Call it for k = 0 .. r - 1 on one stream with the same arguments; nothing is read back in between. k = 0 first
+ * marks every row as not chosen and leaves the candidates of column 0. Step k: the pivot is the row not yet chosen with the largest
+ * |a_ik|; idx[k] <- that row; every other row i not yet chosen stores l = a_ik / p_kk in place of a_ik and takes
+ * a_ij <- fmaf(-l, p_kj, a_ij) for j > k (p: the pivot row, which is final by then). A pivot whose magnitude is zero or not above
+ * r * 2^-24 * (the largest pivot magnitude of the steps before) sets *info to k + 1 unless it is set already (zero on entry; an error
+ * return, not a fault: the chain runs on): the block has numerical rank below r. The step k = r - 1 also unpacks: A becomes the unit
+ * lower factor L over all rows (a pivot row's diagonal element 1, zeros behind it), Ltop [r, r] (ldl) its pivot rows in pivot order,
+ * and Utop [r, r] (ldu; may be NULL) the upper factor, so that A_in[idx] = Ltop Utop. Only the n x r view of A is written.
+ * New (additive to ABI 4). */
+int sbr_maxvol_lu_step_f32(float* A, long n, long lda, int r, int k, int* idx, float* Ltop, long ldl, float* Utop, long ldu, int* info,
+                           void* workspace, long workspace_bytes, int slab_rows, void* stream);
+/* out[i, 0:r] = in[i, 0:r] T^-1 for the n rows of `in` (ldi) with T fp32 [r, r] triangular (ldt), 1 <= r <= 128; upper = 0: the lower
+ * triangle of T is read, 1: the upper one; unit = 1: the diagonal is taken as 1 and not read. T is staged once per workgroup in LDS on
+ * a padded row stride (r | 1 floats: 66 KiB at r = 128, two workgroups per CU); a wave owns a row. x T = b by columns: lower T, j
+ * descending: x_j = b_j / T_jj (one division; none when unit), then b_m <- fmaf(-x_j, T[j][m], b_m) for every m < j; upper T: j
+ * ascending and m > j. out may be `in` itself (a wave reads its row before it writes it). It serves mf_algs.py:168-186 three times:
+ * B = L Ltop^-1 = u inv(u[idx]) with no r x r inverse ever formed, and X = (M R^-T) R^-1 with C C^T + lam I = R R^T.
+ * New (additive to ABI 4). */
+int sbr_tri_solve_rows_f32(const float* in, long ldi, long n, int r, const float* T, long ldt, int upper, int unit, float* out, long ldo,
+                           void* stream);
+/* Iteration s of maxvol's swap loop (mf_algs.py:168-186) on B fp32 [n, r] = u inv(u[idx]) (ldb), in place. Call it for s = 0, 1, ..
+ * on one stream; s = 0 first derives the rows' state from idx and leaves the candidates of B as it is. The rows of the basis are not
+ * stored: row idx[c] stands for e_c, and what B holds of it is neither read nor written. Iteration s takes the largest |B_ij| over the
+ * other rows. If it is <= tol the launch leaves B, idx and *n_swaps alone and only hands the candidates on: a converged chain idles.
+ * Otherwise row i replaces idx[j]: w_c = (B_ic - [c = j]) / B_ij (one subtraction, one division), every other row m outside the basis
+ * takes B_mc <- fmaf(-B_mj, w_c, B_mc) with the B_mj of before the update, the row that leaves the basis becomes fmaf(-1, w_c, [c = j]),
+ * idx[j] <- i and *n_swaps is raised by one (a device int32 the caller zeroes). tol must be finite and >= 1 (the largest |B_ij| is
+ * never below 1). One launch makes at most one swap, so the caller bounds the swaps by the launches it enqueues.
+ * New (additive to ABI 4). */
+int sbr_maxvol_swap_step_f32(float* B, long n, long ldb, int r, float tol, int s, int* idx, int* n_swaps, void* workspace,
+                             long workspace_bytes, int slab_rows, void* stream);
+/* K = R R^T for a symmetric positive definite fp32 K [n, n], 1 <= n <= 128 (ldk; the lower triangle is read): the ridge system
+ * C C^T + lam I of mf_algs.py:168-186. One workgroup factors it in LDS by the unpivoted Cholesky by columns of sbr_als_solve_rows_f32
+ * (the same device function, csrc/chol_lds.h): q = K[p][p] - sum_{k<p} R[p][k]^2 and s_i = K[i][p] - sum_{k<p} R[i][k] R[p][k] as fmaf
+ * chains in ascending k, R[p][p] = sqrtf(q), R[i][p] = s_i / R[p][p]. R [n, n] (ldr) is written whole, zeros above the diagonal.
+ * info: one device int32, zero on entry; the first pivot p with q <= 0 or not finite sets it to p + 1 (an error return, not a fault; R
+ * is then unspecified). New (additive to ABI 4). */
+int sbr_chol_f32(const float* K, int n, long ldk, float* R, long ldr, int* info, void* stream);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

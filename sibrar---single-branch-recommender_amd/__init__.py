@@ -26,6 +26,7 @@ from .ease import EASE                                                          
 from .p3alpha import P3alpha                                                                # noqa: F401
 from .als import AlternatingLeastSquare                                                     # noqa: F401
 from .svd import SVDAlgorithm                                                               # noqa: F401
+from .rbmf import RBMF                                                                      # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
                      RecSampledSoftmaxLoss, RecommenderSystemLoss, RecommenderSystemLossesEnum)
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
@@ -52,10 +53,10 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
     ops.set_deterministic(deterministic)
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
-# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ease / .p3alpha / .als / .svd -> class
+# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ease / .p3alpha / .als / .svd / .rbmf -> class
 # (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
               'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ease': EASE,
-              'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm}
+              'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF}

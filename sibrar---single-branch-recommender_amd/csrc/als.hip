@@ -7,6 +7,7 @@
 // factorisation and the two substitutions are fixed sequences, so both entry points give the same bits on every run, for every split of
 // the row range, and are valid in deterministic mode. tests/als_ref.py restates the update in float64 and in float32.
 #include "common.h"
+#include "chol_lds.h"
 
 #define ALS_F_MAX 128
 #define ALS_TILE 8                    // a thread's register tile of A_r / G: 8 x 8
@@ -126,8 +127,7 @@ extern "C" int sbr_gram_f32(const float* Y, long n_y, long ldy, int f, float* G,
 #define ALS_CHUNK 24                  // observed entries staged at a time: 12 KiB, so that two workgroups fit one CU's 160 KiB at f = 128
 #define ALS_FIXED (ALS_CHUNK * ALS_YS + 32 + 32 + ALS_F_MAX + ALS_F_MAX)          // floats of LDS in front of A
 
-// odd row stride of A in LDS: a walk down a column (stride lda) and 64 rows at the same column both touch every bank once
-__host__ __device__ static inline int als_lda(int f) { return f | 1; }
+__host__ __device__ static inline int als_lda(int f) { return sbr_chol_lda(f); }      // the odd row stride of A in LDS
 static inline size_t als_lds_bytes(int f) { return 4 * ((size_t)ALS_FIXED + (size_t)(f + 1) * als_lda(f)); }
 
 // *info <- v if it is still 0 or holds a larger value: the smallest 1 + r over the rows that met a bad pivot, whatever the arrival order
@@ -215,30 +215,8 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_rows_kernel(const long*
   }
   if (t < f) A[f * lda + t] = bacc;
   __syncthreads();
-  // ---- unpivoted Cholesky by columns (Cholesky-Crout), b_r carried as row f: thread t owns row t. Column p: every owner of a row >= p
-  // walks row p (a broadcast read) and its own row, so it also has the pivot q = A[p][p] - sum_k L[p][k]^2 in the same bits as everybody
-  // else, and one barrier per column is enough. ----
-  for (int p = 0; p < f; ++p) {
-    if (t >= p && t <= f) {
-      const float* rp = A + p * lda;
-      float* ri = A + t * lda;
-      float s = ri[p], q = rp[p];
-      for (int k = 0; k < p; ++k) {
-        const float lp = rp[k];
-        s = fmaf(-ri[k], lp, s);
-        q = fmaf(-lp, lp, q);
-      }
-      const bool ok = q > 0.f && q <= 3.402823466e+38f;
-      const float d = ok ? sqrtf(q) : 1.f;                          // a bad pivot: reported, and the row goes on with d = 1 (output unspecified)
-      if (t == p) {
-        diag[p] = d;
-        if (!ok) als_report(info, (int)(1 + r));
-      } else {
-        ri[p] = s / d;
-      }
-    }
-    __syncthreads();
-  }
+  // ---- unpivoted Cholesky by columns (chol_lds.h), b_r carried as row f: thread t owns row t ----
+  sbr_chol_lds(A, lda, f, f + 1, diag, t, [=](int) { als_report(info, (int)(1 + r)); });
   // ---- L^T x = z by columns, p descending: thread t owns x[t] ----
   float z = t < f ? A[f * lda + t] : 0.f;
   for (int p = f - 1; p >= 0; --p) {

@@ -8,7 +8,7 @@ skeleton are written here once. ``model.npz`` holds the model, not ``pred_mtx``,
 
 A model writes: its constructor, ``fit``, ``_score_rows``, the class-level names below and ``build_from_conf``.
 
-``FactorModel`` is the other kind: the model is two factor matrices (ALS, SVD), nothing stays resident after ``fit``, and the hooks hand out
+``FactorModel`` is the other kind: the model is two factor matrices (ALS, SVD, RBMF), nothing stays resident after ``fit``, and the hooks hand out
 plain tensors.
 """
 from __future__ import annotations
@@ -169,11 +169,13 @@ class ResidentMatrixAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
 
 class FactorModel(SparseMatrixBasedRecommenderAlgorithm):
     """The model is two float32 factor matrices, ``users_factors`` [n_users, f] and ``items_factors`` [n_items, f], and the score their dot
-    product (algorithms/mf_algs.py: ALS, SVD). Nothing of the interaction matrix is needed to score, so a loaded model needs no ``attach``,
+    product (algorithms/mf_algs.py: ALS, SVD, RBMF). Nothing of the interaction matrix is needed to score, so a loaded model needs no ``attach``,
     and both sides of the evaluation hooks are plain tensors: the fused scorers serve such a model. ``model.npz`` holds the reference's two
     fields and ``name``; a file written by the reference (no ``name``) loads as is. ``kwargs`` of every model: ``device``.
 
-    A model writes: its constructor, ``fit`` and ``build_from_conf``."""
+    A model writes: its constructor, ``fit`` and ``build_from_conf``; RBMF also names its two fields of ``model.npz``."""
+    USERS_FIELD = 'users_factors'       # the reference's names of the two arrays in model.npz (algorithms/mf_algs.py:52-55, :127-130;
+    ITEMS_FIELD = 'items_factors'       # RBMF: X and C, :197-200)
 
     def __init__(self, device=None):
         super().__init__()
@@ -216,19 +218,19 @@ class FactorModel(SparseMatrixBasedRecommenderAlgorithm):
     # ---- persistence -------------------------------------------------------------------------------------------------------------------
     def save_model_to_path(self, path: str):
         self._need_fit()
-        np.savez(os.path.join(path, 'model.npz'), users_factors=self.users_factors.cpu().numpy(), items_factors=self.items_factors.cpu().numpy(),
-                 name=np.array(self.name))
+        np.savez(os.path.join(path, 'model.npz'), **{self.USERS_FIELD: self.users_factors.cpu().numpy(),
+                                                     self.ITEMS_FIELD: self.items_factors.cpu().numpy()}, name=np.array(self.name))
         print('Model Saved')
 
     def load_model_from_path(self, path: str):
         with np.load(os.path.join(path, 'model.npz'), allow_pickle=False) as f:
-            if 'pred_mtx' in f.files or 'users_factors' not in f.files or 'items_factors' not in f.files:
+            if 'pred_mtx' in f.files or self.USERS_FIELD not in f.files or self.ITEMS_FIELD not in f.files:
                 raise ValueError(f'{os.path.join(path, "model.npz")} is not a model of this package (it holds {f.files}): the reference '
                                  f'stores its pickled prediction matrix `pred_mtx`, this package the two factor matrices; fit the model again')
             name = str(f['name']) if 'name' in f.files else self.name           # the reference's files carry no name
             if name != self.name:
                 raise ValueError(f'model.npz holds a {name}, this model is a {self.name}')
-            u, i = f['users_factors'], f['items_factors']
+            u, i = f[self.USERS_FIELD], f[self.ITEMS_FIELD]
             if u.ndim != 2 or i.ndim != 2 or u.shape[1] != i.shape[1]:
                 raise ValueError(f'model.npz: factor matrices of shapes {u.shape} and {i.shape} do not belong together')
             self.users_factors = torch.from_numpy(u.astype(np.float32)).to(self.device)

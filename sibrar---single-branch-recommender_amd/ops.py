@@ -1496,6 +1496,133 @@ def col_residual(Y: torch.Tensor, U: torch.Tensor, s: torch.Tensor, f: int) -> t
     return res
 
 
+# ---- RBMF: representative rows by maxvol, and the ridge solve (csrc/rbmf.hip) -------------------------------------------------------------
+MAXVOL_MAX_R = 128
+MAXVOL_GROUP = 16                 # swap launches enqueued between two read-backs of the swap counter
+_MAXVOL_WS = {}
+
+
+def tri_solve_rows(X: torch.Tensor, T: torch.Tensor, upper: bool = False, unit: bool = False, out=None) -> torch.Tensor:
+    """``X T^-1`` row by row for ``X`` float32 [n, r] and a triangular ``T`` float32 [r, r], r <= 128 (``sbr_tri_solve_rows_f32``: T in
+    LDS, a wave per row, one fmaf chain per element). ``upper``: which triangle of ``T`` is read; ``unit``: its diagonal is taken as 1.
+    ``X``, ``T`` and ``out`` are views with unit column stride; ``out`` may be ``X`` itself."""
+    _need_cuda(X, T, out)
+    n, r, ldx = _f32_rows_view('tri_solve_rows', 'X', X)
+    if not 1 <= r <= MAXVOL_MAX_R:
+        raise ValueError(f'tri_solve_rows: {r} columns, outside [1, {MAXVOL_MAX_R}]')
+    ldt = _f32_rows_view('tri_solve_rows', 'T', T, (r, r))[2]
+    out, ldo = _rows_out('tri_solve_rows', out, (n, r), True, X.device)
+    call('sbr_tri_solve_rows_f32', ptr(X), ldx, n, r, ptr(T), ldt, int(bool(upper)), int(bool(unit)), ptr(out), ldo, stream())
+    return out
+
+
+def cholesky(K: torch.Tensor) -> torch.Tensor:
+    """The lower triangular ``R`` float32 [n, n] with ``K = R R^T`` for a symmetric positive definite float32 ``K`` (a square row-major
+    view whose lower triangle is read), n <= 128 — ``sbr_chol_f32``, the LDS factorisation of ``als_solve_rows``. Raises
+    ``SibrarHipError`` naming the first pivot that is not positive in float32. Reads one int32 back: synchronises with the stream."""
+    _need_cuda(K)
+    n, _, ldk = _f32_rows_view('cholesky', 'K', K, square=True)
+    if not 1 <= n <= MAXVOL_MAX_R:
+        raise ValueError(f'cholesky: a [{n}, {n}] matrix, outside [1, {MAXVOL_MAX_R}]')
+    R = torch.empty(n, n, device=K.device, dtype=torch.float32)
+    info = torch.zeros(1, device=K.device, dtype=torch.int32)
+    call('sbr_chol_f32', ptr(K), n, ldk, ptr(R), n, ptr(info), stream())
+    bad = int(info.item())
+    if bad:
+        from ._lib import SibrarHipError
+        raise SibrarHipError(f'cholesky: the [{n}, {n}] matrix is not positive definite in float32 (pivot {bad - 1} of its Cholesky '
+                             f'factorisation is not positive): raise the ridge term well above n * 2^-24 * ||K||')
+    return R
+
+
+def _maxvol_ws(device, n, slab_rows):
+    need = int(lib().sbr_maxvol_f32_workspace(n, slab_rows))
+    if need == 0:
+        raise ValueError(f'maxvol: slab_rows={slab_rows} outside [0, 1024] (n = {n})')
+    return _device_ws(_MAXVOL_WS, device, need // 4, torch.int32)
+
+
+def maxvol_lu(A: torch.Tensor, slab_rows: int = 0, want_upper: bool = False):
+    """The row-pivoted LU of ``A`` float32 [n, r] (n >= r, r <= 128), IN PLACE, by r launches of ``sbr_maxvol_lu_step_f32`` with no
+    read-back in between -> ``(idx int32 [r], L_top [r, r], U_top [r, r] or None)``: the pivot rows in pivot order, ``A`` overwritten
+    with the unit lower factor over all rows, its pivot rows, and (``want_upper``) the upper factor: ``A_in[idx] = L_top U_top``. Raises
+    ``SibrarHipError`` naming the first step whose pivot is not above r * 2^-24 * the largest pivot before it: the block has numerical
+    rank below r. Reads one int32 back: synchronises with the stream."""
+    _need_cuda(A)
+    n, r, lda = _f32_rows_view('maxvol_lu', 'A', A)
+    if not 1 <= r <= MAXVOL_MAX_R or n < r:
+        raise ValueError(f'maxvol_lu: a [{n}, {r}] matrix; 1 <= r <= {MAXVOL_MAX_R} and n >= r are needed')
+    ws = _maxvol_ws(A.device, n, slab_rows)
+    idx = torch.empty(r, device=A.device, dtype=torch.int32)
+    ltop = torch.empty(r, r, device=A.device, dtype=torch.float32)
+    utop = torch.empty(r, r, device=A.device, dtype=torch.float32) if want_upper else None
+    info = torch.zeros(1, device=A.device, dtype=torch.int32)
+    for k in range(r):
+        call('sbr_maxvol_lu_step_f32', ptr(A), n, lda, r, k, ptr(idx), ptr(ltop), r, ptr(utop), r, ptr(info), ptr(ws), 4 * ws.numel(),
+             int(slab_rows), stream())
+    bad = int(info.item())
+    if bad:
+        from ._lib import SibrarHipError
+        raise SibrarHipError(f'maxvol_lu: the pivot of step {bad - 1} of the row-pivoted LU of the [{n}, {r}] block is not above r * 2^-24 * '
+                             f'the largest pivot before it (or is not finite): the block has numerical rank below {r} in float32; ask for '
+                             f'fewer representatives')
+    return idx, ltop, utop
+
+
+def _maxvol_basis(U, idx, slab_rows):
+    """``U inv(U[idx])`` from ``idx`` alone: G = U[idx] = P^T L_top U_top by the LU of the r gathered rows, two triangular solves, and
+    the columns put back in basis order (Y[idx[piv[s]]] = e_s, and row idx[c] of the result has to be e_c)"""
+    G = U[idx.long()].contiguous()
+    piv, gl, gu = maxvol_lu(G, slab_rows, want_upper=True)
+    Y = tri_solve_rows(tri_solve_rows(U, gu, upper=True, unit=False), gl, upper=False, unit=True)
+    B = torch.empty_like(Y)
+    B[:, piv.long()] = Y
+    return B
+
+
+def maxvol(U: torch.Tensor, tol: float = 1.05, max_iters: int = 100, slab_rows: int = 0, start=None):
+    """``maxvolpy.maxvol.maxvol(U)`` (algorithms/mf_algs.py:177) for ``U`` float32 [n, r], n >= r, r <= 128 -> ``(idx int64 [r],
+    n_swaps)``: r rows whose r x r submatrix has locally maximal volume, ``max |U inv(U[idx])| <= tol`` unless ``max_iters`` swaps were
+    not enough. The start is the pivot rows of a row-pivoted LU (``maxvol_lu``), ``B = L L_top^-1`` (``tri_solve_rows``), then
+    ``sbr_maxvol_swap_step_f32`` in groups of ``MAXVOL_GROUP`` launches, the swap counter read back once per group. When a chain has
+    stopped after swaps, B is computed afresh from ``idx`` (an LU of the r gathered rows, two triangular solves) and the chain goes on
+    if the fresh maximum is still above ``tol``. ``U`` is not written. The same bits, and the same ``idx``, on every run and for every
+    ``slab_rows`` (0: the default of the header). ``start``: r distinct row indices to start from instead of the LU's pivots (tests)."""
+    _need_cuda(U)
+    n, r, _ = _f32_rows_view('maxvol', 'U', U)
+    if not 1 <= r <= MAXVOL_MAX_R or n < r:
+        raise ValueError(f'maxvol: a [{n}, {r}] matrix; 1 <= r <= {MAXVOL_MAX_R} and n >= r are needed')
+    if not (tol >= 1 and tol < float('inf')):
+        raise ValueError(f'maxvol: tol ({tol}) has to be a finite number >= 1')
+    if int(max_iters) != max_iters or max_iters < 0:
+        raise ValueError(f'maxvol: max_iters ({max_iters}) has to be a non-negative integer')
+    if start is None:
+        B = U.clone(memory_format=torch.contiguous_format)
+        idx, ltop, _ = maxvol_lu(B, slab_rows)
+        tri_solve_rows(B, ltop, upper=False, unit=True, out=B)
+    else:
+        idx = torch.as_tensor(start).to(device=U.device, dtype=torch.int32).contiguous()
+        if tuple(idx.shape) != (r,) or len(set(idx.tolist())) != r or not 0 <= int(idx.min()) <= int(idx.max()) < n:
+            raise ValueError(f'maxvol: start must be {r} distinct rows below {n}')
+        B = _maxvol_basis(U, idx, slab_rows)
+    ws = _maxvol_ws(U.device, n, slab_rows)
+    counter = torch.zeros(1, device=U.device, dtype=torch.int32)
+    done, fresh = 0, True                                            # swaps so far; B was computed from idx and has seen no swap since
+    while done < max_iters:
+        group = min(MAXVOL_GROUP, int(max_iters) - done)
+        for s in range(group):
+            call('sbr_maxvol_swap_step_f32', ptr(B), n, r, r, float(tol), s, ptr(idx), ptr(counter), ptr(ws), 4 * ws.numel(), int(slab_rows),
+                 stream())
+        now = int(counter.item())
+        idle, fresh, done = now - done < group, fresh and now == done, now
+        if not idle:
+            continue                                                 # every launch of the group swapped: the chain may have more to do
+        if fresh:
+            break                                                    # a B fresh from idx holds nothing above tol
+        B, fresh = _maxvol_basis(U, idx, slab_rows), True           # drift: B again from idx alone
+    return idx.long(), done
+
+
 class BiasScoreFn(Function):
     """out[b, n] = base[b, n] + user_bias[u[b]] + item_bias[i[b, n]] + global_bias (sgd_alg.py:186-194, 110-119); every term
     optional (None). Bias tables are 1-D float views of the [n, 1] embedding weights. u None: row b; i None: column n."""

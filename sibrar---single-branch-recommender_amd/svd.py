@@ -32,6 +32,57 @@ from .features import DeviceCSR
 from .matrix_models import FactorModel
 
 
+def canonical_csr(matrix, name: str, f: int, what: str) -> sp.csr_matrix:
+    """the matrix as canonical CSR, refused when it has fewer than ``f`` singular triplets (``what``: the parameter's name) or a
+    non-finite entry"""
+    m = sp.csr_matrix(matrix).copy()
+    m.sum_duplicates()
+    m.eliminate_zeros()
+    m.sort_indices()
+    n_users, n_items = m.shape
+    if f > min(n_users, n_items):
+        raise ValueError(f'{name}: {what} ({f}) exceeds min(n_users, n_items) = {min(n_users, n_items)}: the matrix has no more '
+                         f'singular triplets')
+    if m.nnz and not bool(np.isfinite(m.data).all()):
+        raise ValueError(f'{name}: the matrix has non-finite entries')
+    return m
+
+
+def _orth(Y):
+    """(Y W diag(1 / s) in place of Y, s, W) with Y^T Y = W diag(lam) W^T"""
+    lam, W = ops.sym_eig(ops.gram(Y))
+    Y, s = ops.rotate_cols(Y, W, lam, out=Y)
+    return Y, s, W
+
+
+def block_iteration(m: sp.csr_matrix, V0: np.ndarray, f: int, n_iterations: int, tol: float, device, x=None):
+    """The block subspace iteration of the module's header on the canonical CSR ``m`` from the start ``V0`` [n_items, b] ->
+    ``(U [n_users, b], s [b], V [n_items, b], Y = X V, iterations run, residual history)``: the left singular vectors themselves (RBMF
+    selects its representatives among their rows), the singular values descending and the right singular vectors; ``U`` and ``s`` are
+    None when ``n_iterations`` is 0. The iteration stops when the largest residual of the first ``f`` triplets is ``<= tol * s_0``.
+    ``x``: X already resident (a ``DeviceCSR`` on ``device``); it is made here, for the time of the call, when None."""
+    n_users, n_items = m.shape
+    if x is None:
+        x = DeviceCSR(m).to(device)                                  # X, resident during fit only
+    t_indptr, t_indices, t_data = x.transposed()
+    xt = SimpleNamespace(shape=(n_items, n_users), indptr=t_indptr, indices=t_indices, data=t_data)      # X^T, made on the device
+    V, _, _ = _orth(torch.from_numpy(V0).to(device))
+    U = s = None
+    history = []
+    for it in range(n_iterations + 1):
+        Y = ops.csr_times_dense(x, V)
+        if it:
+            history.append(float(ops.col_residual(Y, U, s, f).max()))
+            if history[-1] <= tol * float(s[0]):
+                break
+        if it == n_iterations:
+            break
+        U, _, _ = _orth(Y)
+        V, s, W = _orth(ops.csr_times_dense(xt, U))
+        ops.rotate_cols(U, W, out=U)
+    return U, s, V, Y, it, history
+
+
 class SVDAlgorithm(FactorModel):
     """algorithms/mf_algs.py:14-66. ``factors``: the number of singular triplets kept (1 .. 128). ``kwargs``: ``device``, ``random_state``
     (the seed of the initial block, default 0), ``oversample`` (extra columns of the iterated block, default 28, clipped so that the block
@@ -64,45 +115,17 @@ class SVDAlgorithm(FactorModel):
         """-> V0 [n_items, b] float32 numpy: ``RandomState(random_state).standard_normal``, before it is orthonormalised"""
         return np.random.RandomState(self.random_state).standard_normal(size=(n_items, b)).astype(np.float32)
 
-    @staticmethod
-    def _orth(Y):
-        """(Y W diag(1 / s) in place of Y, s, W) with Y^T Y = W diag(lam) W^T"""
-        lam, W = ops.sym_eig(ops.gram(Y))
-        Y, s = ops.rotate_cols(Y, W, lam, out=Y)
-        return Y, s, W
+    _orth = staticmethod(_orth)          # (tools/time_svd.py times one iteration by hand)
 
     def fit(self, matrix: sp.spmatrix, **kwargs):
         """:param matrix: user x item sparse matrix; any finite values"""
-        m = sp.csr_matrix(matrix).copy()
-        m.sum_duplicates()
-        m.eliminate_zeros()
-        m.sort_indices()
+        m = canonical_csr(matrix, self.name, self.factors, 'factors')
         n_users, n_items = m.shape
         f = self.factors
-        if f > min(n_users, n_items):
-            raise ValueError(f'SVDAlgorithm: factors ({f}) exceeds min(n_users, n_items) = {min(n_users, n_items)}: the matrix has no more '
-                             f'singular triplets')
-        if m.nnz and not bool(np.isfinite(m.data).all()):
-            raise ValueError('SVDAlgorithm: the matrix has non-finite entries')
         b = min(f + self.oversample, n_users, n_items)
-        x = DeviceCSR(m).to(self.device)                             # X, resident during fit only
-        t_indptr, t_indices, t_data = x.transposed()
-        xt = SimpleNamespace(shape=(n_items, n_users), indptr=t_indptr, indices=t_indices, data=t_data)      # X^T, made on the device
-        V, _, _ = self._orth(torch.from_numpy(self.initial_block(n_items, b)).to(self.device))
-        U = s = None
-        history = []
-        for it in range(self.n_iterations + 1):
-            Y = ops.csr_times_dense(x, V)
-            if it:
-                history.append(float(ops.col_residual(Y, U, s, f).max()))
-                if history[-1] <= self.tol * float(s[0]):
-                    break
-            if it == self.n_iterations:
-                break
-            U, _, _ = self._orth(Y)
-            V, s, W = self._orth(ops.csr_times_dense(xt, U))
-            ops.rotate_cols(U, W, out=U)
-        self.n_iterations_run, self.residual_history = it, history
+        U, s, V, Y, self.n_iterations_run, self.residual_history = block_iteration(m, self.initial_block(n_items, b), f, self.n_iterations,
+                                                                                   self.tol, self.device)
+        history = self.residual_history
         if U is None:                                                # no iteration: the orthonormalised start and its projection
             self.users_factors, self.items_factors = Y[:, :f].contiguous(), V[:, :f].contiguous()
             self.singular_values, self.residual = torch.sqrt(torch.diagonal(ops.gram(Y))[:f]), float('inf')
