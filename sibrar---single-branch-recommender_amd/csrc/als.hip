@@ -84,8 +84,6 @@ __global__ __launch_bounds__(256) void als_gram_reduce_kernel(const float* __res
   G[(long)i * ldg + j] = s;
 }
 
-static inline bool als_pos_finite(float v) { return v > 0.f && v <= 3.402823466e+38f; }
-
 extern "C" long sbr_als_gram_f32_workspace(long n_y, int f) {
   if (n_y <= 0 || f < 1 || f > ALS_F_MAX) return 0;
   return ((n_y + ALS_G_SLAB - 1) / ALS_G_SLAB) * (long)f * f * 4;
@@ -95,7 +93,7 @@ extern "C" long sbr_als_gram_f32_workspace(long n_y, int f) {
 static int als_gram_launch(const char* who, const float* Y, long n_y, long ldy, int f, float reg, float* G, long ldg, void* workspace,
                            long workspace_bytes, void* stream) {
   SBR_REQUIRE(f >= 1 && f <= ALS_F_MAX, "%s: f=%d outside [1, %d]", who, f, ALS_F_MAX);
-  SBR_REQUIRE(reg == 0.f || als_pos_finite(reg), "%s: reg=%g is not positive and finite", who, (double)reg);
+  SBR_REQUIRE(reg == 0.f || sbr_pos_finite(reg), "%s: reg=%g is not positive and finite", who, (double)reg);
   SBR_REQUIRE(n_y >= 0 && n_y <= 2147483647L * ALS_G_SLAB, "%s: n_y=%ld out of range", who, n_y);
   SBR_REQUIRE(ldy >= f && ldg >= f, "%s: leading dimension below f=%d (ldy=%ld, ldg=%ld)", who, f, ldy, ldg);
   SBR_REQUIRE(G && (Y || n_y == 0), "%s: null operand", who);
@@ -113,7 +111,7 @@ static int als_gram_launch(const char* who, const float* Y, long n_y, long ldy, 
 
 extern "C" int sbr_als_gram_f32(const float* Y, long n_y, long ldy, int f, float reg, float* G, long ldg, void* workspace, long workspace_bytes,
                                 void* stream) {
-  SBR_REQUIRE(f < 1 || f > ALS_F_MAX || als_pos_finite(reg), "sbr_als_gram_f32: reg=%g is not positive and finite", (double)reg);
+  SBR_REQUIRE(f < 1 || f > ALS_F_MAX || sbr_pos_finite(reg), "sbr_als_gram_f32: reg=%g is not positive and finite", (double)reg);
   return als_gram_launch("sbr_als_gram_f32", Y, n_y, ldy, f, reg, G, ldg, workspace, workspace_bytes, stream);
 }
 
@@ -230,20 +228,16 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_rows_kernel(const long*
 extern "C" int sbr_als_solve_rows_f32(const long* indptr, const int* indices, const float* data, long r0, long r1, const float* Y, long n_y,
                                       long ldy, int f, const float* G, float alpha, float* X, long ldx, int* info, void* stream) {
   SBR_REQUIRE(f >= 1 && f <= ALS_F_MAX, "sbr_als_solve_rows_f32: f=%d outside [1, %d]", f, ALS_F_MAX);
-  SBR_REQUIRE(als_pos_finite(alpha), "sbr_als_solve_rows_f32: alpha=%g is not positive and finite", (double)alpha);
+  SBR_REQUIRE(sbr_pos_finite(alpha), "sbr_als_solve_rows_f32: alpha=%g is not positive and finite", (double)alpha);
   SBR_REQUIRE(ldx >= f && ldy >= f, "sbr_als_solve_rows_f32: leading dimension below f=%d (ldx=%ld, ldy=%ld)", f, ldx, ldy);
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= 2147483646L && r1 - r0 <= 2147483647L, "sbr_als_solve_rows_f32: row range [%ld, %ld) outside [0, 2^31 - 2]",
               r0, r1);
   SBR_REQUIRE(n_y >= 0, "sbr_als_solve_rows_f32: n_y=%ld is negative", n_y);
   if (r0 == r1) return SBR_OK;
   SBR_REQUIRE(indptr && indices && Y && G && X && info, "sbr_als_solve_rows_f32: null operand");
-  static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev) && hipFuncSetAttribute((const void*)als_solve_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)als_lds_bytes(ALS_F_MAX)) != hipSuccess) {
-    attr_dev = -1;
-    sbr_set_error("sbr_als_solve_rows_f32: cannot raise the dynamic LDS limit");
-    return SBR_ERR_HIP;
-  }
+  static SbrLdsSlot lds_slot;
+  const int lds_rc = sbr_raise_lds("sbr_als_solve_rows_f32", (const void*)als_solve_rows_kernel, &lds_slot, als_lds_bytes(ALS_F_MAX));
+  if (lds_rc) return lds_rc;
   als_solve_rows_kernel<<<(unsigned)(r1 - r0), ALS_THREADS, als_lds_bytes(f), (hipStream_t)stream>>>(indptr, indices, data, r0, Y, ldy, f, G, alpha,
                                                                                                  X, ldx, info);
   SBR_CHECK_LAUNCH("sbr_als_solve_rows_f32");

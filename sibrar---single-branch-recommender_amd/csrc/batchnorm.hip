@@ -6,33 +6,20 @@
 // Train backward: pass 1 column sums of dz and dz*xhat        -> ws[2*D] ; pass 2 dx = w*rstd*(dz - mean(dz) - xhat*mean(dz*xhat)).
 // HBM-bound: forward reads X twice and writes Y once (12 B/element), backward reads X, Y, dY twice and writes dX.
 #include "common.h"
-#include "det.h"
+#include "colred.h"
 
-// grid: (row chunks, column groups of 64); block 256 = 4 row lanes x 64 columns
+// generic fallback (colred.h: sbr_col_reduce_generic): sum x, sum x^2 in double
 __global__ void bn_stats_kernel(const float* __restrict__ X, long n, int D, double* __restrict__ ws) {
-  const int c = blockIdx.y * 64 + (threadIdx.x & 63);
-  const int rg = threadIdx.x >> 6;
-  double s = 0.0, ss = 0.0;
-  if (c < D)
-    for (long j = blockIdx.x * 4L + rg; j < n; j += gridDim.x * 4L) {
-      const double v = (double)X[j * D + c];
-      s += v;
-      ss += v * v;
-    }
-  __shared__ double sm[2][256];
-  sm[0][threadIdx.x] = s;
-  sm[1][threadIdx.x] = ss;
-  __syncthreads();
-  if (rg == 0 && c < D) {
-    const int t = threadIdx.x;
-    atomicAdd(&ws[c], sm[0][t] + sm[0][t + 64] + sm[0][t + 128] + sm[0][t + 192]);
-    atomicAdd(&ws[D + c], sm[1][t] + sm[1][t + 64] + sm[1][t + 128] + sm[1][t + 192]);
-  }
+  sbr_col_reduce_generic<2>(n, D, ws, [&](long j, int c, double* v) {
+    const double x = (double)X[j * D + c];
+    v[0] = x;
+    v[1] = x * x;
+  });
 }
 
-// The geometry of sbr_col_reduce<2> (common.h: same row ranges per block, same replicas, same slots in deterministic mode), but the
-// squares are formed and both sums are carried in DOUBLE from the first addition: the finaliser takes var = ss / n - m * m, whose
-// cancellation multiplies every relative error of ss and of m by (mean / std)^2. With fp32 squares and fp32 per-thread sums the
+// The vector form (colred.h: geometry and publish tail), with the squares formed and both sums carried in DOUBLE from the first
+// addition: the finaliser takes var = ss / n - m * m, whose cancellation multiplies every relative error of ss and of m by
+// (mean / std)^2. With fp32 squares and fp32 per-thread sums the
 // variance of a column with mean / std = 256 was off by 5e-4 (numerical contract of the BatchNorm statistics); with
 // exact squares of fp32 values (24 + 24 bits fit a double) and double sums it is as good as the generic kernel's. The kernel
 // stays bound by its one read of X.
@@ -45,43 +32,23 @@ __device__ __forceinline__ void bn_acc4(const float4 x, double* s, double* q) {
 __global__ __launch_bounds__(256) void bn_stats4_kernel(const float* __restrict__ X, long n, int D, double* __restrict__ ws,
                                                         double* __restrict__ slots) {
   __shared__ double sm[2][4][256];
-  const int C4 = D >> 2, RL = 256 / C4;
-  const int t = threadIdx.x, cg = t % C4, rl = t / C4;
-  const long chunk = (n + gridDim.x - 1) / gridDim.x;
-  const long lo = blockIdx.x * chunk, hi = (lo + chunk < n) ? lo + chunk : n;
+  const SbrColGeom g(n, D);
+  const int RL = g.RL, t = threadIdx.x;
   double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
-  if (rl < RL) {
-    const float* xp = X + 4 * cg;
-    long j = lo + rl;
-    for (; j + 3L * RL < hi; j += 4L * RL) {       // four independent 16-byte loads in flight
+  if (g.rl < RL) {
+    const float* xp = X + 4 * g.cg;
+    long j = g.lo + g.rl;
+    for (; j + 3L * RL < g.hi; j += 4L * RL) {       // four independent 16-byte loads in flight
       const float4 x0 = *reinterpret_cast<const float4*>(xp + j * D), x1 = *reinterpret_cast<const float4*>(xp + (j + RL) * D),
                    x2 = *reinterpret_cast<const float4*>(xp + (j + 2L * RL) * D), x3 = *reinterpret_cast<const float4*>(xp + (j + 3L * RL) * D);
       bn_acc4(x0, s, q); bn_acc4(x1, s, q); bn_acc4(x2, s, q); bn_acc4(x3, s, q);
     }
-    for (; j < hi; j += RL) bn_acc4(*reinterpret_cast<const float4*>(xp + j * D), s, q);
+    for (; j < g.hi; j += RL) bn_acc4(*reinterpret_cast<const float4*>(xp + j * D), s, q);
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) { sm[0][i][t] = s[i]; sm[1][i][t] = q[i]; }
   __syncthreads();
-  if (t < C4) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      double o4[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        double a = 0.0;
-        for (int r = 0; r < RL; ++r) a += sm[k][i][r * C4 + t];
-        o4[i] = a;
-      }
-      if (slots) {               // deterministic mode: this block's own slot, plain stores (det.h: sbr_det_fold_slots adds the slots)
-        double* o = slots + (long)blockIdx.x * 2 * D + (long)k * D + 4 * t;
-        o[0] = o4[0]; o[1] = o4[1]; o[2] = o4[2]; o[3] = o4[3];
-        continue;
-      }
-      double* o = ws + (long)(1 + (blockIdx.x % SBR_COLRED_REP)) * 2 * D + (long)k * D + 4 * t;
-      atomicAdd(o, o4[0]); atomicAdd(o + 1, o4[1]); atomicAdd(o + 2, o4[2]); atomicAdd(o + 3, o4[3]);
-    }
-  }
+  sbr_colred_publish(sm, g, D, ws, slots);
 }
 
 // one thread per column: batch mean / rstd, running-stat update
@@ -122,27 +89,15 @@ static int grid1d(long total) {
   return b > 4096 ? 4096 : (b < 1 ? 1 : b);
 }
 
-// workspace ws: 34*D doubles (2*D totals + 16 replicas, see sbr_col_reduce in common.h), ZERO on first use; every call
+// workspace ws: 34*D doubles (2*D totals + 16 replicas, see colred.h), ZERO on first use; every call
 // leaves the replica part zeroed again (no memset per call)
 static int bn_train_stats(const float* X, long n, int D, float* running_mean, float* running_var, long* num_batches_tracked,
                           float* save_mean, float* save_rstd, double* ws, float eps, float momentum, hipStream_t s) {
-  if (sbr_det_on()) {            // fixed-slot form: one slot per block, folded into replica 1 in slot order
-    SBR_REQUIRE(sbr_col_reduce_ok(X, D, D), "sbr_bn_train_fwd/stats: no deterministic form for D=%d (needs D %% 4 == 0, D <= 1024, 16-byte aligned rows)", D);
-    const int nb = sbr_col_reduce_blocks(n, D);
-    double* slots = (double*)sbr_det_scratch(SBR_SCRATCH_COLRED, (size_t)nb * 2 * D * sizeof(double), s, "sbr_bn_train_fwd/stats");
-    if (!slots) return SBR_ERR_HIP;
-    bn_stats4_kernel<<<nb, 256, 0, s>>>(X, n, D, ws, slots);
-    const int rc = sbr_det_fold_slots(slots, nb, 2 * D, ws, s, "sbr_bn_train_fwd/stats");
-    if (rc) return rc;
-  } else if (sbr_col_reduce_ok(X, D, D)) {
-    sbr_note_arrival_order();
-    bn_stats4_kernel<<<sbr_col_reduce_blocks(n, D), 256, 0, s>>>(X, n, D, ws, nullptr);
-  } else {                       // generic path: atomics straight into replica 1
-    sbr_note_arrival_order();
-    int bx = sbr_cdiv(n, 64);
-    if (bx > 512) bx = 512;
-    bn_stats_kernel<<<dim3(bx, sbr_cdiv(D, 64)), 256, 0, s>>>(X, n, D, ws + 2 * D);
-  }
+  const int rc = sbr_colred_dispatch(
+      "sbr_bn_train_fwd/stats", 'D', n, D, 2, sbr_col_reduce_ok(X, D, D), ws, s,
+      [&](int blocks, double* slots) { bn_stats4_kernel<<<blocks, 256, 0, s>>>(X, n, D, ws, slots); },
+      [&](dim3 grid, double* rep1) { bn_stats_kernel<<<grid, 256, 0, s>>>(X, n, D, rep1); });
+  if (rc) return rc;
   SBR_CHECK_LAUNCH("sbr_bn_train_fwd/stats");
   bn_finalize_kernel<<<sbr_cdiv(D, 256), 256, 0, s>>>(ws, n, D, eps, momentum, save_mean, save_rstd, running_mean,
                                                       running_var, num_batches_tracked);
@@ -199,27 +154,14 @@ extern "C" int sbr_bn_eval_fwd(const float* X, float* Y, long n, int D, const fl
 __global__ void bn_bwd_stats_kernel(const float* __restrict__ dY, const float* __restrict__ Y, const float* __restrict__ X,
                                     long n, int D, const float* __restrict__ mean, const float* __restrict__ rstd, int act,
                                     double* __restrict__ ws) {
-  const int c = blockIdx.y * 64 + (threadIdx.x & 63);
-  const int rg = threadIdx.x >> 6;
-  double s = 0.0, sx = 0.0;
-  if (c < D) {
-    const float m = mean[c], r = rstd[c];
-    for (long j = blockIdx.x * 4L + rg; j < n; j += gridDim.x * 4L) {
-      const long e = j * D + c;
-      const float dz = dY[e] * sbr_act_grad_from_out(Y[e], act);
-      s += (double)dz;
-      sx += (double)(dz * ((X[e] - m) * r));
-    }
-  }
-  __shared__ double sm[2][256];
-  sm[0][threadIdx.x] = s;
-  sm[1][threadIdx.x] = sx;
-  __syncthreads();
-  if (rg == 0 && c < D) {
-    const int t = threadIdx.x;
-    atomicAdd(&ws[c], sm[0][t] + sm[0][t + 64] + sm[0][t + 128] + sm[0][t + 192]);
-    atomicAdd(&ws[D + c], sm[1][t] + sm[1][t + 64] + sm[1][t + 128] + sm[1][t + 192]);
-  }
+  const int c0 = blockIdx.y * 64 + (threadIdx.x & 63);
+  const float m = c0 < D ? mean[c0] : 0.f, r = c0 < D ? rstd[c0] : 0.f;
+  sbr_col_reduce_generic<2>(n, D, ws, [&](long j, int c, double* v) {
+    const long e = j * D + c;
+    const float dz = dY[e] * sbr_act_grad_from_out(Y[e], act);
+    v[0] = (double)dz;
+    v[1] = (double)(dz * ((X[e] - m) * r));
+  });
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_stats4_kernel(const float* __restrict__ dY, const float* __restrict__ Y,
@@ -267,23 +209,11 @@ extern "C" int sbr_bn_train_bwd(const float* dY, const float* Y, const float* X,
   SBR_REQUIRE(n >= 1, "sbr_bn_train_bwd: empty batch");
   hipStream_t s = (hipStream_t)stream;
   const bool vec_ok = sbr_col_reduce_ok(X, D, D) && ((((uintptr_t)dY) | ((uintptr_t)Y) | ((uintptr_t)save_mean) | ((uintptr_t)save_rstd)) & 15) == 0;
-  if (sbr_det_on()) {            // fixed-slot form (see bn_train_stats)
-    SBR_REQUIRE(vec_ok, "sbr_bn_train_bwd: no deterministic form for D=%d (needs D %% 4 == 0, D <= 1024, 16-byte aligned operands)", D);
-    const int nb = sbr_col_reduce_blocks(n, D);
-    double* slots = (double*)sbr_det_scratch(SBR_SCRATCH_COLRED, (size_t)nb * 2 * D * sizeof(double), s, "sbr_bn_train_bwd");
-    if (!slots) return SBR_ERR_HIP;
-    bn_bwd_stats4_kernel<<<nb, 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, ws, slots);
-    const int rc = sbr_det_fold_slots(slots, nb, 2 * D, ws, s, "sbr_bn_train_bwd");
-    if (rc) return rc;
-  } else if (vec_ok) {
-    sbr_note_arrival_order();
-    bn_bwd_stats4_kernel<<<sbr_col_reduce_blocks(n, D), 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, ws, nullptr);
-  } else {                       // generic path: atomics straight into replica 1
-    sbr_note_arrival_order();
-    int bx = sbr_cdiv(n, 64);
-    if (bx > 512) bx = 512;
-    bn_bwd_stats_kernel<<<dim3(bx, sbr_cdiv(D, 64)), 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, ws + 2 * D);
-  }
+  const int rc = sbr_colred_dispatch(
+      "sbr_bn_train_bwd", 'D', n, D, 2, vec_ok, ws, s,
+      [&](int blocks, double* slots) { bn_bwd_stats4_kernel<<<blocks, 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, ws, slots); },
+      [&](dim3 grid, double* rep1) { bn_bwd_stats_kernel<<<grid, 256, 0, s>>>(dY, Y, X, n, D, save_mean, save_rstd, act, rep1); });
+  if (rc) return rc;
   sbr_colred_final_kernel<<<sbr_cdiv(2 * D, 256), 256, 0, s>>>(ws, 2 * D);
   SBR_CHECK_LAUNCH("sbr_bn_train_bwd/stats");
   bn_bwd_apply_kernel<<<grid1d(n * D), 256, 0, s>>>(dY, Y, X, dX, n, D, save_mean, save_rstd, weight, act, ws, dWeight, dBias);

@@ -25,7 +25,7 @@ __device__ __forceinline__ void sbr_chol_lds(float* A, int lda, int f, int rows,
         s = fmaf(-ri[k], lp, s);
         q = fmaf(-lp, lp, q);
       }
-      const bool ok = q > 0.f && q <= 3.402823466e+38f;
+      const bool ok = sbr_pos_finite(q);
       const float d = ok ? sqrtf(q) : 1.f;
       if (t == p) {
         diag[p] = d;

@@ -7,7 +7,7 @@
 //                                every segment is brought into ascending source position, and ONE wave owns a destination row: it adds
 //                                the segment's rows in that order and writes the row with plain vector stores.
 //   fixed-slot column reduction  every workgroup of a column reduction stores its partial sums in the slot of its own blockIdx
-//                                (common.h: sbr_col_reduce with `slots`), sbr_det_fold_slots adds the slots in a fixed pattern.
+//                                (colred.h: sbr_colred_publish with `slots`), sbr_det_fold_slots adds the slots in a fixed pattern.
 #include "det.h"
 #include <atomic>
 #include <mutex>

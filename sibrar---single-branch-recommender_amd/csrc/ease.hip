@@ -44,8 +44,8 @@ extern "C" int sbr_gram_dense(const long* indptr, const int* indices, const long
               "than 2^24 entries has no exact fp32 count", n, m);
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= m, "sbr_gram_dense: row range [%d, %d) outside [0, %d]", r0, r1, m);
   SBR_REQUIRE(ld >= m, "sbr_gram_dense: leading dimension %ld below m=%d", ld, m);
-  static int attr_dev = -1;
-  const int tw = sbr_row_tile("sbr_gram_dense", (const void*)gram_dense_kernel, &attr_dev, m, tile_cols, 0, r1 - r0,
+  static SbrLdsSlot lds_slot;
+  const int tw = sbr_row_tile("sbr_gram_dense", (const void*)gram_dense_kernel, &lds_slot, m, tile_cols, 0, r1 - r0,
                               indptr && indices && t_indptr && t_indices && G);
   if (tw <= 0) return -tw;
   // the kernel owns X^T's row i: the roles of the matrix and its transpose are those of sbr_knn_topk on X^T
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void spd_diag_kernel(const float* __restrict__
   int bad = 0;
   for (int p = 0; p < b; ++p) {
     const float piv = Ds[p][p];
-    if (bad == 0 && !(piv > 0.f && piv <= 3.402823466e+38f)) bad = 1 + k0 + p;
+    if (bad == 0 && !sbr_pos_finite(piv)) bad = 1 + k0 + p;
     const float d = 1.f / piv;
     const float rp = Ds[p][j] * d;
     float cp[16];

@@ -17,7 +17,7 @@
 // sums of its output (the bias gradient of its layer) into a column-reduction workspace; all pending workspaces of a step
 // are turned into float vectors by ONE launch at the end of the backward pass.
 #include "loss_common.h"
-#include "det.h"
+#include "colred.h"
 
 // The three kernels that walk the rows of Z (scorer forward, backward pass A, and the fused forward + loss + pass A kernel) go
 // through these functions — explicit fused multiply-adds, no contraction left to the compiler — so that they produce the same bits
@@ -99,10 +99,9 @@ __global__ __launch_bounds__(256) void bn_score_bwd_stats_kernel(const float* __
                                                                  const float* __restrict__ w, const float* __restrict__ beta,
                                                                  double* __restrict__ ws) {
   __shared__ float4 sm[2][256];
-  const int C4 = D >> 2, RL = 256 / C4;
-  const int t = threadIdx.x, cg = t % C4, rl = t / C4;
-  const long chunk = (B + gridDim.x - 1) / gridDim.x;
-  const long lo = blockIdx.x * chunk, hi = (lo + chunk < B) ? lo + chunk : B;
+  const SbrColGeom cr(B, D);                                     // a row = a user
+  const int C4 = cr.C4, RL = cr.RL, t = threadIdx.x, cg = cr.cg, rl = cr.rl;
+  const long lo = cr.lo, hi = cr.hi;
   float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
   if (rl < RL) {
     const float4 m = *reinterpret_cast<const float4*>(mean + 4 * cg), r = *reinterpret_cast<const float4*>(rstd + 4 * cg);
@@ -132,7 +131,7 @@ __global__ __launch_bounds__(256) void bn_score_bwd_stats_kernel(const float* __
         const float4 p = sm[k][q * C4 + t];
         s0 += (double)p.x; s1 += (double)p.y; s2 += (double)p.z; s3 += (double)p.w;
       }
-      double* o = ws + (long)(1 + (blockIdx.x % SBR_COLRED_REP)) * 2 * D + (long)k * D + 4 * t;
+      double* o = sbr_colred_replica(ws, blockIdx.x, 2, D) + (long)k * D + 4 * t;
       atomicAdd(o, s0); atomicAdd(o + 1, s1); atomicAdd(o + 2, s2); atomicAdd(o + 3, s3);
     }
   }
@@ -272,7 +271,7 @@ __global__ __launch_bounds__(256) void bn_score_loss_kernel(const float* __restr
         const float4 p = sm[k][q * C4 + t];
         s0 += (double)p.x; s1 += (double)p.y; s2 += (double)p.z; s3 += (double)p.w;
       }
-      double* o = ws + (long)(1 + (blockIdx.x % SBR_COLRED_REP)) * 2 * D + (long)k * D + 4 * t;
+      double* o = sbr_colred_replica(ws, blockIdx.x, 2, D) + (long)k * D + 4 * t;
       atomicAdd(o, s0); atomicAdd(o + 1, s1); atomicAdd(o + 2, s2); atomicAdd(o + 3, s3);
     }
   }
@@ -290,9 +289,6 @@ __global__ __launch_bounds__(256) void bn_score_loss_kernel(const float* __restr
     last_flag = before == gridDim.x - 1;
   }
   __syncthreads();
-#ifdef BSL_NO_FINAL
-  return;
-#endif
   if (!last_flag) return;
   // (the last block reads what the others published with agent-scope atomic loads only)
   // (all 256 threads fetch the block partial sums — one thread walking up to 512 dependent-latency loads took 120 us — and add them
@@ -307,23 +303,11 @@ __global__ __launch_bounds__(256) void bn_score_loss_kernel(const float* __restr
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(lws), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   const int KD = 2 * D;
-  for (int i = t; i < KD; i += 256) {
-    double s = 0.0;
-#pragma unroll
-    for (int q = 1; q <= SBR_COLRED_REP; ++q) {
-      s += __hip_atomic_load(&ws[(long)q * KD + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ws[(long)q * KD + i] = 0.0;
-    }
-    ws[i] = s;
-  }
+  for (int i = t; i < KD; i += 256) ws[i] = sbr_colred_take_agent(ws, KD, i);
 }
 
-#ifndef BSL_MAX_BLOCKS
 #define BSL_MAX_BLOCKS 512
-#endif
-#ifndef BSL_USERS
 #define BSL_USERS 2                                      // users per row lane the grid aims for
-#endif
 extern "C" int sbr_bn_score_loss_supported(int D, int N) { return sbr_bn_score_supported(D) && N >= 1 && N <= (D >> 2) && N <= 16; }
 extern "C" long sbr_bn_score_loss_workspace(void) { return (BSL_MAX_BLOCKS + 1) * (long)sizeof(double); }
 

@@ -15,7 +15,7 @@
 // MFMAs of slab t). Within each 8-wide k group lane-half h supplies k = 4h + s to MFMA step s, so one 16-byte LDS
 // read feeds four MFMAs.
 #include "gemm_args.h"
-#include "det.h"
+#include "colred.h"
 #include <stdlib.h>
 
 #define BK 32

@@ -96,12 +96,3 @@ __device__ __forceinline__ float sp_bias_act(const float acc, const float bias, 
 }
 
 static inline bool sp_al16(const void* p, long ld) { return (((uintptr_t)p) & 15) == 0 && (ld & 3) == 0; }
-
-// raise a kernel's dynamic LDS limit once per device (slot: one static int per kernel instantiation, see sbr_attr_stale)
-static inline int sp_raise_lds(const void* kernel, size_t lds, int* slot, const char* message) {
-  if (sbr_attr_stale(slot) && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    sbr_set_error("%s", message);
-    return SBR_ERR_HIP;
-  }
-  return SBR_OK;
-}

@@ -25,7 +25,7 @@
 //   * epilogue options of the training step as in gemm_wres_f32.hip: bias + activation (forward); multiply by the activation
 //     derivative of a second matrix Y and accumulate column sums (backward: dZ_prev = (dZ W) * act'(Y) and its bias gradient).
 #include "gemm_split_common.h"
-#include "det.h"
+#include "colred.h"
 #include <type_traits>
 
 #define SP_N 128
@@ -194,8 +194,8 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_kernel(SplitArgs 
     }
   }
   if constexpr (EPI == 2) {
-    // replica layout of sbr_col_reduce<2>: [1 + replica][2][128] doubles (sums, then sums of squares)
-    double* rep = g.colsum_ws + (long)(1 + (gw % SBR_COLRED_REP)) * 2 * SP_N;
+    // replica layout of a K = 2 column reduction (colred.h): [2][128] doubles per replica (sums, then sums of squares)
+    double* rep = sbr_colred_replica(g.colsum_ws, gw, 2, SP_N);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const double o = cs[j] + __shfl_xor(cs[j], 32, 64), q = cq[j] + __shfl_xor(cq[j], 32, 64);
@@ -211,6 +211,8 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_kernel(SplitArgs 
       __syncthreads();
       if (fin_last && t < SP_N) {
         // = bn_finalize_kernel (batchnorm.hip): replicas summed in replica order, left zeroed
+        // (sbr_colred_take_agent of the sum and of the sum of squares, written out so that their 32 loads are in flight together: this
+        // block is the tail of the kernel's critical path)
         const int KD = 2 * SP_N;
         double sm = 0.0, sq = 0.0;
 #pragma unroll
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, 1) void gemm_split_kernel(SplitArgs 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const double o = cs[j] + __shfl_xor(cs[j], 32, 64);
-        if (half == 0) atomicAdd(g.colsum_ws + (long)(1 + (gw % SBR_COLRED_REP)) * SP_N + j * 32 + l31, o);
+        if (half == 0) atomicAdd(sbr_colred_replica(g.colsum_ws, gw, 1, SP_N) + j * 32 + l31, o);
       }
     }
   }
@@ -251,9 +253,9 @@ extern "C" int sbr_gemm_split_supported(long M, int N, int K) { return M >= 1 &&
 // and sums of squares of C are left pending there (sbr_bn_finalize_stats turns them into the statistics of the BatchNorm behind C).
 template <int MODE, int EPI>
 static int sp_launch(const SplitArgs& g, int n_blocks, int grid, hipStream_t s) {
-  static int attr_dev = -1;
+  static SbrLdsSlot lds_slot;
   const size_t lds = 3 * SP_PLANE;
-  const int rc = sp_raise_lds((const void*)gemm_split_kernel<MODE, EPI>, lds, &attr_dev, "sbr_gemm_split_f32: cannot raise the dynamic LDS limit");
+  const int rc = sbr_raise_lds("sbr_gemm_split_f32", (const void*)gemm_split_kernel<MODE, EPI>, &lds_slot, lds);
   if (rc != SBR_OK) return rc;
   gemm_split_kernel<MODE, EPI><<<grid, 64 * SP_WAVES, lds, s>>>(g, n_blocks);
   SBR_CHECK_LAUNCH("sbr_gemm_split_f32");
@@ -505,8 +507,8 @@ extern "C" int sbr_gemm_split_proj_f32(const float* A, long lda, const int* a_id
   int grid = sbr_cdiv(n_blocks, 4);                              // one block per SIMD first: the second wave of a SIMD only adds
   if (grid > 256) grid = 256;                                    // matrix-pipe time to it (see the work-item note in the kernel)
   const size_t lds = 2 * PJ_BUF;
-  static int attr_dev = -1;
-  const int rc = sp_raise_lds((const void*)gemm_split_proj_kernel, lds, &attr_dev, "sbr_gemm_split_proj_f32: cannot raise the dynamic LDS limit");
+  static SbrLdsSlot lds_slot;
+  const int rc = sbr_raise_lds("sbr_gemm_split_proj_f32", (const void*)gemm_split_proj_kernel, &lds_slot, lds);
   if (rc != SBR_OK) return rc;
   gemm_split_proj_kernel<<<grid, 64 * SP_WAVES, lds, (hipStream_t)stream>>>(g, n_blocks);
   SBR_CHECK_LAUNCH("sbr_gemm_split_proj_f32");

@@ -275,10 +275,10 @@ int sbr_tn_split_launch(const float* A, long lda, const int* a_idx, const float*
   g.M = M; g.nz = nz; g.nj = N / 128; g.nm = M / 128; g.chunks = sbr_cdiv(K, TS_KC);
   const size_t lds = 2 * TS_BUF + 2 * TS_MAXROWS * sizeof(unsigned long long);
   const int grid = sbr_cdiv(nz * g.nj * g.nm, 8) * 8;
-  static int attr_dev[2] = {-1, -1};                               // one per instantiation
+  static SbrLdsSlot lds_slot[2];                                   // one per instantiation
   const bool wide = g.nj * g.nm > 1;
   const void* kernel = wide ? (const void*)gemm_split_tn_kernel<true> : (const void*)gemm_split_tn_kernel<false>;
-  const int rc = sp_raise_lds(kernel, lds, &attr_dev[wide], "sbr_gemm_tn_f32: cannot raise the dynamic LDS limit of the bf16-split kernel");
+  const int rc = sbr_raise_lds("sbr_gemm_tn_f32 (bf16 split)", kernel, &lds_slot[wide], lds);
   if (rc != SBR_OK) return rc;
   if (wide) gemm_split_tn_kernel<true><<<grid, 512, lds, s>>>(g);
   else gemm_split_tn_kernel<false><<<grid, 512, lds, s>>>(g);

@@ -237,8 +237,8 @@ extern "C" int sbr_gemm_split_wide_f32(int mode, const float* A, long lda, const
   int grid = n_groups * n_cb;
   if (grid > 256) grid = 256;
   const size_t lds = 2 * SW_BUF;
-  static int attr_dev = -1;
-  const int rc = sp_raise_lds((const void*)gemm_split_wide_kernel, lds, &attr_dev, "sbr_gemm_split_wide_f32: cannot raise the dynamic LDS limit");
+  static SbrLdsSlot lds_slot;
+  const int rc = sbr_raise_lds("sbr_gemm_split_wide_f32", (const void*)gemm_split_wide_kernel, &lds_slot, lds);
   if (rc != SBR_OK) return rc;
   gemm_split_wide_kernel<<<grid, 64 * SW_WAVES, lds, (hipStream_t)stream>>>(g, n_groups, n_cb);
   SBR_CHECK_LAUNCH("sbr_gemm_split_wide_f32");

@@ -18,7 +18,7 @@
 //     gradient of that layer), accumulated per workgroup over all its tiles and flushed once into a column-reduction workspace.
 // Persistent: 2 workgroups per CU (64 KB of LDS, ~200 VGPRs), workgroup b walks tiles b, b + grid, ...
 #include "gemm_args.h"
-#include "det.h"
+#include "colred.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -240,8 +240,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wres_kernel(WresArgs g, int n_til
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const double o = cs[j] + __shfl_xor(cs[j], 32, 64);
-        if (half == 0)
-          atomicAdd(g.colsum_ws + (long)(1 + (blockIdx.x % SBR_COLRED_REP)) * WR_N + wn * 64 + j * 32 + l31, o);
+        if (half == 0) atomicAdd(sbr_colred_replica(g.colsum_ws, blockIdx.x, 1, WR_N) + wn * 64 + j * 32 + l31, o);
       }
     }
   }
@@ -275,13 +274,9 @@ extern "C" int sbr_gemm_wres_f32(int mode, const float* A, long lda, const float
   hipStream_t s = (hipStream_t)stream;
 #define WR_LAUNCH(MODE, EPI)                                                                                              \
   do {                                                                                                                     \
-    static int attr_dev = -1;                                                                                          \
-    if (sbr_attr_stale(&attr_dev)) {                                                                                                       \
-      if (hipFuncSetAttribute((const void*)gemm_wres_kernel<MODE, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        sbr_set_error("sbr_gemm_wres_f32: cannot raise the dynamic LDS limit");                                            \
-        return SBR_ERR_HIP;                                                                                                \
-      }                                                                                                                    \
-    }                                                                                                                      \
+    static SbrLdsSlot lds_slot;                                                                                            \
+    const int rc = sbr_raise_lds("sbr_gemm_wres_f32", (const void*)gemm_wres_kernel<MODE, EPI>, &lds_slot, lds);           \
+    if (rc) return rc;                                                                                                     \
     gemm_wres_kernel<MODE, EPI><<<grid, 256, lds, s>>>(g, n_tiles);                                                        \
   } while (0)
   if (mode == 0) WR_LAUNCH(0, 0);

@@ -238,8 +238,8 @@ extern "C" int sbr_knn_topk(const long* indptr, const int* indices, const long* 
   SBR_REQUIRE(n >= 0 && m >= 0 && m <= KNN_M_MAX, "sbr_knn_topk: shape [%d, %d] outside [0, 2^31) x [0, 2^24]", n, m);
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= n, "sbr_knn_topk: row range [%d, %d) outside [0, %d]", r0, r1, n);
   const long fixed = 2L * KNN_K_MAX * 8 + 256 * 4 + 64;         // the kernel's static LDS: two lists, the histogram, the scalars
-  static int attr_dev = -1;
-  const int tw = sbr_row_tile("sbr_knn_topk", (const void*)knn_topk_kernel, &attr_dev, n, tile_cols, fixed, r1 - r0,
+  static SbrLdsSlot lds_slot;
+  const int tw = sbr_row_tile("sbr_knn_topk", (const void*)knn_topk_kernel, &lds_slot, n, tile_cols, fixed, r1 - r0,
                               indptr && indices && t_indptr && t_indices && nbr_idx && nbr_val && nbr_len);
   if (tw <= 0) return -tw;
   int kpad = 2;

@@ -355,6 +355,12 @@ static int infonce_small_lds(int N, int D) { return 4 * (2 * N * (D + 4) + N * (
 #define INFONCE_MAX_N 176
 
 static int infonce_lds(int N) { return (N * (N + 1) + 2 * N) * (int)sizeof(float); }
+// above the 64 KiB that every kernel may use without asking, KERN's limit is raised (one slot per kernel)
+template <auto KERN>
+static int infonce_raise_lds(const char* who, int bytes) {
+  static SbrLdsSlot lds_slot;
+  return bytes > 64 * 1024 ? sbr_raise_lds(who, (const void*)KERN, &lds_slot, bytes) : SBR_OK;
+}
 
 extern "C" int sbr_infonce_max_n(void) { return INFONCE_MAX_N; }
 
@@ -378,12 +384,12 @@ extern "C" int sbr_infonce_fwd(const float* A, const float* B, long ld, long G, 
   }
   if (small) {
     const int ls = infonce_small_lds(N, D);
-    if (ls > 64 * 1024) (void)hipFuncSetAttribute((const void*)infonce_small_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ls);
+    if (const int rc = infonce_raise_lds<infonce_small_kernel<false>>("sbr_infonce_fwd (small groups)", ls)) return rc;
     infonce_small_kernel<false><<<(unsigned)nb, 256, ls, s>>>(A, B, ld, G, N, D, 1.f / tau, scale, loss_out, nullptr, nullptr, nullptr, 0, part);
     SBR_CHECK_LAUNCH("sbr_infonce_fwd (small groups)");
   } else {
     const int lds = infonce_lds(N);
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)infonce_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (const int rc = infonce_raise_lds<infonce_kernel<false>>("sbr_infonce_fwd", lds)) return rc;
     infonce_kernel<false><<<(unsigned)G, 256, lds, s>>>(A, B, ld, N, D, 1.f / tau, scale, loss_out, nullptr, nullptr, nullptr, 0, part);
     SBR_CHECK_LAUNCH("sbr_infonce_fwd");
   }
@@ -398,13 +404,13 @@ extern "C" int sbr_infonce_bwd(const float* A, const float* B, long ld, long G, 
   if (G == 0) return SBR_OK;
   if (infonce_small_ok(A, B, ld, N, D, dA, dB, ldg)) {
     const int ls = infonce_small_lds(N, D);
-    if (ls > 64 * 1024) (void)hipFuncSetAttribute((const void*)infonce_small_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ls);
+    if (const int rc = infonce_raise_lds<infonce_small_kernel<true>>("sbr_infonce_bwd (small groups)", ls)) return rc;
     infonce_small_kernel<true><<<(unsigned)sbr_cdiv(G, 4 * INF_S_GPW(true)), 256, ls, (hipStream_t)stream>>>(A, B, ld, G, N, D, 1.f / tau, scale, nullptr, grad_out, dA, dB, ldg);
     SBR_CHECK_LAUNCH("sbr_infonce_bwd (small groups)");
     return SBR_OK;
   }
   const int lds = infonce_lds(N);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)infonce_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (const int rc = infonce_raise_lds<infonce_kernel<true>>("sbr_infonce_bwd", lds)) return rc;
   infonce_kernel<true><<<(unsigned)G, 256, lds, (hipStream_t)stream>>>(A, B, ld, N, D, 1.f / tau, scale, nullptr, grad_out, dA, dB, ldg);
   SBR_CHECK_LAUNCH("sbr_infonce_bwd");
   return SBR_OK;

@@ -73,8 +73,8 @@ extern "C" int sbr_p3_walk_dense(const long* indptr, const int* indices, const l
               "degree over 2^24 has no exact fp32 form", n, m);
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= m, "sbr_p3_walk_dense: row range [%d, %d) outside [0, %d]", r0, r1, m);
   SBR_REQUIRE(ld >= m, "sbr_p3_walk_dense: leading dimension %ld below m=%d", ld, m);
-  static int attr_dev = -1;
-  const int tw = sbr_row_tile("sbr_p3_walk_dense", (const void*)p3_walk_dense_kernel, &attr_dev, m, tile_cols, 0, r1 - r0,
+  static SbrLdsSlot lds_slot;
+  const int tw = sbr_row_tile("sbr_p3_walk_dense", (const void*)p3_walk_dense_kernel, &lds_slot, m, tile_cols, 0, r1 - r0,
                               indptr && indices && t_indptr && t_indices && W);
   if (tw <= 0) return -tw;
   const int strip = (tw + P3_WAVES - 1) / P3_WAVES;
@@ -143,7 +143,7 @@ extern "C" int sbr_p3_score_rows(const long* indptr, const int* indices, const l
                                  float alpha, float* out, long ldo, void* stream) {
   SBR_REQUIRE(B >= 0 && m >= 0 && m <= P3_DIM_MAX && ldw >= m && ldo >= m, "sbr_p3_score_rows: bad shape (B=%ld, m=%d, ldw=%ld, ldo=%ld)", B,
               m, ldw, ldo);
-  SBR_REQUIRE(alpha > 0.f && alpha <= 3.402823466e+38f, "sbr_p3_score_rows: alpha=%g is not a positive finite power", (double)alpha);
+  SBR_REQUIRE(sbr_pos_finite(alpha), "sbr_p3_score_rows: alpha=%g is not a positive finite power", (double)alpha);
   if (B == 0 || m == 0) return SBR_OK;
   SBR_REQUIRE(indptr && indices && W && out, "sbr_p3_score_rows: null operand");
   const int col_blocks = sbr_cdiv(m, P3S_THREADS * P3S_COLS);

@@ -260,13 +260,9 @@ extern "C" int sbr_tri_solve_rows_f32(const float* in, long ldi, long n, int r, 
   SBR_REQUIRE((upper == 0 || upper == 1) && (unit == 0 || unit == 1), "%s: flags upper=%d unit=%d are not 0 / 1", who, upper, unit);
   if (n == 0) return SBR_OK;
   SBR_REQUIRE(in && T && out, "%s: null operand", who);
-  static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev) && hipFuncSetAttribute((const void*)tri_solve_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)tri_lds_bytes(RBMF_R_MAX)) != hipSuccess) {
-    attr_dev = -1;
-    sbr_set_error("%s: cannot raise the dynamic LDS limit", who);
-    return SBR_ERR_HIP;
-  }
+  static SbrLdsSlot lds_slot;
+  const int lds_rc = sbr_raise_lds(who, (const void*)tri_solve_rows_kernel, &lds_slot, tri_lds_bytes(RBMF_R_MAX));
+  if (lds_rc) return lds_rc;
   const long blocks = (n + TRI_WAVES - 1) / TRI_WAVES;
   tri_solve_rows_kernel<<<(unsigned)(blocks < TRI_MAX_BLOCKS ? blocks : TRI_MAX_BLOCKS), RBMF_THREADS, tri_lds_bytes(r), (hipStream_t)stream>>>(
       in, ldi, n, r, T, ldt, upper, unit, out, ldo);
@@ -385,7 +381,7 @@ extern "C" int sbr_maxvol_swap_step_f32(float* B, long n, long ldb, int r, float
                                         long workspace_bytes, int slab_rows, void* stream) {
   const char* who = "sbr_maxvol_swap_step_f32";
   if (int rc = mv_check(who, n, ldb, r, workspace, workspace_bytes, slab_rows)) return rc;
-  SBR_REQUIRE(tol >= 1.f && tol <= 3.402823466e+38f, "%s: tol=%g is not a finite number >= 1", who, (double)tol);
+  SBR_REQUIRE(tol >= 1.f && sbr_pos_finite(tol), "%s: tol=%g is not a finite number >= 1", who, (double)tol);
   SBR_REQUIRE(s >= 0, "%s: step s=%d is negative", who, s);
   SBR_REQUIRE(B && idx && n_swaps, "%s: null operand", who);
   const int slab = mv_slab(slab_rows), S = (int)mv_slabs(n, slab_rows);
@@ -426,13 +422,9 @@ extern "C" int sbr_chol_f32(const float* K, int n, long ldk, float* R, long ldr,
   SBR_REQUIRE(n >= 1 && n <= RBMF_R_MAX, "%s: n=%d outside [1, %d]", who, n, RBMF_R_MAX);
   SBR_REQUIRE(ldk >= n && ldr >= n, "%s: leading dimension below n=%d (ldk=%ld, ldr=%ld)", who, n, ldk, ldr);
   SBR_REQUIRE(K && R && info, "%s: null operand", who);
-  static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev) && hipFuncSetAttribute((const void*)chol_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)chol_lds_bytes(RBMF_R_MAX)) != hipSuccess) {
-    attr_dev = -1;
-    sbr_set_error("%s: cannot raise the dynamic LDS limit", who);
-    return SBR_ERR_HIP;
-  }
+  static SbrLdsSlot lds_slot;
+  const int lds_rc = sbr_raise_lds(who, (const void*)chol_kernel, &lds_slot, chol_lds_bytes(RBMF_R_MAX));
+  if (lds_rc) return lds_rc;
   chol_kernel<<<1, RBMF_R_MAX, chol_lds_bytes(n), (hipStream_t)stream>>>(K, n, ldk, R, ldr, info);
   SBR_CHECK_LAUNCH(who);
   return SBR_OK;

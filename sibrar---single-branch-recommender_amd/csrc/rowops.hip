@@ -4,7 +4,7 @@
 // All of them move rows of C..D floats; lanes run along the feature dimension so that every wave instruction
 // touches one contiguous 256-byte (or wider) segment of a row.
 #include "common.h"
-#include "det.h"
+#include "colred.h"
 
 #define SBR_MAX_SEG 16
 
@@ -719,17 +719,9 @@ extern "C" int sbr_act_grad_gather(const float* dY, const float* Y, long ld, con
 // ---------------------------------------------------------------------------------------------------------------
 // column sums (bias gradients): out[c] = sum_j X[j, c]; double accumulation, one atomic per block and column
 // ---------------------------------------------------------------------------------------------------------------
+// generic fallback (colred.h: sbr_col_reduce_generic)
 __global__ void colsum_kernel(const float* __restrict__ X, long ld, long n, int C, double* __restrict__ acc) {
-  // block = 256 threads as 4 row-groups x 64 columns
-  const int cg = blockIdx.y * 64 + (threadIdx.x & 63);
-  const int rg = threadIdx.x >> 6;
-  double s = 0.0;
-  if (cg < C)
-    for (long j = blockIdx.x * 4L + rg; j < n; j += gridDim.x * 4L) s += (double)X[j * ld + cg];
-  __shared__ double sm[256];
-  sm[threadIdx.x] = s;
-  __syncthreads();
-  if (rg == 0 && cg < C) atomicAdd(&acc[cg], sm[threadIdx.x] + sm[threadIdx.x + 64] + sm[threadIdx.x + 128] + sm[threadIdx.x + 192]);
+  sbr_col_reduce_generic<1>(n, C, acc, [&](long j, int c, double* v) { v[0] = (double)X[j * ld + c]; });
 }
 
 // workspace: C doubles, zeroed by this call
@@ -747,22 +739,12 @@ __global__ void colsum_final_kernel(double* __restrict__ ws, int C, float* __res
 extern "C" int sbr_colsum(const float* X, long ld, long n, int C, float* out, double* workspace, void* stream) {
   SBR_REQUIRE(out && workspace, "sbr_colsum: null operand");
   hipStream_t s = (hipStream_t)stream;
-  if (n > 0 && sbr_det_on()) {   // fixed-slot form: one slot per block, folded into replica 1 in slot order
-    SBR_REQUIRE(sbr_col_reduce_ok(X, ld, C), "sbr_colsum: no deterministic form for C=%d (needs C %% 4 == 0, C <= 1024, 16-byte aligned rows)", C);
-    const int nb = sbr_col_reduce_blocks(n, C);
-    double* slots = (double*)sbr_det_scratch(SBR_SCRATCH_COLRED, (size_t)nb * C * sizeof(double), s, "sbr_colsum");
-    if (!slots) return SBR_ERR_HIP;
-    colsum4_kernel<<<nb, 256, 0, s>>>(X, ld, n, C, workspace, slots);
-    const int rc = sbr_det_fold_slots(slots, nb, C, workspace, s, "sbr_colsum");
+  if (n > 0) {                   // (no rows: only the finishing kernel, which writes zeros)
+    const int rc = sbr_colred_dispatch(
+        "sbr_colsum", 'C', n, C, 1, sbr_col_reduce_ok(X, ld, C), workspace, s,
+        [&](int blocks, double* slots) { colsum4_kernel<<<blocks, 256, 0, s>>>(X, ld, n, C, workspace, slots); },
+        [&](dim3 grid, double* rep1) { colsum_kernel<<<grid, 256, 0, s>>>(X, ld, n, C, rep1); });
     if (rc) return rc;
-  } else if (n > 0 && sbr_col_reduce_ok(X, ld, C)) {
-    sbr_note_arrival_order();
-    colsum4_kernel<<<sbr_col_reduce_blocks(n, C), 256, 0, s>>>(X, ld, n, C, workspace, nullptr);
-  } else if (n > 0) {          // generic path: atomics straight into replica 1
-    sbr_note_arrival_order();
-    int bx = sbr_cdiv(n, 64);
-    if (bx > 512) bx = 512;
-    colsum_kernel<<<dim3(bx, sbr_cdiv(C, 64)), 256, 0, s>>>(X, ld, n, C, workspace + C);
   }
   colsum_final_kernel<<<sbr_cdiv(C, 256), 256, 0, s>>>(workspace, C, out);
   SBR_CHECK_LAUNCH("sbr_colsum");

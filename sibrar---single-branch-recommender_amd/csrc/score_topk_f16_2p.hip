@@ -766,10 +766,9 @@ static int s2_launch(const void* U, const void* It, long Bu, int I, const long* 
     const size_t lds = (size_t)NS * (32 * NJ) * KS * 32 + 2 * NS * 4 + 16 + (size_t)S5_MAXW * 4096;
     SBR_REQUIRE(lds <= 160 * 1024, "sbr_score_topk_f16 (two-pass): LDS budget exceeded (%zu bytes)", lds);
     auto kern = score_max_f16_kernel<KS, NS, NJ>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      sbr_set_error("sbr_score_topk_f16 (two-pass): cannot raise the dynamic LDS limit to %zu", lds);
-      return SBR_ERR_HIP;
-    }
+    static SbrLdsSlot lds_slot;
+    const int lds_rc = sbr_raise_lds("sbr_score_topk_f16 (two-pass)", (const void*)kern, &lds_slot, lds);
+    if (lds_rc) return lds_rc;
     kern<<<(unsigned int)plan.n_wg, (plan.W + (plan.n_part > 0 ? 1 : 0) + S5_NL) * 64, lds, s>>>(
         (const _Float16*)U, (const _Float16*)It, Bu, I, evs.events, evs.group_base, k, plan.W, plan.n_part, plan.P, M, Lb);
     SBR_CHECK_LAUNCH("sbr_score_topk_f16 (two-pass, pass 1)");

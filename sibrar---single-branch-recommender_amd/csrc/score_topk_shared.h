@@ -293,12 +293,9 @@ static int s5_build_events(void* buf, long buf_bytes, long Bu, int I, const long
   if (hipMemsetAsync(gc, 0, G * 4, s) != hipSuccess) { sbr_set_error("sbr_score_topk_f16: memset failed"); return SBR_ERR_HIP; }
   s5_ev_rows_kernel<<<(unsigned int)sbr_cdiv(Bu, 256), 256, 0, s>>>(Bu, u_idx, eptr, eidx, item_offset, I, rl, rc, gc);
   s5_ev_scan_kernel<<<1, 1024, 0, s>>>((int)G, gc, gb);
-  // (set on every build: the attribute belongs to the current device's copy of the kernel, a process-wide flag would skip the second GPU
-  // of a multi-device process; building the stream happens once per evaluation split)
-  if (hipFuncSetAttribute((const void*)s5_ev_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-    sbr_set_error("sbr_score_topk_f16: cannot raise the dynamic LDS limit of the event builder");
-    return SBR_ERR_HIP;
-  }
+  static SbrLdsSlot lds_slot;
+  const int lds_rc = sbr_raise_lds("sbr_score_topk_f16 (exclusion events)", (const void*)s5_ev_scatter_kernel, &lds_slot, 150 * 1024);
+  if (lds_rc) return lds_rc;
   s5_ev_scatter_kernel<<<(unsigned int)G, 256, (size_t)n_tiles_ev * 4, s>>>(Bu, eidx, item_offset, tile_items, n_tiles_ev, rl, rc, gc, gb, ev, cap);
   SBR_CHECK_LAUNCH("sbr_score_topk_f16 (exclusion events)");
   return SBR_OK;

@@ -529,10 +529,9 @@ static int st_launch(void (*kern)(const UT*, const IT*, long, int, const unsigne
   // 1.76 ms, 8: 1.59, 16: 1.54, 32: 1.55, 65: 1.58)
   const int n_tiles = sbr_cdiv(I, 32 * NJ);
   const int n_pre = !WIDE && n_tiles >= 6 * Pol::PRE_TILES ? Pol::PRE_TILES : 0;      // (wide lists bootstrap from their first selection)
-  if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    sbr_set_error("%s: cannot raise the dynamic LDS limit to %zu", what, lds);
-    return SBR_ERR_HIP;
-  }
+  static SbrLdsSlot lds_slot;                                      // (one per instantiation, each of which launches one kernel)
+  const int lds_rc = sbr_raise_lds(what, (const void*)kern, &lds_slot, lds);
+  if (lds_rc) return lds_rc;
   // (a full wave of the last workgroups may own a unit past the last user: it scores a copy of the last user and nobody reads its buffers)
   kern<<<(unsigned int)n_wg, (W + (plan.n_part > 0 ? 1 : 0) + Pol::NL) * 64, lds, s>>>(U, It, Bu, I, evs.events, evs.group_base, item_offset, k,
                                                                                       n_pre, W, plan.n_part, plan.P, cnt, (unsigned long long*)workspace);

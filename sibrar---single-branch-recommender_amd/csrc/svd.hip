@@ -215,13 +215,9 @@ extern "C" int sbr_sym_eig_f32(const float* A, int n, long lda, float* W, long l
   SBR_REQUIRE(A && W && lam && info, "sbr_sym_eig_f32: null operand");
   SBR_REQUIRE(workspace && workspace_bytes >= sbr_sym_eig_f32_workspace(n) && ((uintptr_t)workspace & 7) == 0,
               "sbr_sym_eig_f32: workspace of %ld bytes, %ld needed at an 8-byte boundary", workspace_bytes, sbr_sym_eig_f32_workspace(n));
-  static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev) && hipFuncSetAttribute((const void*)sym_eig_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)eig_lds_bytes(SVD_B_MAX)) != hipSuccess) {
-    attr_dev = -1;
-    sbr_set_error("sbr_sym_eig_f32: cannot raise the dynamic LDS limit");
-    return SBR_ERR_HIP;
-  }
+  static SbrLdsSlot lds_slot;
+  const int lds_rc = sbr_raise_lds("sbr_sym_eig_f32", (const void*)sym_eig_kernel, &lds_slot, eig_lds_bytes(SVD_B_MAX));
+  if (lds_rc) return lds_rc;
   sym_eig_kernel<<<1, EIG_THREADS, eig_lds_bytes(n), (hipStream_t)stream>>>(A, lda, n, W, ldw, lam, info, (double*)workspace);
   SBR_CHECK_LAUNCH("sbr_sym_eig_f32");
   return SBR_OK;
@@ -297,13 +293,9 @@ extern "C" int sbr_rotate_cols_f32(const float* Y, long n, long ldy, int b, cons
   SBR_REQUIRE(ldy >= b && ldw >= b && ldo >= b, "sbr_rotate_cols_f32: leading dimension below b=%d (ldy=%ld, ldw=%ld, ldo=%ld)", b, ldy, ldw,
               ldo);
   SBR_REQUIRE(W && (!lam || s) && (n == 0 || (Y && out)), "sbr_rotate_cols_f32: null operand");
-  static int attr_dev = -1;
-  if (sbr_attr_stale(&attr_dev) && hipFuncSetAttribute((const void*)rotate_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)rot_lds_bytes(SVD_B_MAX)) != hipSuccess) {
-    attr_dev = -1;
-    sbr_set_error("sbr_rotate_cols_f32: cannot raise the dynamic LDS limit");
-    return SBR_ERR_HIP;
-  }
+  static SbrLdsSlot lds_slot;
+  const int lds_rc = sbr_raise_lds("sbr_rotate_cols_f32", (const void*)rotate_cols_kernel, &lds_slot, rot_lds_bytes(SVD_B_MAX));
+  if (lds_rc) return lds_rc;
   const long tiles = (n + ROT_ROWS - 1) / ROT_ROWS;                 // a workgroup without rows still writes s
   rotate_cols_kernel<<<(unsigned)(tiles > 0 ? tiles : 1), ROT_THREADS, rot_lds_bytes(b), (hipStream_t)stream>>>(Y, n, ldy, b, W, ldw, lam, s, out,
                                                                                                            ldo);

@@ -20,7 +20,7 @@ BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 NORM_EPS = 1e-12
 PARTITION_MAX_MODALITIES = 8      # sbr_partition_slots (SBR_PART_MAX in rowops.hip)
-COLRED_WS_FACTOR = 17             # column-reduction workspaces: totals + SBR_COLRED_REP replicas (common.h)
+COLRED_WS_FACTOR = 17             # column-reduction workspaces: totals + SBR_COLRED_REP replicas (colred.h)
 
 
 # ---- deterministic mode (include/sibrar_hip.h: sbr_set_deterministic; utilities/utils.py:22-27) -----------------------------------

@@ -1,5 +1,5 @@
 """Lab: the fused scorer + loss + statistics kernel (sbr_bn_score_loss_fwd_bwd) against the three launches it replaces, at the c2
-shape (B = 8192, N = 11, D = 128), HIP-event timed. SBR_LAB_LIB picks a variant library."""
+shape (B = 8192, N = 11, D = 128), HIP-event timed. SBR_LAB_LIB picks another commit's library."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
