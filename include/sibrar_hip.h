@@ -857,7 +857,7 @@ int sbr_maxvol_swap_step_f32(float* B, long n, long ldb, int r, float tol, int s
                              long workspace_bytes, int slab_rows, void* stream);
 /* K = R R^T for a symmetric positive definite fp32 K [n, n], 1 <= n <= 128 (ldk; the lower triangle is read): the ridge system
  * C C^T + lam I of mf_algs.py:168-186. One workgroup factors it in LDS by the unpivoted Cholesky by columns of sbr_als_solve_rows_f32
- * (the same device function, csrc/chol_lds.h): q = K[p][p] - sum_{k<p} R[p][k]^2 and s_i = K[i][p] - sum_{k<p} R[i][k] R[p][k] as fmaf
+ * (the same device function, sbr_chol_lds of csrc/block128.h, once csrc/chol_lds.h): q = K[p][p] - sum_{k<p} R[p][k]^2 and s_i = K[i][p] - sum_{k<p} R[i][k] R[p][k] as fmaf
  * chains in ascending k, R[p][p] = sqrtf(q), R[i][p] = s_i / R[p][p]. R [n, n] (ldr) is written whole, zeros above the diagonal.
  * info: one device int32, zero on entry; the first pivot p with q <= 0 or not finite sets it to p + 1 (an error return, not a fault; R
  * is then unspecified). New (additive to ABI 4). */

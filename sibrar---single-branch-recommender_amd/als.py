@@ -41,8 +41,8 @@ class AlternatingLeastSquare(FactorModel):
         super().__init__(kwargs.get('device'))
         if not use_gpu:
             raise ValueError('use_gpu=False: this package has no CPU fallback, ALS runs on the GPU only')
-        if int(factors) != factors or not 1 <= factors <= ops.ALS_MAX_FACTORS:
-            raise ValueError(f'factors ({factors}) has to be an integer in [1, {ops.ALS_MAX_FACTORS}]')
+        if int(factors) != factors or not 1 <= factors <= ops.BLOCK_MAX:
+            raise ValueError(f'factors ({factors}) has to be an integer in [1, {ops.BLOCK_MAX}]')
         if not alpha > 0 or not np.isfinite(alpha):
             raise ValueError(f'alpha ({alpha}) has to be positive')
         if not regularization > 0 or not np.isfinite(regularization):

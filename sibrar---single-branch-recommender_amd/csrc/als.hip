@@ -6,10 +6,8 @@
 // No float atomics: every element of G, A_r and b_r has one owner and receives its terms in a stated order (include/sibrar_hip.h), the
 // factorisation and the two substitutions are fixed sequences, so both entry points give the same bits on every run, for every split of
 // the row range, and are valid in deterministic mode. tests/als_ref.py restates the update in float64 and in float32.
-#include "common.h"
-#include "chol_lds.h"
+#include "block128.h"
 
-#define ALS_F_MAX 128
 #define ALS_TILE 8                    // a thread's register tile of A_r / G: 8 x 8
 #define ALS_YS 128                    // floats per staged row of Y (columns [f, 8 * ceil(f / 8)) are staged as zeros)
 
@@ -72,46 +70,38 @@ __global__ __launch_bounds__(ALS_G_THREADS) void als_gram_slab_kernel(const floa
       if (i0 + a < f && j0 + b < f) out[(i0 + a) * f + j0 + b] = acc[a][b];
 }
 
-__global__ __launch_bounds__(256) void als_gram_reduce_kernel(const float* __restrict__ ws, int n_slabs, int f, float reg, float* __restrict__ G,
-                                                              long ldg) {
-#pragma clang fp contract(off)
-  const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;
-  if (e >= f * f) return;
-  const int i = e / f, j = e - i * f;
-  float s = 0.f;
-  for (int b = 0; b < n_slabs; ++b) s = s + ws[(long)b * f * f + e];
-  if (i == j && reg != 0.f) s = s + reg;                             // sbr_gram_f32 (reg = 0): nothing is added
-  G[(long)i * ldg + j] = s;
-}
-
 extern "C" long sbr_als_gram_f32_workspace(long n_y, int f) {
-  if (n_y <= 0 || f < 1 || f > ALS_F_MAX) return 0;
-  return ((n_y + ALS_G_SLAB - 1) / ALS_G_SLAB) * (long)f * f * 4;
+  if (n_y <= 0 || f < 1 || f > SBR_BLOCK_MAX) return 0;
+  return sbr_slab_ws_bytes(n_y, ALS_G_SLAB, (long)f * f);
 }
 
 // the two launches of both Gram entries; `reg` = 0: the plain Gram matrix
 static int als_gram_launch(const char* who, const float* Y, long n_y, long ldy, int f, float reg, float* G, long ldg, void* workspace,
                            long workspace_bytes, void* stream) {
-  SBR_REQUIRE(f >= 1 && f <= ALS_F_MAX, "%s: f=%d outside [1, %d]", who, f, ALS_F_MAX);
+  SBR_REQUIRE_WIDTH(who, "f", f);
   SBR_REQUIRE(reg == 0.f || sbr_pos_finite(reg), "%s: reg=%g is not positive and finite", who, (double)reg);
-  SBR_REQUIRE(n_y >= 0 && n_y <= 2147483647L * ALS_G_SLAB, "%s: n_y=%ld out of range", who, n_y);
-  SBR_REQUIRE(ldy >= f && ldg >= f, "%s: leading dimension below f=%d (ldy=%ld, ldg=%ld)", who, f, ldy, ldg);
-  SBR_REQUIRE(G && (Y || n_y == 0), "%s: null operand", who);
-  const long need = sbr_als_gram_f32_workspace(n_y, f);
-  SBR_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "%s: workspace of %ld bytes, %ld needed", who, workspace_bytes, need);
-  const int n_slabs = (int)((n_y + ALS_G_SLAB - 1) / ALS_G_SLAB);
+  SBR_REQUIRE_SLAB_ROWS(who, "n_y", n_y, ALS_G_SLAB);
+  SBR_TRY(sbr_check_ld(who, "f", f, {{"ldy", ldy}, {"ldg", ldg}}));
+  SBR_REQUIRE_OPERANDS(who, G && (Y || n_y == 0));
+  SBR_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, sbr_als_gram_f32_workspace(n_y, f), 4);
+  const int n_slabs = (int)sbr_slabs(n_y, ALS_G_SLAB);
   if (n_slabs > 0) {
     als_gram_slab_kernel<<<(unsigned)n_slabs, ALS_G_THREADS, 0, (hipStream_t)stream>>>(Y, n_y, ldy, f, (float*)workspace);
     SBR_CHECK_LAUNCH(who);
   }
-  als_gram_reduce_kernel<<<(unsigned)sbr_cdiv(f * f, 256), 256, 0, (hipStream_t)stream>>>((const float*)workspace, n_slabs, f, reg, G, ldg);
+  // the finishing step: element e = (i, j) of G gets `reg` on the diagonal; sbr_gram_f32 (reg = 0): nothing is added
+  sbr_slab_reduce_kernel<<<(unsigned)sbr_cdiv(f * f, 256), 256, 0, (hipStream_t)stream>>>(
+      (const float*)workspace, n_slabs, f * f, [=] __device__(int e, float s) {
+        const int i = e / f, j = e - i * f;
+        G[(long)i * ldg + j] = (i == j && reg != 0.f) ? s + reg : s;
+      });
   SBR_CHECK_LAUNCH(who);
   return SBR_OK;
 }
 
 extern "C" int sbr_als_gram_f32(const float* Y, long n_y, long ldy, int f, float reg, float* G, long ldg, void* workspace, long workspace_bytes,
                                 void* stream) {
-  SBR_REQUIRE(f < 1 || f > ALS_F_MAX || sbr_pos_finite(reg), "sbr_als_gram_f32: reg=%g is not positive and finite", (double)reg);
+  SBR_REQUIRE(f < 1 || f > SBR_BLOCK_MAX || sbr_pos_finite(reg), "sbr_als_gram_f32: reg=%g is not positive and finite", (double)reg);
   return als_gram_launch("sbr_als_gram_f32", Y, n_y, ldy, f, reg, G, ldg, workspace, workspace_bytes, stream);
 }
 
@@ -123,20 +113,9 @@ extern "C" int sbr_gram_f32(const float* Y, long n_y, long ldy, int f, float* G,
 // ---- x_r = A_r^-1 b_r, one workgroup per row -------------------------------------------------------------------------------------------
 #define ALS_THREADS 192               // 136 lower-triangle tiles of 8 x 8 at f = 128; f + 1 <= 129 row owners in the factorisation
 #define ALS_CHUNK 24                  // observed entries staged at a time: 12 KiB, so that two workgroups fit one CU's 160 KiB at f = 128
-#define ALS_FIXED (ALS_CHUNK * ALS_YS + 32 + 32 + ALS_F_MAX + ALS_F_MAX)          // floats of LDS in front of A
+#define ALS_FIXED (ALS_CHUNK * ALS_YS + 32 + 32 + SBR_BLOCK_MAX + SBR_BLOCK_MAX)          // floats of LDS in front of A
 
-__host__ __device__ static inline int als_lda(int f) { return sbr_chol_lda(f); }      // the odd row stride of A in LDS
-static inline size_t als_lds_bytes(int f) { return 4 * ((size_t)ALS_FIXED + (size_t)(f + 1) * als_lda(f)); }
-
-// *info <- v if it is still 0 or holds a larger value: the smallest 1 + r over the rows that met a bad pivot, whatever the arrival order
-__device__ __forceinline__ void als_report(int* info, int v) {
-  int old = atomicCAS(info, 0, v);
-  while (old != 0 && old > v) {
-    const int seen = atomicCAS(info, old, v);
-    if (seen == old) break;
-    old = seen;
-  }
-}
+static inline size_t als_lds_bytes(int f) { return 4 * ((size_t)ALS_FIXED + sbr_odd_cells(f + 1, f)); }      // A at the odd row stride
 
 // LDS: ys [24][128] the staged rows of Y | wv [24] alpha r - 1 | bw [24] alpha r | diag [128] the pivots' square roots | xs [128] the
 // solution | A [(f + 1)][lda]: rows 0 .. f-1 the lower triangle of A_r, then of its Cholesky factor L below the diagonal (the diagonal
@@ -151,8 +130,8 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_rows_kernel(const long*
   float* wv = ys + ALS_CHUNK * ALS_YS;
   float* bw = wv + 32;
   float* diag = bw + 32;
-  float* xs = diag + ALS_F_MAX;
-  float* A = xs + ALS_F_MAX;
+  float* xs = diag + SBR_BLOCK_MAX;
+  float* A = xs + SBR_BLOCK_MAX;
   const int t = threadIdx.x;
   const long r = r0 + (long)blockIdx.x;
   const long p_beg = indptr[r], p_end = indptr[r + 1];
@@ -161,7 +140,7 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_rows_kernel(const long*
     if (t < f) xr[t] = 0.f;
     return;
   }
-  const int lda = als_lda(f), nb = (f + ALS_TILE - 1) / ALS_TILE, cols = nb * ALS_TILE;
+  const int lda = sbr_odd_ld(f), nb = (f + ALS_TILE - 1) / ALS_TILE, cols = nb * ALS_TILE;
   // ---- A_r and b_r: thread t < nb (nb + 1) / 2 owns the 8 x 8 tile (ti, tj), tj <= ti, in registers; thread t < f owns b[t] ----
   const bool tile = t < nb * (nb + 1) / 2;
   int ti = 0, tj = 0;
@@ -213,8 +192,8 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_rows_kernel(const long*
   }
   if (t < f) A[f * lda + t] = bacc;
   __syncthreads();
-  // ---- unpivoted Cholesky by columns (chol_lds.h), b_r carried as row f: thread t owns row t ----
-  sbr_chol_lds(A, lda, f, f + 1, diag, t, [=](int) { als_report(info, (int)(1 + r)); });
+  // ---- unpivoted Cholesky by columns (block128.h), b_r carried as row f: thread t owns row t ----
+  sbr_chol_lds(A, lda, f, f + 1, diag, t, [=](int) { sbr_report_min(info, (int)(1 + r)); });
   // ---- L^T x = z by columns, p descending: thread t owns x[t] ----
   float z = t < f ? A[f * lda + t] : 0.f;
   for (int p = f - 1; p >= 0; --p) {
@@ -227,19 +206,16 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_rows_kernel(const long*
 
 extern "C" int sbr_als_solve_rows_f32(const long* indptr, const int* indices, const float* data, long r0, long r1, const float* Y, long n_y,
                                       long ldy, int f, const float* G, float alpha, float* X, long ldx, int* info, void* stream) {
-  SBR_REQUIRE(f >= 1 && f <= ALS_F_MAX, "sbr_als_solve_rows_f32: f=%d outside [1, %d]", f, ALS_F_MAX);
-  SBR_REQUIRE(sbr_pos_finite(alpha), "sbr_als_solve_rows_f32: alpha=%g is not positive and finite", (double)alpha);
-  SBR_REQUIRE(ldx >= f && ldy >= f, "sbr_als_solve_rows_f32: leading dimension below f=%d (ldx=%ld, ldy=%ld)", f, ldx, ldy);
-  SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= 2147483646L && r1 - r0 <= 2147483647L, "sbr_als_solve_rows_f32: row range [%ld, %ld) outside [0, 2^31 - 2]",
-              r0, r1);
-  SBR_REQUIRE(n_y >= 0, "sbr_als_solve_rows_f32: n_y=%ld is negative", n_y);
+  SBR_REQUIRE_WIDTH(__func__, "f", f);
+  SBR_REQUIRE(sbr_pos_finite(alpha), "%s: alpha=%g is not positive and finite", __func__, (double)alpha);
+  SBR_TRY(sbr_check_ld(__func__, "f", f, {{"ldx", ldx}, {"ldy", ldy}}));
+  SBR_REQUIRE_ROWS(__func__, r0, r1, 2147483646L);
+  SBR_REQUIRE(n_y >= 0, "%s: n_y=%ld is negative", __func__, n_y);
   if (r0 == r1) return SBR_OK;
-  SBR_REQUIRE(indptr && indices && Y && G && X && info, "sbr_als_solve_rows_f32: null operand");
-  static SbrLdsSlot lds_slot;
-  const int lds_rc = sbr_raise_lds("sbr_als_solve_rows_f32", (const void*)als_solve_rows_kernel, &lds_slot, als_lds_bytes(ALS_F_MAX));
-  if (lds_rc) return lds_rc;
+  SBR_REQUIRE_OPERANDS(__func__, indptr && indices && Y && G && X && info);
+  SBR_RAISE_LDS(als_solve_rows_kernel, als_lds_bytes(SBR_BLOCK_MAX));
   als_solve_rows_kernel<<<(unsigned)(r1 - r0), ALS_THREADS, als_lds_bytes(f), (hipStream_t)stream>>>(indptr, indices, data, r0, Y, ldy, f, G, alpha,
                                                                                                  X, ldx, info);
-  SBR_CHECK_LAUNCH("sbr_als_solve_rows_f32");
+  SBR_CHECK_LAUNCH(__func__);
   return SBR_OK;
 }

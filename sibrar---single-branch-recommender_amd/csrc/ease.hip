@@ -4,7 +4,7 @@
 //   sbr_ease_weights_f32  B[i, j] = P[i, j] / -P[j, j], zero diagonal, in place (:157-158)
 // No float atomics anywhere: the counts are integers (LDS integer atomics), every float has one owner per launch and a fixed
 // operation order, so all three give the same bits on every run and are valid in deterministic mode.
-#include "common.h"
+#include "block128.h"
 #include "csr_walk.h"
 
 typedef float ease_f32x16 __attribute__((ext_vector_type(16)));
@@ -40,18 +40,18 @@ __global__ __launch_bounds__(GRAM_THREADS) void gram_dense_kernel(const long* __
 
 extern "C" int sbr_gram_dense(const long* indptr, const int* indices, const long* t_indptr, const int* t_indices, int n, int m, int r0,
                               int r1, float diag_add, int tile_cols, float* G, long ld, void* stream) {
-  SBR_REQUIRE(n >= 0 && n <= GRAM_N_MAX && m >= 0, "sbr_gram_dense: shape [%d, %d] outside [0, 2^24] x [0, 2^31): a column with more "
-              "than 2^24 entries has no exact fp32 count", n, m);
-  SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= m, "sbr_gram_dense: row range [%d, %d) outside [0, %d]", r0, r1, m);
-  SBR_REQUIRE(ld >= m, "sbr_gram_dense: leading dimension %ld below m=%d", ld, m);
+  SBR_REQUIRE(n >= 0 && n <= GRAM_N_MAX && m >= 0, "%s: shape [%d, %d] outside [0, 2^24] x [0, 2^31): a column with more than 2^24 entries "
+              "has no exact fp32 count", __func__, n, m);
+  SBR_REQUIRE_ROWS(__func__, r0, r1, m);
+  SBR_TRY(sbr_check_ld(__func__, "m", m, {{"ld", ld}}));
   static SbrLdsSlot lds_slot;
-  const int tw = sbr_row_tile("sbr_gram_dense", (const void*)gram_dense_kernel, &lds_slot, m, tile_cols, 0, r1 - r0,
+  const int tw = sbr_row_tile(__func__, (const void*)gram_dense_kernel, &lds_slot, m, tile_cols, 0, r1 - r0,
                               indptr && indices && t_indptr && t_indices && G);
   if (tw <= 0) return -tw;
   // the kernel owns X^T's row i: the roles of the matrix and its transpose are those of sbr_knn_topk on X^T
   gram_dense_kernel<<<(unsigned)(r1 - r0), GRAM_THREADS, 4 * (size_t)tw, (hipStream_t)stream>>>(t_indptr, t_indices, indptr, indices, m, r0,
                                                                                          diag_add, tw, G, ld);
-  SBR_CHECK_LAUNCH("sbr_gram_dense");
+  SBR_CHECK_LAUNCH(__func__);
   return SBR_OK;
 }
 
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void spd_diag_kernel(const float* __restrict__
   }
 #pragma unroll
   for (int q = 0; q < 16; ++q) Dinv[(w + 4 * q) * SPD_B + j] = Ds[w + 4 * q][j];
-  if (t == 0 && bad != 0 && *info == 0) *info = bad;
+  if (t == 0 && bad != 0) sbr_report_first(info, bad);
 }
 
 // One workgroup per 64 columns of the panel (the grid covers ldp): P = A[K, :] and R = D^-1 P, R[p][j] = fmaf chain over q = 0 .. 63
@@ -218,13 +218,11 @@ extern "C" long sbr_spd_inverse_f32_workspace(int n) {
 }
 
 extern "C" int sbr_spd_inverse_f32(float* A, int n, long ld, void* workspace, long workspace_bytes, int* info, void* stream) {
-  SBR_REQUIRE(n >= 0 && n <= SPD_N_MAX, "sbr_spd_inverse_f32: n=%d outside [0, 2^20]", n);
+  SBR_REQUIRE(n >= 0 && n <= SPD_N_MAX, "%s: n=%d outside [0, 2^20]", __func__, n);
   if (n == 0) return SBR_OK;
-  SBR_REQUIRE(ld >= n, "sbr_spd_inverse_f32: leading dimension %ld below n=%d", ld, n);
-  SBR_REQUIRE(A && info, "sbr_spd_inverse_f32: null operand");
-  SBR_REQUIRE(workspace && workspace_bytes >= sbr_spd_inverse_f32_workspace(n) && (((uintptr_t)workspace) & 15) == 0,
-              "sbr_spd_inverse_f32: the workspace needs %ld bytes at a 16-byte boundary (got %ld)", sbr_spd_inverse_f32_workspace(n),
-              workspace_bytes);
+  SBR_TRY(sbr_check_ld(__func__, "n", n, {{"ld", ld}}));
+  SBR_REQUIRE_OPERANDS(__func__, A && info);
+  SBR_REQUIRE_WORKSPACE(__func__, workspace, workspace_bytes, sbr_spd_inverse_f32_workspace(n), 16);
   hipStream_t s = (hipStream_t)stream;
   const long ldp = spd_ldp(n);
   float* Dinv = (float*)workspace;
@@ -237,7 +235,7 @@ extern "C" int sbr_spd_inverse_f32(float* A, int n, long ld, void* workspace, lo
     spd_panel_kernel<<<(unsigned)(ldp / SPD_B), 256, 0, s>>>(A, ld, n, k0, b, Dinv, P, R, ldp);
     spd_update_kernel<<<dim3(tiles, tiles), 256, 0, s>>>(A, ld, n, k0, P, R, ldp, k0 + SPD_B >= n ? -1.f : 1.f);
   }
-  SBR_CHECK_LAUNCH("sbr_spd_inverse_f32");
+  SBR_CHECK_LAUNCH(__func__);
   return SBR_OK;
 }
 
@@ -258,11 +256,12 @@ __global__ __launch_bounds__(256) void ease_weights_kernel(float* __restrict__ P
 }
 
 extern "C" int sbr_ease_weights_f32(float* P, int n, long ld, float* diag, void* stream) {
-  SBR_REQUIRE(n >= 0 && n <= SPD_N_MAX && (n == 0 || ld >= n), "sbr_ease_weights_f32: bad shape (n=%d, ld=%ld)", n, ld);
+  SBR_REQUIRE(n >= 0 && n <= SPD_N_MAX, "%s: n=%d outside [0, 2^20]", __func__, n);
   if (n == 0) return SBR_OK;
-  SBR_REQUIRE(P && diag, "sbr_ease_weights_f32: null operand");
+  SBR_TRY(sbr_check_ld(__func__, "n", n, {{"ld", ld}}));
+  SBR_REQUIRE_OPERANDS(__func__, P && diag);
   ease_diag_kernel<<<sbr_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(P, ld, n, diag);
   ease_weights_kernel<<<dim3(sbr_cdiv(n, 256), n < 4096 ? n : 4096), 256, 0, (hipStream_t)stream>>>(P, ld, n, diag);
-  SBR_CHECK_LAUNCH("sbr_ease_weights_f32");
+  SBR_CHECK_LAUNCH(__func__);
   return SBR_OK;
 }

@@ -8,23 +8,20 @@
 // No float atomics anywhere: every output element has one owner and receives its terms in a stated order (include/sibrar_hip.h), so
 // every entry gives the same bits on every run and is valid in deterministic mode. csr_walk.h is not used: its walkers enter a sorted
 // row inside a window of columns, and these products take whole rows. tests/svd_ref.py restates the iteration in float32 numpy.
-#include "common.h"
-
-#define SVD_B_MAX 128
+#include "block128.h"
 
 // ---- out[r, 0:c] = sum_k data_k D[col_k, 0:c] ---------------------------------------------------------------------------------------
-#define CTD_THREADS 256               // four waves, a wave owns a row: lane l holds columns l and l + 64
+#define CTD_THREADS 256               // four waves, a wave owns a row (block128.h: SbrRow2)
 
 __global__ __launch_bounds__(CTD_THREADS) void csr_times_dense_kernel(const long* __restrict__ indptr, const int* __restrict__ indices,
                                                                       const float* __restrict__ data, long r0, long r1,
                                                                       const float* __restrict__ D, long ldd, int c, float* __restrict__ out,
                                                                       long ldo) {
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63;
+  const SbrRow2 w(c);
   const long r = r0 + (long)blockIdx.x * (CTD_THREADS / 64) + (threadIdx.x >> 6);
   if (r >= r1) return;
   const long beg = indptr[r], end = indptr[r + 1];
-  const bool h0 = lane < c, h1 = lane + 64 < c;
   float a0 = 0.f, a1 = 0.f;
   long p = beg;
   for (; p + 4 <= end; p += 4) {                                    // four rows of D in flight; the terms still enter in CSR order
@@ -33,8 +30,7 @@ __global__ __launch_bounds__(CTD_THREADS) void csr_times_dense_kernel(const long
     for (int u = 0; u < 4; ++u) {
       const float* d = D + (long)indices[p + u] * ldd;
       v[u] = data ? data[p + u] : 1.f;
-      x0[u] = h0 ? d[lane] : 0.f;
-      x1[u] = h1 ? d[lane + 64] : 0.f;
+      w.load(d, x0[u], x1[u]);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -45,25 +41,25 @@ __global__ __launch_bounds__(CTD_THREADS) void csr_times_dense_kernel(const long
   for (; p < end; ++p) {
     const float* d = D + (long)indices[p] * ldd;
     const float v = data ? data[p] : 1.f;
-    a0 = fmaf(v, h0 ? d[lane] : 0.f, a0);
-    a1 = fmaf(v, h1 ? d[lane + 64] : 0.f, a1);
+    float x0, x1;
+    w.load(d, x0, x1);
+    a0 = fmaf(v, x0, a0);
+    a1 = fmaf(v, x1, a1);
   }
-  if (h0) out[r * ldo + lane] = a0;
-  if (h1) out[r * ldo + lane + 64] = a1;
+  w.store(out + r * ldo, a0, a1);
 }
 
 extern "C" int sbr_csr_times_dense_f32(const long* indptr, const int* indices, const float* data, long r0, long r1, const float* D, long n_d,
                                        long ldd, int c, float* out, long ldo, void* stream) {
-  SBR_REQUIRE(c >= 1 && c <= SVD_B_MAX, "sbr_csr_times_dense_f32: c=%d outside [1, %d]", c, SVD_B_MAX);
-  SBR_REQUIRE(ldd >= c && ldo >= c, "sbr_csr_times_dense_f32: leading dimension below c=%d (ldd=%ld, ldo=%ld)", c, ldd, ldo);
-  SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= 2147483646L, "sbr_csr_times_dense_f32: row range [%ld, %ld) outside [0, 2^31 - 2]", r0, r1);
-  SBR_REQUIRE(n_d >= 0, "sbr_csr_times_dense_f32: n_d=%ld is negative", n_d);
+  SBR_REQUIRE_WIDTH(__func__, "c", c);
+  SBR_TRY(sbr_check_ld(__func__, "c", c, {{"ldd", ldd}, {"ldo", ldo}}));
+  SBR_REQUIRE_ROWS(__func__, r0, r1, 2147483646L);
+  SBR_REQUIRE(n_d >= 0, "%s: n_d=%ld is negative", __func__, n_d);
   if (r0 == r1) return SBR_OK;
-  SBR_REQUIRE(indptr && out && (n_d == 0 || D), "sbr_csr_times_dense_f32: null operand");      // (a matrix without entries has no indices)
-  const long rows_per_block = CTD_THREADS / 64;
-  csr_times_dense_kernel<<<(unsigned)((r1 - r0 + rows_per_block - 1) / rows_per_block), CTD_THREADS, 0, (hipStream_t)stream>>>(
-      indptr, indices, data, r0, r1, D, ldd, c, out, ldo);
-  SBR_CHECK_LAUNCH("sbr_csr_times_dense_f32");
+  SBR_REQUIRE_OPERANDS(__func__, indptr && out && (n_d == 0 || D));                                  // (a matrix without entries has no indices)
+  csr_times_dense_kernel<<<(unsigned)sbr_slabs(r1 - r0, CTD_THREADS / 64), CTD_THREADS, 0, (hipStream_t)stream>>>(indptr, indices, data, r0, r1, D, ldd,
+                                                                                                          c, out, ldo);
+  SBR_CHECK_LAUNCH(__func__);
   return SBR_OK;
 }
 
@@ -73,16 +69,16 @@ extern "C" int sbr_csr_times_dense_f32(const long* indptr, const int* indices, c
 #define EIG_THREADS 512
 #define EIG_MAX_SWEEPS 30             // the sweep cap of include/sibrar_hip.h
 #define EIG_EPS 0x1p-40               // a pair is left alone when |a_pq| <= EIG_EPS * sqrt(|a_pp| |a_qq|)
-#define EIG_PAIRS (SVD_B_MAX / 2)
+#define EIG_PAIRS (SBR_BLOCK_MAX / 2)
 
 // n is padded to the even np = n + (n & 1): the extra index of an odd n is the bye, a zero row and column that no rotation touches.
 // Odd row stride: the elements of a column, and the scattered elements of a step's 2 x 2 blocks, spread over the banks.
 __host__ __device__ static inline int eig_np(int n) { return (n + 1) & ~1; }
-__host__ __device__ static inline int eig_ld(int n) { return eig_np(n) | 1; }
-static inline size_t eig_lds_bytes(int n) { return 8 * ((size_t)eig_np(n) * eig_ld(n) + 4 * EIG_PAIRS + SVD_B_MAX) + 4 * (3 * EIG_PAIRS + SVD_B_MAX + 4); }
+__host__ __device__ static inline int eig_ld(int n) { return sbr_odd_ld(eig_np(n)); }
+static inline size_t eig_lds_bytes(int n) { return 8 * (sbr_odd_cells(eig_np(n), eig_np(n)) + 4 * EIG_PAIRS + SBR_BLOCK_MAX) + 4 * (3 * EIG_PAIRS + SBR_BLOCK_MAX + 4); }
 
 extern "C" long sbr_sym_eig_f32_workspace(int n) {
-  if (n < 1 || n > SVD_B_MAX) return 0;
+  if (n < 1 || n > SBR_BLOCK_MAX) return 0;
   return 8L * eig_np(n) * eig_np(n);
 }
 
@@ -102,18 +98,18 @@ __global__ __launch_bounds__(EIG_THREADS) void sym_eig_kernel(const float* __res
   double* dp = sn + EIG_PAIRS;
   double* dq = dp + EIG_PAIRS;
   double* sg = dq + EIG_PAIRS;
-  int* pi = (int*)(sg + SVD_B_MAX);
+  int* pi = (int*)(sg + SBR_BLOCK_MAX);
   int* qi = pi + EIG_PAIRS;
   int* on = qi + EIG_PAIRS;
   int* perm = on + EIG_PAIRS;
-  int* flag = perm + SVD_B_MAX;
+  int* flag = perm + SBR_BLOCK_MAX;
   // the lower triangle of the n x n view is read, and mirrored
   for (int e = t; e < np * np; e += EIG_THREADS) {
     const int i = e / np, j = e - i * np;
     A[i * ld + j] = (i < n && j < n) ? (double)Ain[(long)(i > j ? i : j) * lda + (i > j ? j : i)] : 0.0;
     Wt[e] = i == j ? 1.0 : 0.0;
   }
-  if (t < SVD_B_MAX) perm[t] = 0;
+  if (t < SBR_BLOCK_MAX) perm[t] = 0;
   if (t == 0) flag[0] = 0;
   __syncthreads();
   bool converged = false;
@@ -205,21 +201,18 @@ __global__ __launch_bounds__(EIG_THREADS) void sym_eig_kernel(const float* __res
     Wout[(long)i * ldw + c] = (float)(Wt[src * np + i] * sg[src]);
   }
   if (t < n) lam[t] = (float)A[perm[t] * ld + perm[t]];
-  if (t == 0 && !converged) *info = EIG_MAX_SWEEPS + 1;
+  if (t == 0 && !converged) sbr_report_first(info, EIG_MAX_SWEEPS + 1);
 }
 
 extern "C" int sbr_sym_eig_f32(const float* A, int n, long lda, float* W, long ldw, float* lam, int* info, void* workspace, long workspace_bytes,
                                void* stream) {
-  SBR_REQUIRE(n >= 1 && n <= SVD_B_MAX, "sbr_sym_eig_f32: n=%d outside [1, %d]", n, SVD_B_MAX);
-  SBR_REQUIRE(lda >= n && ldw >= n, "sbr_sym_eig_f32: leading dimension below n=%d (lda=%ld, ldw=%ld)", n, lda, ldw);
-  SBR_REQUIRE(A && W && lam && info, "sbr_sym_eig_f32: null operand");
-  SBR_REQUIRE(workspace && workspace_bytes >= sbr_sym_eig_f32_workspace(n) && ((uintptr_t)workspace & 7) == 0,
-              "sbr_sym_eig_f32: workspace of %ld bytes, %ld needed at an 8-byte boundary", workspace_bytes, sbr_sym_eig_f32_workspace(n));
-  static SbrLdsSlot lds_slot;
-  const int lds_rc = sbr_raise_lds("sbr_sym_eig_f32", (const void*)sym_eig_kernel, &lds_slot, eig_lds_bytes(SVD_B_MAX));
-  if (lds_rc) return lds_rc;
+  SBR_REQUIRE_WIDTH(__func__, "n", n);
+  SBR_TRY(sbr_check_ld(__func__, "n", n, {{"lda", lda}, {"ldw", ldw}}));
+  SBR_REQUIRE_OPERANDS(__func__, A && W && lam && info);
+  SBR_REQUIRE_WORKSPACE(__func__, workspace, workspace_bytes, sbr_sym_eig_f32_workspace(n), 8);
+  SBR_RAISE_LDS(sym_eig_kernel, eig_lds_bytes(SBR_BLOCK_MAX));
   sym_eig_kernel<<<1, EIG_THREADS, eig_lds_bytes(n), (hipStream_t)stream>>>(A, lda, n, W, ldw, lam, info, (double*)workspace);
-  SBR_CHECK_LAUNCH("sbr_sym_eig_f32");
+  SBR_CHECK_LAUNCH(__func__);
   return SBR_OK;
 }
 
@@ -229,7 +222,7 @@ extern "C" int sbr_sym_eig_f32(const float* A, int n, long lda, float* W, long l
 #define ROT_WS 128                    // floats per staged row of W: a wave reads 32 consecutive ones, no bank twice
 #define ROT_YS 132                    // floats per staged row of Y: the two rows a wave reads at once lie 4 * 132 floats apart, 16 banks
 #define ROT_TINY_REL 1.4210855e-14f   // 2^-46: s_j = sqrt(max(lam_j, max(lam_0 * 2^-46, FLT_MIN)))
-static inline size_t rot_lds_bytes(int b) { return 4 * ((size_t)b * ROT_WS + ROT_ROWS * ROT_YS + SVD_B_MAX); }
+static inline size_t rot_lds_bytes(int b) { return 4 * ((size_t)b * ROT_WS + ROT_ROWS * ROT_YS + SBR_BLOCK_MAX); }
 
 // Y and out may be the same matrix: a workgroup stages its rows before it writes them
 __global__ __launch_bounds__(ROT_THREADS) void rotate_cols_kernel(const float* Y, long n, long ldy, int b, const float* __restrict__ W, long ldw,
@@ -251,7 +244,7 @@ __global__ __launch_bounds__(ROT_THREADS) void rotate_cols_kernel(const float* Y
     const int rr = e / b, k = e - rr * b;
     ys[rr * ROT_YS + k] = rr < nr ? Y[(row0 + rr) * ldy + k] : 0.f;
   }
-  if (t < SVD_B_MAX) {
+  if (t < SBR_BLOCK_MAX) {
     float iv = 1.f;
     if (lam && t < b) {
       const float s = sqrtf(fmaxf(lam[t], fmaxf(lam[0] * ROT_TINY_REL, 1.17549435e-38f)));
@@ -288,25 +281,22 @@ __global__ __launch_bounds__(ROT_THREADS) void rotate_cols_kernel(const float* Y
 
 extern "C" int sbr_rotate_cols_f32(const float* Y, long n, long ldy, int b, const float* W, long ldw, const float* lam, float* s, float* out,
                                    long ldo, void* stream) {
-  SBR_REQUIRE(b >= 1 && b <= SVD_B_MAX, "sbr_rotate_cols_f32: b=%d outside [1, %d]", b, SVD_B_MAX);
-  SBR_REQUIRE(n >= 0 && n <= 2147483647L * ROT_ROWS, "sbr_rotate_cols_f32: n=%ld out of range", n);
-  SBR_REQUIRE(ldy >= b && ldw >= b && ldo >= b, "sbr_rotate_cols_f32: leading dimension below b=%d (ldy=%ld, ldw=%ld, ldo=%ld)", b, ldy, ldw,
-              ldo);
-  SBR_REQUIRE(W && (!lam || s) && (n == 0 || (Y && out)), "sbr_rotate_cols_f32: null operand");
-  static SbrLdsSlot lds_slot;
-  const int lds_rc = sbr_raise_lds("sbr_rotate_cols_f32", (const void*)rotate_cols_kernel, &lds_slot, rot_lds_bytes(SVD_B_MAX));
-  if (lds_rc) return lds_rc;
-  const long tiles = (n + ROT_ROWS - 1) / ROT_ROWS;                 // a workgroup without rows still writes s
+  SBR_REQUIRE_WIDTH(__func__, "b", b);
+  SBR_REQUIRE_SLAB_ROWS(__func__, "n", n, ROT_ROWS);
+  SBR_TRY(sbr_check_ld(__func__, "b", b, {{"ldy", ldy}, {"ldw", ldw}, {"ldo", ldo}}));
+  SBR_REQUIRE_OPERANDS(__func__, W && (!lam || s) && (n == 0 || (Y && out)));
+  SBR_RAISE_LDS(rotate_cols_kernel, rot_lds_bytes(SBR_BLOCK_MAX));
+  const long tiles = sbr_slabs(n, ROT_ROWS);                        // a workgroup without rows still writes s
   rotate_cols_kernel<<<(unsigned)(tiles > 0 ? tiles : 1), ROT_THREADS, rot_lds_bytes(b), (hipStream_t)stream>>>(Y, n, ldy, b, W, ldw, lam, s, out,
                                                                                                            ldo);
-  SBR_CHECK_LAUNCH("sbr_rotate_cols_f32");
+  SBR_CHECK_LAUNCH(__func__);
   return SBR_OK;
 }
 
 // ---- res[j] = ||Y[:, j] - s_j U[:, j]||_2 -------------------------------------------------------------------------------------------
 #define RES_SLAB 256                  // rows per workgroup: one partial sum of squares per column and slab, added in slab order
 
-__global__ __launch_bounds__(SVD_B_MAX) void col_residual_slab_kernel(const float* __restrict__ Y, long ldy, const float* __restrict__ U, long ldu,
+__global__ __launch_bounds__(SBR_BLOCK_MAX) void col_residual_slab_kernel(const float* __restrict__ Y, long ldy, const float* __restrict__ U, long ldu,
                                                                       const float* __restrict__ s, long n, int f, float* __restrict__ ws) {
 #pragma clang fp contract(off)
   const int j = threadIdx.x;
@@ -322,35 +312,25 @@ __global__ __launch_bounds__(SVD_B_MAX) void col_residual_slab_kernel(const floa
   ws[(long)blockIdx.x * f + j] = acc;
 }
 
-__global__ __launch_bounds__(SVD_B_MAX) void col_residual_reduce_kernel(const float* __restrict__ ws, int n_slabs, int f, float* __restrict__ res) {
-#pragma clang fp contract(off)
-  const int j = threadIdx.x;
-  if (j >= f) return;
-  float acc = 0.f;
-  for (int b = 0; b < n_slabs; ++b) acc = acc + ws[(long)b * f + j];
-  res[j] = sqrtf(acc);
-}
-
 extern "C" long sbr_col_residual_f32_workspace(long n, int f) {
-  if (n <= 0 || f < 1 || f > SVD_B_MAX) return 0;
-  return ((n + RES_SLAB - 1) / RES_SLAB) * (long)f * 4;
+  if (n <= 0 || f < 1 || f > SBR_BLOCK_MAX) return 0;
+  return sbr_slab_ws_bytes(n, RES_SLAB, f);
 }
 
 extern "C" int sbr_col_residual_f32(const float* Y, long ldy, const float* U, long ldu, const float* s, long n, int f, float* res, void* workspace,
                                     long workspace_bytes, void* stream) {
-  SBR_REQUIRE(f >= 1 && f <= SVD_B_MAX, "sbr_col_residual_f32: f=%d outside [1, %d]", f, SVD_B_MAX);
-  SBR_REQUIRE(n >= 0 && n <= 2147483647L * RES_SLAB, "sbr_col_residual_f32: n=%ld out of range", n);
-  SBR_REQUIRE(ldy >= f && ldu >= f, "sbr_col_residual_f32: leading dimension below f=%d (ldy=%ld, ldu=%ld)", f, ldy, ldu);
-  SBR_REQUIRE(res && s && (n == 0 || (Y && U)), "sbr_col_residual_f32: null operand");
-  const long need = sbr_col_residual_f32_workspace(n, f);
-  SBR_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "sbr_col_residual_f32: workspace of %ld bytes, %ld needed", workspace_bytes,
-              need);
-  const int n_slabs = (int)((n + RES_SLAB - 1) / RES_SLAB);
+  SBR_REQUIRE_WIDTH(__func__, "f", f);
+  SBR_REQUIRE_SLAB_ROWS(__func__, "n", n, RES_SLAB);
+  SBR_TRY(sbr_check_ld(__func__, "f", f, {{"ldy", ldy}, {"ldu", ldu}}));
+  SBR_REQUIRE_OPERANDS(__func__, res && s && (n == 0 || (Y && U)));
+  SBR_REQUIRE_WORKSPACE(__func__, workspace, workspace_bytes, sbr_col_residual_f32_workspace(n, f), 4);
+  const int n_slabs = (int)sbr_slabs(n, RES_SLAB);
   if (n_slabs > 0) {
-    col_residual_slab_kernel<<<(unsigned)n_slabs, SVD_B_MAX, 0, (hipStream_t)stream>>>(Y, ldy, U, ldu, s, n, f, (float*)workspace);
-    SBR_CHECK_LAUNCH("sbr_col_residual_f32");
+    col_residual_slab_kernel<<<(unsigned)n_slabs, SBR_BLOCK_MAX, 0, (hipStream_t)stream>>>(Y, ldy, U, ldu, s, n, f, (float*)workspace);
+    SBR_CHECK_LAUNCH(__func__);
   }
-  col_residual_reduce_kernel<<<1, SVD_B_MAX, 0, (hipStream_t)stream>>>((const float*)workspace, n_slabs, f, res);
-  SBR_CHECK_LAUNCH("sbr_col_residual_f32");
+  sbr_slab_reduce_kernel<<<1, SBR_BLOCK_MAX, 0, (hipStream_t)stream>>>((const float*)workspace, n_slabs, f,
+                                                                       [=] __device__(int j, float acc) { res[j] = sqrtf(acc); });
+  SBR_CHECK_LAUNCH(__func__);
   return SBR_OK;
 }

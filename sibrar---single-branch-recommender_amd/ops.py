@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence
 import torch
 from torch.autograd import Function
 
-from ._lib import call, lib, ptr, stream
+from ._lib import SibrarHipError, call, lib, ptr, stream
 
 ACT_CODES = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'selu': 4}
 BN_EPS = 1e-5
@@ -1179,11 +1179,44 @@ def csr_rows_times_dense(csr, rows: torch.Tensor, dense: torch.Tensor) -> torch.
     return SparseLinearActFn.apply(csr, rows, dense.t(), None, 0)
 
 
-# ---- operands of the fit-matrix entries (knn.hip, ease.hip, p3alpha.hip, als.hip) -------------------------------------------------------
-def _row_range(rows, n):
-    """``(r0, r1, whole)`` of ``rows=(r0, r1)`` among ``n`` rows (None: every row)"""
+# ---- operands of the fit-matrix entries (knn.hip, ease.hip, p3alpha.hip, als.hip, svd.hip, rbmf.hip) --------------------------------------
+BLOCK_MAX = 128                   # columns of a dense block: ALS factors, the SVD's block, RBMF's representatives (csrc/block128.h)
+SVD_MAX_BLOCK = MAXVOL_MAX_R = BLOCK_MAX
+
+
+def _block_width(who, c, n=None):
+    """Refuses a dense block of ``c`` columns outside [1, BLOCK_MAX] and (``n`` given) one of fewer rows than columns"""
+    if not 1 <= c <= BLOCK_MAX or (n is not None and n < c):
+        raise ValueError(f'{who}: {c} columns, outside [1, {BLOCK_MAX}]' + ('' if n is None else f', or more than its {n} rows'))
+
+
+def _row_range(rows, n, who=None):
+    """``(r0, r1, whole)`` of ``rows=(r0, r1)`` among ``n`` rows (None: every row). ``who``: the caller's name, to refuse a range outside
+    [0, n] here (None: the C entry refuses it)"""
     r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if who is not None and not 0 <= r0 <= r1 <= n:
+        raise ValueError(f'{who}: row range [{r0}, {r1}) outside [0, {n}]')
     return r0, r1, (r0, r1) == (0, n)
+
+
+_ENTRY_WS = {}                    # entry -> device -> its scratch
+
+
+def _entry_ws(device, entry, *args, dtype=torch.float32):
+    """``(pointer, bytes)`` of ``entry``'s grow-only scratch on ``device`` (elements of ``dtype``), grown to what the library's
+    ``<entry>_workspace(*args)`` asks for; ``(None, 0)`` when it asks for nothing"""
+    need = int(getattr(lib(), entry + '_workspace')(*args))
+    if need == 0:
+        return None, 0
+    ws = _device_ws(_ENTRY_WS.setdefault(entry, {}), device, (need + dtype.itemsize - 1) // dtype.itemsize, dtype)
+    return ptr(ws), dtype.itemsize * ws.numel()
+
+
+def _check_info(info, error):
+    """Reads an entry's ``info`` word back (synchronises with the stream) and raises ``error(word)`` when it is set"""
+    bad = int(info.item())
+    if bad:
+        raise error(bad)
 
 
 def _binary_csr_rows(who, csr, rows, n_rows, why):
@@ -1274,9 +1307,6 @@ def csr_rows_times_csr(x, rows: Optional[torch.Tensor], y, tile_cols: int = 0) -
 
 
 # ---- EASE (csrc/ease.hip) ---------------------------------------------------------------------------------------------------------
-_SPD_WS = {}
-
-
 def gram_dense(csr, diag_add: float = 0., rows=None, tile_cols: int = 0, out=None) -> torch.Tensor:
     """``X^T X + diag_add * I`` of a binary resident ``features.DeviceCSR`` X [n, m] as dense float32 [m, m], counted exactly
     (algorithms/linear_algs.py:150-153). ``rows=(r0, r1)`` computes that row range only (the other rows of a new result are zero, those
@@ -1289,10 +1319,6 @@ def gram_dense(csr, diag_add: float = 0., rows=None, tile_cols: int = 0, out=Non
     return out
 
 
-def _spd_workspace(device, n):
-    return _device_ws(_SPD_WS, device, (int(lib().sbr_spd_inverse_f32_workspace(n)) + 3) // 4, torch.float32)
-
-
 def spd_inverse_(A: torch.Tensor) -> torch.Tensor:
     """In-place inverse of a symmetric positive definite float32 matrix (a square row-major view; what lies outside the view is left
     alone) by the blocked symmetric sweep of ``sbr_spd_inverse_f32`` — ``np.linalg.inv(G)``, algorithms/linear_algs.py:155. Fixed
@@ -1302,12 +1328,9 @@ def spd_inverse_(A: torch.Tensor) -> torch.Tensor:
     n, _, ld = _f32_rows_view('spd_inverse_', 'A', A, square=True)
     if n == 0:
         return A
-    ws = _spd_workspace(A.device, n)
     info = torch.zeros(1, device=A.device, dtype=torch.int32)
-    call('sbr_spd_inverse_f32', ptr(A), n, ld, ptr(ws), ws.numel() * 4, ptr(info), stream())
-    bad = int(info.item())
-    if bad:
-        raise ValueError(f'spd_inverse_: pivot {bad - 1} is not positive: the matrix is not positive definite in float32')
+    call('sbr_spd_inverse_f32', ptr(A), n, ld, *_entry_ws(A.device, 'sbr_spd_inverse_f32', n), ptr(info), stream())
+    _check_info(info, lambda bad: ValueError(f'spd_inverse_: pivot {bad - 1} is not positive: the matrix is not positive definite in float32'))
     return A
 
 
@@ -1316,7 +1339,7 @@ def ease_weights_(P: torch.Tensor) -> torch.Tensor:
     _need_cuda(P)
     n, _, ld = _f32_rows_view('ease_weights_', 'P', P, square=True)
     if n:
-        call('sbr_ease_weights_f32', ptr(P), n, ld, ptr(_spd_workspace(P.device, n)), stream())
+        call('sbr_ease_weights_f32', ptr(P), n, ld, _entry_ws(P.device, 'sbr_spd_inverse_f32', n)[0], stream())
     return P
 
 
@@ -1352,19 +1375,13 @@ def p3_score_rows(csr, rows: Optional[torch.Tensor], W: torch.Tensor, alpha: flo
 
 
 # ---- implicit-feedback ALS (csrc/als.hip) -------------------------------------------------------------------------------------------
-ALS_MAX_FACTORS = 128
-_ALS_WS = {}
-
-
 def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
     """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a
     half-sweep shares (``sbr_als_gram_f32``: row slabs added in slab order, the same bits on every run)."""
     _need_cuda(Y)
     n, f, ldy = _f32_rows_view('als_gram', 'Y', Y)
-    need = (int(lib().sbr_als_gram_f32_workspace(n, f)) + 3) // 4 if 1 <= f <= ALS_MAX_FACTORS else 0
-    ws = _device_ws(_ALS_WS, Y.device, need, torch.float32) if need else None
     G = torch.empty(f, f, device=Y.device, dtype=torch.float32)
-    call('sbr_als_gram_f32', ptr(Y), n, ldy, f, float(reg), ptr(G), max(f, 1), ptr(ws), 4 * ws.numel() if need else 0, stream())
+    call('sbr_als_gram_f32', ptr(Y), n, ldy, f, float(reg), ptr(G), max(f, 1), *_entry_ws(Y.device, 'sbr_als_gram_f32', n, f), stream())
     return G
 
 
@@ -1382,42 +1399,27 @@ def als_solve_rows(csr, Y: torch.Tensor, G: torch.Tensor, alpha: float, out=None
     if G.dtype != torch.float32 or tuple(G.shape) != (f, f):
         raise ValueError(f'als_solve_rows: G must be float32 [{f}, {f}], got {G.dtype} {tuple(G.shape)}')
     G = G.contiguous()
-    r0, r1, whole = _row_range(rows, n)
-    if not 0 <= r0 <= r1 <= n:
-        raise ValueError(f'als_solve_rows: row range [{r0}, {r1}) outside [0, {n}]')
+    r0, r1, whole = _row_range(rows, n, 'als_solve_rows')
     out, ldo = _rows_out('als_solve_rows', out, (n, f), whole, Y.device)
     info = torch.zeros(1, device=Y.device, dtype=torch.int32)
     call('sbr_als_solve_rows_f32', ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), r0, r1, ptr(Y), n_y, ldy, f, ptr(G), float(alpha),
          ptr(out), ldo, ptr(info), stream())
-    bad = int(info.item())
-    if bad:
-        from ._lib import SibrarHipError
-        raise SibrarHipError(f'als_solve_rows: the system of row {bad - 1} is not positive definite in float32 (a pivot of its Cholesky '
-                             f'factorisation is not positive); the fp32 factorisation needs `regularization` well above f * 2^-24 * ||A|| '
-                             f'(f = {f}, alpha = {float(alpha):g}): raise `regularization` or lower `factors`')
+    _check_info(info, lambda bad: SibrarHipError(
+        f'als_solve_rows: the system of row {bad - 1} is not positive definite in float32 (a pivot of its Cholesky factorisation is not '
+        f'positive); the fp32 factorisation needs `regularization` well above f * 2^-24 * ||A|| (f = {f}, alpha = {float(alpha):g}): raise '
+        f'`regularization` or lower `factors`'))
     return out
 
 
 # ---- truncated SVD by block subspace iteration (csrc/svd.hip) -----------------------------------------------------------------------
-SVD_MAX_BLOCK = 128
-_EIG_WS = {}
-
-
-def _block_width(who, c):
-    if not 1 <= c <= SVD_MAX_BLOCK:
-        raise ValueError(f'{who}: {c} columns, outside [1, {SVD_MAX_BLOCK}]')
-
-
 def gram(Y: torch.Tensor) -> torch.Tensor:
     """``Y^T Y`` as float32 [f, f] for ``Y`` [n, f], f <= 128 (``sbr_gram_f32``: ``als_gram``'s kernels with nothing added to the
     diagonal; symmetric bit for bit, the same bits on every run)."""
     _need_cuda(Y)
     n, f, ldy = _f32_rows_view('gram', 'Y', Y)
     _block_width('gram', f)
-    need = (int(lib().sbr_als_gram_f32_workspace(n, f)) + 3) // 4
-    ws = _device_ws(_ALS_WS, Y.device, need, torch.float32) if need else None
     G = torch.empty(f, f, device=Y.device, dtype=torch.float32)
-    call('sbr_gram_f32', ptr(Y), n, ldy, f, ptr(G), f, ptr(ws), 4 * ws.numel() if need else 0, stream())
+    call('sbr_gram_f32', ptr(Y), n, ldy, f, ptr(G), f, *_entry_ws(Y.device, 'sbr_als_gram_f32', n, f), stream())
     return G
 
 
@@ -1436,13 +1438,11 @@ def sym_eig(A: torch.Tensor, info: Optional[torch.Tensor] = None):
         raise ValueError(f'sym_eig: info must be one int32, got {info.dtype} {tuple(info.shape)}')
     W = torch.empty(n, n, device=A.device, dtype=torch.float32)
     lam = torch.empty(n, device=A.device, dtype=torch.float32)
-    ws = _device_ws(_EIG_WS, A.device, int(lib().sbr_sym_eig_f32_workspace(n)) // 8, torch.float64)
-    call('sbr_sym_eig_f32', ptr(A), n, lda, ptr(W), n, ptr(lam), ptr(info), ptr(ws), 8 * ws.numel(), stream())
-    bad = int(info.item())
-    if bad:
-        from ._lib import SibrarHipError
-        raise SibrarHipError(f'sym_eig: the Jacobi iteration on the [{n}, {n}] matrix still rotated in sweep {bad - 1}, its last (info = '
-                             f'{bad}): the matrix holds non-finite values, or is no symmetric matrix of float32 numbers')
+    call('sbr_sym_eig_f32', ptr(A), n, lda, ptr(W), n, ptr(lam), ptr(info), *_entry_ws(A.device, 'sbr_sym_eig_f32', n, dtype=torch.float64),
+         stream())
+    _check_info(info, lambda bad: SibrarHipError(
+        f'sym_eig: the Jacobi iteration on the [{n}, {n}] matrix still rotated in sweep {bad - 1}, its last (info = {bad}): the matrix holds '
+        f'non-finite values, or is no symmetric matrix of float32 numbers'))
     return lam, W
 
 
@@ -1457,9 +1457,7 @@ def csr_times_dense(csr, D: torch.Tensor, out=None, rows=None) -> torch.Tensor:
     if nd != n_d:
         raise ValueError(f'csr_times_dense: D has {nd} rows, the matrix {n_d} columns')
     _block_width('csr_times_dense', c)
-    r0, r1, whole = _row_range(rows, n)
-    if not 0 <= r0 <= r1 <= n:
-        raise ValueError(f'csr_times_dense: row range [{r0}, {r1}) outside [0, {n}]')
+    r0, r1, whole = _row_range(rows, n, 'csr_times_dense')
     out, ldo = _rows_out('csr_times_dense', out, (n, c), whole, D.device)
     call('sbr_csr_times_dense_f32', ptr(csr.indptr), ptr(csr.indices), ptr(csr.data), r0, r1, ptr(D), n_d, ldd, c, ptr(out), ldo, stream())
     return out
@@ -1487,19 +1485,16 @@ def col_residual(Y: torch.Tensor, U: torch.Tensor, s: torch.Tensor, f: int) -> t
     _need_cuda(Y, U, s)
     n, cy, ldy = _f32_rows_view('col_residual', 'Y', Y)
     nu, cu, ldu = _f32_rows_view('col_residual', 'U', U)
-    if nu != n or not 1 <= f <= min(cy, cu, SVD_MAX_BLOCK) or s.dtype != torch.float32 or s.dim() != 1 or s.numel() < f or not s.is_contiguous():
+    _block_width('col_residual', f)
+    if nu != n or f > min(cy, cu) or s.dtype != torch.float32 or s.dim() != 1 or s.numel() < f or not s.is_contiguous():
         raise ValueError(f'col_residual: f={f} columns of Y {tuple(Y.shape)}, U {tuple(U.shape)} and s {s.dtype} {tuple(s.shape)} are asked for')
-    need = (int(lib().sbr_col_residual_f32_workspace(n, f)) + 3) // 4
-    ws = _device_ws(_ALS_WS, Y.device, need, torch.float32) if need else None
     res = torch.empty(f, device=Y.device, dtype=torch.float32)
-    call('sbr_col_residual_f32', ptr(Y), ldy, ptr(U), ldu, ptr(s), n, f, ptr(res), ptr(ws), 4 * ws.numel() if need else 0, stream())
+    call('sbr_col_residual_f32', ptr(Y), ldy, ptr(U), ldu, ptr(s), n, f, ptr(res), *_entry_ws(Y.device, 'sbr_col_residual_f32', n, f), stream())
     return res
 
 
 # ---- RBMF: representative rows by maxvol, and the ridge solve (csrc/rbmf.hip) -------------------------------------------------------------
-MAXVOL_MAX_R = 128
 MAXVOL_GROUP = 16                 # swap launches enqueued between two read-backs of the swap counter
-_MAXVOL_WS = {}
 
 
 def tri_solve_rows(X: torch.Tensor, T: torch.Tensor, upper: bool = False, unit: bool = False, out=None) -> torch.Tensor:
@@ -1508,8 +1503,7 @@ def tri_solve_rows(X: torch.Tensor, T: torch.Tensor, upper: bool = False, unit: 
     ``X``, ``T`` and ``out`` are views with unit column stride; ``out`` may be ``X`` itself."""
     _need_cuda(X, T, out)
     n, r, ldx = _f32_rows_view('tri_solve_rows', 'X', X)
-    if not 1 <= r <= MAXVOL_MAX_R:
-        raise ValueError(f'tri_solve_rows: {r} columns, outside [1, {MAXVOL_MAX_R}]')
+    _block_width('tri_solve_rows', r)
     ldt = _f32_rows_view('tri_solve_rows', 'T', T, (r, r))[2]
     out, ldo = _rows_out('tri_solve_rows', out, (n, r), True, X.device)
     call('sbr_tri_solve_rows_f32', ptr(X), ldx, n, r, ptr(T), ldt, int(bool(upper)), int(bool(unit)), ptr(out), ldo, stream())
@@ -1522,24 +1516,21 @@ def cholesky(K: torch.Tensor) -> torch.Tensor:
     ``SibrarHipError`` naming the first pivot that is not positive in float32. Reads one int32 back: synchronises with the stream."""
     _need_cuda(K)
     n, _, ldk = _f32_rows_view('cholesky', 'K', K, square=True)
-    if not 1 <= n <= MAXVOL_MAX_R:
-        raise ValueError(f'cholesky: a [{n}, {n}] matrix, outside [1, {MAXVOL_MAX_R}]')
+    _block_width('cholesky', n)
     R = torch.empty(n, n, device=K.device, dtype=torch.float32)
     info = torch.zeros(1, device=K.device, dtype=torch.int32)
     call('sbr_chol_f32', ptr(K), n, ldk, ptr(R), n, ptr(info), stream())
-    bad = int(info.item())
-    if bad:
-        from ._lib import SibrarHipError
-        raise SibrarHipError(f'cholesky: the [{n}, {n}] matrix is not positive definite in float32 (pivot {bad - 1} of its Cholesky '
-                             f'factorisation is not positive): raise the ridge term well above n * 2^-24 * ||K||')
+    _check_info(info, lambda bad: SibrarHipError(
+        f'cholesky: the [{n}, {n}] matrix is not positive definite in float32 (pivot {bad - 1} of its Cholesky factorisation is not '
+        f'positive): raise the ridge term well above n * 2^-24 * ||K||'))
     return R
 
 
 def _maxvol_ws(device, n, slab_rows):
-    need = int(lib().sbr_maxvol_f32_workspace(n, slab_rows))
-    if need == 0:
+    ws = _entry_ws(device, 'sbr_maxvol_f32', n, int(slab_rows), dtype=torch.int32)
+    if not ws[1]:
         raise ValueError(f'maxvol: slab_rows={slab_rows} outside [0, 1024] (n = {n})')
-    return _device_ws(_MAXVOL_WS, device, need // 4, torch.int32)
+    return ws
 
 
 def maxvol_lu(A: torch.Tensor, slab_rows: int = 0, want_upper: bool = False):
@@ -1550,22 +1541,17 @@ def maxvol_lu(A: torch.Tensor, slab_rows: int = 0, want_upper: bool = False):
     rank below r. Reads one int32 back: synchronises with the stream."""
     _need_cuda(A)
     n, r, lda = _f32_rows_view('maxvol_lu', 'A', A)
-    if not 1 <= r <= MAXVOL_MAX_R or n < r:
-        raise ValueError(f'maxvol_lu: a [{n}, {r}] matrix; 1 <= r <= {MAXVOL_MAX_R} and n >= r are needed')
+    _block_width('maxvol_lu', r, n)
     ws = _maxvol_ws(A.device, n, slab_rows)
     idx = torch.empty(r, device=A.device, dtype=torch.int32)
     ltop = torch.empty(r, r, device=A.device, dtype=torch.float32)
     utop = torch.empty(r, r, device=A.device, dtype=torch.float32) if want_upper else None
     info = torch.zeros(1, device=A.device, dtype=torch.int32)
     for k in range(r):
-        call('sbr_maxvol_lu_step_f32', ptr(A), n, lda, r, k, ptr(idx), ptr(ltop), r, ptr(utop), r, ptr(info), ptr(ws), 4 * ws.numel(),
-             int(slab_rows), stream())
-    bad = int(info.item())
-    if bad:
-        from ._lib import SibrarHipError
-        raise SibrarHipError(f'maxvol_lu: the pivot of step {bad - 1} of the row-pivoted LU of the [{n}, {r}] block is not above r * 2^-24 * '
-                             f'the largest pivot before it (or is not finite): the block has numerical rank below {r} in float32; ask for '
-                             f'fewer representatives')
+        call('sbr_maxvol_lu_step_f32', ptr(A), n, lda, r, k, ptr(idx), ptr(ltop), r, ptr(utop), r, ptr(info), *ws, int(slab_rows), stream())
+    _check_info(info, lambda bad: SibrarHipError(
+        f'maxvol_lu: the pivot of step {bad - 1} of the row-pivoted LU of the [{n}, {r}] block is not above r * 2^-24 * the largest pivot '
+        f'before it (or is not finite): the block has numerical rank below {r} in float32; ask for fewer representatives'))
     return idx, ltop, utop
 
 
@@ -1590,8 +1576,7 @@ def maxvol(U: torch.Tensor, tol: float = 1.05, max_iters: int = 100, slab_rows: 
     ``slab_rows`` (0: the default of the header). ``start``: r distinct row indices to start from instead of the LU's pivots (tests)."""
     _need_cuda(U)
     n, r, _ = _f32_rows_view('maxvol', 'U', U)
-    if not 1 <= r <= MAXVOL_MAX_R or n < r:
-        raise ValueError(f'maxvol: a [{n}, {r}] matrix; 1 <= r <= {MAXVOL_MAX_R} and n >= r are needed')
+    _block_width('maxvol', r, n)
     if not (tol >= 1 and tol < float('inf')):
         raise ValueError(f'maxvol: tol ({tol}) has to be a finite number >= 1')
     if int(max_iters) != max_iters or max_iters < 0:
@@ -1611,8 +1596,7 @@ def maxvol(U: torch.Tensor, tol: float = 1.05, max_iters: int = 100, slab_rows: 
     while done < max_iters:
         group = min(MAXVOL_GROUP, int(max_iters) - done)
         for s in range(group):
-            call('sbr_maxvol_swap_step_f32', ptr(B), n, r, r, float(tol), s, ptr(idx), ptr(counter), ptr(ws), 4 * ws.numel(), int(slab_rows),
-                 stream())
+            call('sbr_maxvol_swap_step_f32', ptr(B), n, r, r, float(tol), s, ptr(idx), ptr(counter), *ws, int(slab_rows), stream())
         now = int(counter.item())
         idle, fresh, done = now - done < group, fresh and now == done, now
         if not idle:

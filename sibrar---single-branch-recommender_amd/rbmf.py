@@ -49,8 +49,8 @@ class RBMF(FactorModel):
     def __init__(self, n_representatives: int, lam: float = 1e-2, **kwargs):
         super().__init__(kwargs.get('device'))
         r = n_representatives
-        if int(r) != r or not 1 <= r <= ops.MAXVOL_MAX_R:
-            raise ValueError(f'n_representatives ({r}) has to be an integer in [1, {ops.MAXVOL_MAX_R}]')
+        if int(r) != r or not 1 <= r <= ops.BLOCK_MAX:
+            raise ValueError(f'n_representatives ({r}) has to be an integer in [1, {ops.BLOCK_MAX}]')
         if not lam > 0 or not np.isfinite(lam):
             raise ValueError(f'lam ({lam}) has to be positive: with lam = 0 the system C C^T is singular as soon as two representatives '
                              f'share their interactions')
@@ -70,7 +70,7 @@ class RBMF(FactorModel):
         self.n_representatives = int(r)
         self.lam = lam
         self.tol, self.max_iters = float(tol), int(max_iters)
-        self.oversample = min(int(oversample), ops.SVD_MAX_BLOCK - self.n_representatives)
+        self.oversample = min(int(oversample), ops.BLOCK_MAX - self.n_representatives)
         self.n_iterations, self.svd_tol = int(n_iterations), float(svd_tol)
         self.random_state = kwargs.get('random_state', 0)
         self.representatives = self.n_swaps = None

@@ -92,8 +92,8 @@ class SVDAlgorithm(FactorModel):
 
     def __init__(self, factors: int = 100, **kwargs):
         super().__init__(kwargs.get('device'))
-        if int(factors) != factors or not 1 <= factors <= ops.SVD_MAX_BLOCK:
-            raise ValueError(f'factors ({factors}) has to be an integer in [1, {ops.SVD_MAX_BLOCK}]')
+        if int(factors) != factors or not 1 <= factors <= ops.BLOCK_MAX:
+            raise ValueError(f'factors ({factors}) has to be an integer in [1, {ops.BLOCK_MAX}]')
         oversample, n_iterations, tol = kwargs.get('oversample', 28), kwargs.get('n_iterations', 100), kwargs.get('tol', 1e-5)
         if int(oversample) != oversample or oversample < 0:
             raise ValueError(f'oversample ({oversample}) has to be a non-negative integer')
@@ -102,7 +102,7 @@ class SVDAlgorithm(FactorModel):
         if not tol >= 0:
             raise ValueError(f'tol ({tol}) has to be non-negative')
         self.factors = int(factors)
-        self.oversample = min(int(oversample), ops.SVD_MAX_BLOCK - self.factors)
+        self.oversample = min(int(oversample), ops.BLOCK_MAX - self.factors)
         self.n_iterations = int(n_iterations)
         self.tol = float(tol)
         self.random_state = kwargs.get('random_state', 0)

@@ -1,4 +1,4 @@
-"""The order oracle of deterministic mode's fixed-order kernels (csrc/deterministic.hip; common.h: sbr_col_reduce) and the case lists of
+"""The order oracle of deterministic mode's fixed-order kernels (csrc/deterministic.hip; colred.h: sbr_col_reduce) and the case lists of
 tests/test_hip_det_order.py, with the host rules restated that the cases are derived from. tests/test_det_order_cpu.py asserts on the
 CPU that every case reaches the branch it is named for. A plain module: numpy only, no fixtures, no GPU.
 
@@ -64,7 +64,7 @@ def nc_of(D):
 
 
 def col_reduce_geometry(n, C):
-    """common.h: sbr_col_reduce_blocks and the row ranges of sbr_col_reduce -> (blocks, RL row lanes, chunk rows per block, [(lo, hi)])"""
+    """colred.h: sbr_col_reduce_blocks and the row ranges of sbr_col_reduce -> (blocks, RL row lanes, chunk rows per block, [(lo, hi)])"""
     RL = 256 // (C >> 2)
     nb = max(1, min(cdiv(n, COLRED_PASSES * RL), COLRED_MAX_BLOCKS))
     chunk = cdiv(n, nb)

@@ -648,7 +648,7 @@ def test_act_grad_gather_scalar_branch(n, C, xl, xz, off, use_ii, act):
 def test_colsum_generic_branch(n, C, xl, off):
     """out[c] = sum_j X[j, c]. C % 4 != 0, C > 1024, ld % 4 != 0 or a misaligned base take the generic kernel (40,000 rows: above its
     512 x 4 row groups), which accumulates in float64 and rounds to fp32 once: |err| <= u |sum| + n 2^-53 sum|terms|. The last case is the
-    float4 kernel on a strided view: its threads add their rows in fp32 before the float64 combination (common.h, sbr_col_reduce), an
+    float4 kernel on a strided view: its threads add their rows in fp32 before the float64 combination (colred.h, sbr_col_reduce), an
     fp32 sum of at most n terms: + n u sum|terms|. The workspace (17 C doubles, zeroed once) is left zeroed by the call."""
     x = _rand(n, C, seed=19)
     X, out = _Buf(n, C, C + xl, off, data=x), _Buf(1, C, off=1)
