@@ -655,6 +655,31 @@ int sbr_csr_rows_times_csr(const long* x_indptr, const int* x_indices, const flo
                            const long* y_indptr, const int* y_indices, const float* y_data, int n_cols, int tile_cols, float* out,
                            long ld, void* stream);
 
+/* ---- neighbourhood model on dense features (csrc/dense_knn.hip) ------------------------------------------------------------------
+ * compute_similarity_top_k + dense_compute_cosine_sim_mtx — utilities/similarities.py:18-61, :86-93 (called from
+ * algorithms/knn_algs.py:136, ItemFeatureKNN). F [n, d]: fp32 rows with leading dimension ld >= d; 1 <= d <= 8192. All in fp32, one
+ * correctly rounded operation per step, no contraction other than the fmaf named here:
+ *   q_i     = sum_k F[i,k]^2      as q = fmaf(F[i,k], F[i,k], q) from +0 over k ascending;   norm_i = sqrtf(q_i)
+ *   dot_ij  = sum_k F[i,k] F[j,k] as acc = fmaf(F[i,k], F[j,k], acc) from +0 over k ascending (the fp32 matrix pipe computes exactly
+ *             this chain): the same order for every pair, whatever tile it falls in and whatever [r0, r1) is, so dot_ij and dot_ji,
+ *             and dot_ii and q_i, carry the same bits
+ *   j != i  v = dot_ij / (norm_i * norm_j);  shrinkage > 0: value = v * (dot_ij / (dot_ij + shrinkage));  shrinkage == 0: value = v
+ *   j == i  value = +0
+ * j is a candidate of i iff dot_ij != 0 (j = i included when q_i > 0): the entries scipy's coo_matrix keeps of the dense product. A
+ * value of -0 is ranked and written as +0. The list of row i is the first min(k, candidates) of them by (value descending, index
+ * ascending), the rule of sbr_topk_rows, selected on the order-preserving unsigned key of the float (negative: all bits flipped;
+ * otherwise: the sign bit set), so negative values rank below the self entry's +0: nbr_idx int32 [n, k], nbr_val fp32 [n, k],
+ * nbr_len int32 [n]; the slots behind nbr_len[i] hold (-1, +0). Only the rows of [r0, r1) are written; r0 == r1 returns without a
+ * launch. sbr_row_norms_f32 writes norm_i of every row into norms [n]; sbr_dense_knn_topk takes that array (the caller may look at
+ * it in between: a non-finite or overflowed norm is the caller's to refuse). Columns [d, ld) and rows >= n of a larger allocation are
+ * never multiplied. 1 <= k <= 256; n k < 2^31; shrinkage >= 0 (a negative dot with shrinkage > 0 can meet the pole of
+ * dot / (dot + shrinkage): the result is then whatever fp32 gives, ranked by its key). No workspace: nothing of size n x n or
+ * rows x n leaves the chip. No float atomics (integer LDS atomics hand out buffer slots; the selection does not depend on the slot
+ * order): the same bits on every run and for every split of the row range, valid in deterministic mode. New (additive to ABI 4). */
+int sbr_row_norms_f32(const float* F, int n, int d, long ld, float* norms, void* stream);
+int sbr_dense_knn_topk(const float* F, const float* norms, int n, int d, long ld, int r0, int r1, float shrinkage, int k,
+                       int* nbr_idx, float* nbr_val, int* nbr_len, void* stream);
+
 /* ---- EASE on 0/1 data (csrc/ease.hip) ------------------------------------------------------------------------------------------
  * G = X^T X + diag_add I — algorithms/linear_algs.py:150-153 (`matrix.transpose().dot(matrix).toarray()`, `G[diag] += int(lam)`) as
  * dense fp32 rows G [m, m] with leading dimension ld >= m. X [n, m] and X^T in the forms sbr_knn_topk takes (binary CSR, sorted,

@@ -10,6 +10,9 @@ per user chunk by ``ops.csr_rows_times_csr`` — ``S[u] @ matrix`` (UserKNN, knn
 Full-catalogue evaluation goes through the hooks ``evaluate_recommender_algorithm`` already calls: the item side is a 1-tuple (the item ids),
 which takes the ``fp32`` route — score rows, exclusion mask, exact top-k — whatever ``scorer`` asks for.
 
+``ItemFeatureKNN`` compares dense item feature rows instead (``ops.dense_knn_topk``, csrc/dense_knn.hip: the n x n x d product on the fp32
+matrix pipe with the cosine value and the top-k selection on chip) and predicts as ItemKNN does; see its docstring.
+
 Deliberate differences from the reference: the similarities are computed in fp32 (the reference: float64) in the operation order stated in
 include/sibrar_hip.h; among equal similarities at the k-th place the lower index is kept (the reference: whichever an unstable argsort
 leaves); ``model.npz`` holds the lists, not ``pred_mtx``, so a loaded model needs the interaction matrix again (``attach``).
@@ -58,14 +61,16 @@ class KNNAlgorithm(ResidentMatrixAlgorithm, ABC):
     ENTITY = None            # 'user' | 'item': whose rows are compared
     KEY, WHAT, STORES = 'nbr_idx', 'neighbour lists', 'the neighbour lists'
     BINARY_ONLY = 'KNN similarities are stated for 0/1 interaction data only (utilities/similarities.py:11-15)'
+    DENSE = False            # the rows compared are dense feature rows (dense_cosine) rather than rows of the 0/1 matrix
+    SIM_REFUSAL = ('dense_cosine is the similarity of ItemFeatureKNN (ifknn), which compares dense feature rows; uknn / iknn compare rows '
+                   'of the 0/1 matrix and take jaccard, cosine, asymmetric_cosine, tversky or sorensen_dice')
 
     def __init__(self, sim_func_enum: SimilarityFunctionEnum = SimilarityFunctionEnum.cosine, k: int = 100, shrinkage: float = .0, **kwargs):
         super().__init__(kwargs.get('device'))
         if isinstance(sim_func_enum, str):
             sim_func_enum = SimilarityFunctionEnum[sim_func_enum]
-        if sim_func_enum == SimilarityFunctionEnum.dense_cosine:
-            raise ValueError('dense_cosine is the similarity of ItemFeatureKNN (ifknn), which this package does not provide; '
-                             'uknn / iknn take jaccard, cosine, asymmetric_cosine, tversky or sorensen_dice')
+        if (sim_func_enum == SimilarityFunctionEnum.dense_cosine) != self.DENSE:
+            raise ValueError(self.SIM_REFUSAL)
         if not (isinstance(k, (int, np.integer)) and 1 <= k <= ops.KNN_MAX_K):
             raise ValueError(f'k={k!r} outside [1, {ops.KNN_MAX_K}] (the longest list the selection kernels keep)')
         if shrinkage < 0:
@@ -148,7 +153,7 @@ class KNNAlgorithm(ResidentMatrixAlgorithm, ABC):
         if conf['alg'] == 'iknn':
             return ItemKNN(sim_func, conf['k'], shrinkage, alpha=alpha, beta=beta)
         if conf['alg'] == 'ifknn':
-            raise ValueError('ifknn (ItemFeatureKNN) is not provided by this package')
+            return ItemFeatureKNN(sim_func, conf['k'], shrinkage)
         raise ValueError(f"{conf['alg']} is an invalid model for KNNAlgorithm")
 
 
@@ -170,3 +175,53 @@ class ItemKNN(KNNAlgorithm):
         super().__init__(sim_func, k, shrinkage, **kwargs)
         self.name = 'ItemKNN'
         logging.info(f'Built {self.name} module \n')
+
+
+def _dense_features(feature_matrix, n_items: int, device) -> torch.Tensor:
+    """``feature_matrix`` (np.ndarray, torch.Tensor or scipy sparse) as a finite float32 [n_items, d] tensor on ``device``"""
+    if feature_matrix is None:
+        raise ValueError('ItemFeatureKNN.fit needs feature_matrix: the dense item x feature_dim matrix (algorithms/knn_algs.py:129-133)')
+    if sp.issparse(feature_matrix):
+        feature_matrix = feature_matrix.toarray()
+    f = feature_matrix.detach() if isinstance(feature_matrix, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feature_matrix))
+    if f.dim() != 2 or f.shape[0] != n_items or f.shape[1] < 1:
+        raise ValueError(f'ItemFeatureKNN.fit: feature_matrix of shape {tuple(f.shape)}, expected [{n_items} items, d >= 1]')
+    f = f.to(device=device, dtype=torch.float32).contiguous()
+    if not bool(torch.isfinite(f).all()):
+        raise ValueError('ItemFeatureKNN.fit: feature_matrix has entries that are not finite (after the cast to float32)')
+    return f
+
+
+class ItemFeatureKNN(KNNAlgorithm):
+    """algorithms/knn_algs.py:121-140: items similar by their dense features (``dense_cosine``, utilities/similarities.py:86-93);
+    ``pred = matrix @ sim_mtx.T`` as ItemKNN. ``fit(matrix, feature_matrix)``; the features are not kept: the model is the lists.
+
+    What the reference does and this model keeps: the candidates of an item are the items with a non-zero dot product, itself included
+    with the value 0, so a list of fewer than k positive similarities goes on with that explicit 0 and then the negative ones; an
+    all-zero feature row has an empty list. Deliberate differences: fp32 instead of float64 (the order of include/sibrar_hip.h); the
+    lowest index wins among equal values (the reference: whichever an unstable argsort leaves); ``dense_cosine`` only, and as the
+    constructor's default (the reference's default, cosine, is stated for 0/1 rows); ``shrinkage > 0`` only with features that are all
+    >= 0 — the factor dot / (dot + shrinkage) has a pole at dot = -shrinkage, and the reference returns "similarities" of any size
+    around it; ``model.npz`` holds the lists and needs ``attach(matrix)``; ``k <= 256``."""
+    ENTITY = 'item'
+    DENSE = True
+    SIM_REFUSAL = ('ifknn (ItemFeatureKNN) compares dense feature rows and takes dense_cosine only; jaccard, cosine, asymmetric_cosine, '
+                   'tversky and sorensen_dice are stated for rows of the 0/1 matrix (uknn / iknn)')
+
+    def __init__(self, sim_func: SimilarityFunctionEnum = SimilarityFunctionEnum.dense_cosine, k: int = 100, shrinkage: float = .0, **kwargs):
+        super().__init__(sim_func, k, shrinkage, **kwargs)
+        self.name = 'ItemFeatureKNN'
+        logging.info(f'Built {self.name} module \n')
+
+    def fit(self, matrix: sp.spmatrix, feature_matrix=None, **kwargs):
+        """:param matrix: user x item sparse matrix
+        :param feature_matrix: item x feature_dim matrix: np.ndarray, torch.Tensor or scipy sparse (densified)"""
+        self.attach(matrix)
+        f = _dense_features(feature_matrix, self.n_items, self.device)
+        if self.shrinkage > 0 and bool((f < 0).any()):
+            raise ValueError(f'ItemFeatureKNN: shrinkage={self.shrinkage} with negative features: the factor dot / (dot + shrinkage) has a '
+                             f'pole at dot = -shrinkage, so negative dot products give values of any size and sign; use shrinkage=0 or '
+                             f'features that are all >= 0')
+        self.nbr_idx, self.nbr_val, self.nbr_len = ops.dense_knn_topk(f, self.k, self.shrinkage)
+        self._operands = None
+        return self

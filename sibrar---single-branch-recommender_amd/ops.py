@@ -1282,6 +1282,34 @@ def knn_topk(csr, sim, k: int, shrinkage: float = 0., alpha=None, beta=None, row
     return idx, val, length
 
 
+def dense_knn_topk(F: torch.Tensor, k: int, shrinkage: float = 0., rows=None):
+    """The ``k`` most similar rows of every row of a dense float32 matrix ``F`` [n, d] by cosine (``compute_similarity_top_k`` with
+    ``dense_compute_cosine_sim_mtx``, utilities/similarities.py:18-61, :86-93; csrc/dense_knn.hip) -> the lists of ``knn_topk``. The
+    candidates of a row are the rows with a non-zero dot product, itself included with value +0; values are signed. ``F``: a 2-D CUDA
+    view with unit column stride (rows may be further apart than ``d``). ``rows=(r0, r1)`` computes that row range only (the other
+    rows come back empty). Refuses a row whose norm is not finite (an inf or NaN entry, or an overflowing sum of squares): reads one
+    flag back, which synchronises with the stream."""
+    if not (isinstance(k, numbers.Integral) and 1 <= k <= KNN_MAX_K):
+        raise ValueError(f'dense_knn_topk: k={k!r} outside [1, {KNN_MAX_K}]')
+    if not shrinkage >= 0:
+        raise ValueError(f'dense_knn_topk: negative shrinkage {shrinkage}')
+    _need_cuda(F)
+    n, d, ld = _f32_rows_view('dense_knn_topk', 'F', F)
+    r0, r1, whole = _row_range(rows, n, 'dense_knn_topk')
+    dev = F.device
+    idx = (torch.empty if whole else partial(torch.full, fill_value=-1))((n, k), device=dev, dtype=torch.int32)
+    val = (torch.empty if whole else torch.zeros)((n, k), device=dev, dtype=torch.float32)
+    length = (torch.empty if whole else torch.zeros)((n,), device=dev, dtype=torch.int32)
+    if n == 0:
+        return idx, val, length
+    norms = torch.empty(n, device=dev, dtype=torch.float32)
+    call('sbr_row_norms_f32', ptr(F), n, d, ld, ptr(norms), stream())
+    if not bool(torch.isfinite(norms).all()):
+        raise ValueError('dense_knn_topk: a row of F has a norm that is not finite (inf / NaN entries, or a sum of squares over the fp32 range)')
+    call('sbr_dense_knn_topk', ptr(F), ptr(norms), n, d, ld, r0, r1, float(shrinkage), int(k), ptr(idx), ptr(val), ptr(length), stream())
+    return idx, val, length
+
+
 def _csr_parts(x):
     """(indptr, indices, data or None, shape) of a ``features.DeviceCSR`` or of a plain tuple of that form"""
     if isinstance(x, (tuple, list)):
