@@ -713,6 +713,29 @@ long sbr_spd_inverse_f32_workspace(int n);
  * division per element. diag: n floats of scratch (the diagonal is read before it is overwritten). New (additive to ABI 4). */
 int sbr_ease_weights_f32(float* P, int n, long ld, float* diag, void* stream);
 
+/* ---- SLIM on 0/1 data (csrc/slim.hip) ------------------------------------------------------------------------------------------
+ * The item-item weights of algorithms/linear_algs.py:39-112 (sklearn's ElasticNet with positive=True, fit_intercept=False, once per
+ * item j on the users x items matrix with column j zeroed), solved from the Gram matrix alone. G [m, m]: X^T X as sbr_gram_dense
+ * counts it (diag_add = 0), symmetric fp32 with leading dimension ldg; its diagonal is read in place. With q = G[:, j], q_j = 0, and
+ * l1 = n alpha l1_ratio, l2 = n alpha (1 - l1_ratio) for n users, column j minimises sklearn's objective times n,
+ *   1/2 (G_jj - 2 w.q + w.G w) + l1 sum(w) + 1/2 l2 w.w   over w >= 0, w_j = 0,
+ * by cyclic coordinate descent in ASCENDING k (the reference: random order; with l2 > 0 the optimum is unique and the order only
+ * changes the path). State: w = 0, r = q. A sweep takes every k != j with G_kk > 0 (a zero-norm column is skipped and stays 0):
+ *   new = max((r_k + G_kk * w_k) - l1, 0) / (G_kk + l2);  d = new - w_k;  if d != 0: r_x = r_x - d * G[k, x] for every x;  w_k = new,
+ * every operation one rounded fp32 operation, nothing fused. The kernel searches for the next coordinate with w_k > 0 or r_k > l1
+ * and passes over the others, whose step is zero, so it gives what the plain loop gives. After a sweep, with w_max = max |w_k| and
+ * d_w_max = max |d| over it, the column stops when w_max == 0 or d_w_max <= tol * w_max (sklearn's first stopping test; its dual-gap
+ * test is not reproduced), or after max_iter sweeps. tol = 0 stops at an exact fixed point or at max_iter.
+ * One workgroup owns one target column j of [c0, c1) and writes W[k, j] for every k in [0, m), zeros included (W [m, m] fp32, leading
+ * dimension ldw; matrix[u] @ W is the prediction, linear_algs.py:59-61); columns outside the range are untouched. n_iter[j]: the
+ * sweeps run, negated when the column stopped at max_iter without meeting the stopping test. r lives in LDS: m <= 40,832 (4 m
+ * bytes beside 512 bytes of fixed state in 160 KiB); w lives in the output column. No atomics, no cooperative launch, no workgroup
+ * waits on another; every element of r and W has one owner thread: the same bits on every run and for every split of [c0, c1),
+ * valid in deterministic mode. l1, l2 and tol must be finite and >= 0, max_iter >= 1. m == 0 or c0 == c1 return at once, before the
+ * operands are looked at; a null operand is an error otherwise. New (additive to ABI 4). */
+int sbr_slim_cd_f32(const float* G, int m, long ldg, int c0, int c1, float l1, float l2, int max_iter, float tol, float* W, long ldw,
+                    int* n_iter, void* stream);
+
 /* ---- P3alpha on 0/1 data (csrc/p3alpha.hip) --------------------------------------------------------------------------------------
  * The users x items block of the reference's P^3 (algorithms/graph_algs.py:35-65) is (D_u^-1 X)(D_i^-1 X^T)(D_u^-1 X); its last two
  * factors are the item-item model W [m, m], dense fp32 rows with leading dimension ld >= m — algorithms/graph_algs.py:35-59 (the

@@ -23,6 +23,7 @@ from .ecf import ECF, ecf_tag_matrix                                            
 from .matrix_models import FactorModel, ResidentMatrixAlgorithm, SparseMatrixBasedRecommenderAlgorithm   # noqa: F401
 from .knn import ItemFeatureKNN, ItemKNN, KNNAlgorithm, SimilarityFunctionEnum, UserKNN                     # noqa: F401
 from .ease import EASE                                                                      # noqa: F401
+from .slim import SLIM                                                                      # noqa: F401
 from .p3alpha import P3alpha                                                                # noqa: F401
 from .als import AlternatingLeastSquare                                                     # noqa: F401
 from .svd import SVDAlgorithm                                                               # noqa: F401
@@ -53,10 +54,10 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
     ops.set_deterministic(deterministic)
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
-# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .p3alpha / .als / .svd / .rbmf -> class
+# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .slim / .p3alpha / .als / .svd / .rbmf -> class
 # (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
               'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ifknn': ItemFeatureKNN, 'ease': EASE,
-              'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF}
+              'slim': SLIM, 'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF}

@@ -118,7 +118,8 @@ static inline int sbr_raise_lds(const char* who, const void* kernel, SbrLdsSlot*
 __host__ __device__ __forceinline__ bool sbr_pos_finite(float v) { return v > 0.f && v <= 3.402823466e+38f; }
 
 // Host prologue of the kernels that run one workgroup per row and keep a tile of four-byte cells in dynamic LDS (sbr_knn_topk,
-// sbr_gram_dense, sbr_p3_walk_dense), after the entry point's shape and range checks: `tile_cols` columns per tile, 0 for the default (all
+// sbr_gram_dense, sbr_p3_walk_dense; sbr_slim_cd_f32 per column, with the whole column as its one tile: tile_cols = cols = m, and its
+// static LDS as `fixed`), after the entry point's shape and range checks: `tile_cols` columns per tile, 0 for the default (all
 // `cols` of them, clamped to [64, SBR_ROW_TILE_DEFAULT]); `fixed`: the kernel's static LDS bytes. -> the tile width when there is
 // something to launch, with the kernel's dynamic LDS limit raised on this device (`slot`: the kernel's slot of sbr_raise_lds);
 // 0 for an empty row range (`n_rows` == 0), before the operands are looked at; otherwise minus the error code, with the message set.

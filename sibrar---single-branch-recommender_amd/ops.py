@@ -1371,6 +1371,34 @@ def ease_weights_(P: torch.Tensor) -> torch.Tensor:
     return P
 
 
+# ---- SLIM (csrc/slim.hip) ---------------------------------------------------------------------------------------------------------
+SLIM_MAX_ITEMS = 40832            # the residual of a column lives in LDS (include/sibrar_hip.h)
+
+
+def slim_weights(G: torch.Tensor, l1: float, l2: float, max_iter: int, tol: float = 1e-4, cols=None, out=None):
+    """The non-negative elastic-net item weights of SLIM (algorithms/linear_algs.py:39-112) from the Gram matrix ``G = X^T X`` (a square
+    float32 row view, as ``gram_dense`` counts it) -> ``(W float32 [m, m], n_iter int32 [m])``: column j of ``W`` minimises
+    ``1/2 (G_jj - 2 w.q + w.G w) + l1 sum(w) + 1/2 l2 w.w`` over ``w >= 0, w_j = 0`` (``q = G[:, j]``, ``q_j = 0``) by cyclic coordinate
+    descent in ascending order, stopped after the sweep with ``max |dw| <= tol * max |w|`` or after ``max_iter`` sweeps (``sbr_slim_cd_f32``;
+    the same bits on every run). ``n_iter[j]``: the sweeps of column j, negative when it stopped at ``max_iter`` unconverged.
+    ``cols=(c0, c1)`` computes that column range only (the other columns of a new result are zero, those of ``out`` keep what they hold;
+    their ``n_iter`` is 0); ``out``: a float32 [m, m] view with unit column stride to write into; it must not overlap ``G``, which the
+    kernel reads while it writes ``W`` (refused)."""
+    _need_cuda(G, out)
+    m, _, ldg = _f32_rows_view('slim_weights', 'G', G, square=True)
+    if not (l1 >= 0 and l2 >= 0 and tol >= 0):
+        raise ValueError(f'slim_weights: l1={l1!r}, l2={l2!r} and tol={tol!r} must not be negative')
+    if not (isinstance(max_iter, numbers.Integral) and max_iter >= 1):
+        raise ValueError(f'slim_weights: max_iter={max_iter!r} must be an integer >= 1')
+    c0, c1, whole = _row_range(cols, m)
+    out, ldw = _rows_out('slim_weights', out, (m, m), whole, G.device)
+    if m and ptr(out) < ptr(G) + 4 * ((m - 1) * ldg + m) and ptr(G) < ptr(out) + 4 * ((m - 1) * ldw + m):
+        raise ValueError('slim_weights: out overlaps G in memory; the weights cannot be written over the Gram matrix they are solved from')
+    n_iter = torch.zeros(m, device=G.device, dtype=torch.int32)
+    call('sbr_slim_cd_f32', ptr(G), m, ldg, c0, c1, float(l1), float(l2), int(max_iter), float(tol), ptr(out), ldw, ptr(n_iter), stream())
+    return out, n_iter
+
+
 # ---- P3alpha (csrc/p3alpha.hip) ----------------------------------------------------------------------------------------------------
 def p3_walk_dense(csr, rows=None, tile_cols: int = 0, out=None) -> torch.Tensor:
     """The item-item matrix ``W = D_i^-1 X^T D_u^-1 X`` of the three-step random walk on a binary resident ``features.DeviceCSR`` X
