@@ -736,6 +736,33 @@ int sbr_ease_weights_f32(float* P, int n, long ld, float* diag, void* stream);
 int sbr_slim_cd_f32(const float* G, int m, long ldg, int c0, int c1, float l1, float l2, int max_iter, float tol, float* W, long ldw,
                     int* n_iter, void* stream);
 
+/* ---- the two baselines without a score matrix (csrc/shared_rank.hip) — algorithms/naive_algs.py:11-60 -----------------------------
+ * PopularItems (algorithms/naive_algs.py:35-60: `self.pop_distribution[i_idxs]`) gives every user the same score row, so a user's list
+ * is the shared ranking minus the user's exclusions (eval/eval.py:219-220, then torch.topk at :320), found with about k + |excl(u)|
+ * reads instead of a [Bu, n_items] score matrix. order: int32 [n_items], a permutation of the split's item positions, best first;
+ * score: fp32 [n_items], indexed by position, not by rank. The kernel does not sort: whatever `order` says is the ranking (the value
+ * rules live where `order` is made: the stable descending order of sbr_topk_rows). The exclusion CSR is the one sbr_mask_scores takes:
+ * indptr int64 over user ids, indices int32 ascending and unique within a row, columns = positions in the split; u_idx: int64 [Bu]
+ * (NULL = identity), in any order, repeats allowed. Row b of out_val / out_idx [Bu, k] gets (score[p], p) for the first k entries p of
+ * `order` that excl(u_b) does not contain, in rank order. One wave per user steps through `order` 64 ranks at a time: a lane tests its
+ * entry by a binary search in the CSR row (an empty row skips the test), a ballot of the kept lanes gives each its slot, and the walk
+ * stops once k are found or `order` ends. Slots behind a user's last scoreable item get (-inf, -1), the empty-slot convention of the
+ * fused scorers and of sbr_merge_topk; a kept item whose score is -inf keeps its index: only empty slots carry -1. k >= 1 with no upper
+ * limit (nothing is held on chip; k > n_items just pads). An entry of `order` outside [0, n_items) is passed over, never read through.
+ * Bu == 0 returns without a launch. No LDS, no atomics, one writer per output element: the same bits on every run, valid in
+ * deterministic mode. New (additive to ABI 4). */
+int sbr_shared_rank_topk(const int* order, const float* score, int n_items, const long* u_idx, const long* excl_indptr,
+                         const int* excl_indices, long Bu, int k, float* out_val, int* out_idx, void* stream);
+/* RandomItems (algorithms/naive_algs.py:11-32: `torch.rand(i_idxs.shape)` from the CPU's global generator, so a list there depends on
+ * the batch size, the order of the batches and whatever drew before) as a pure function: out[b, j] = U(seed, u_idx[b], j) for j in
+ * [0, n_items), out fp32 with leading dimension ld >= n_items, u_idx int64 [Bu] (NULL = identity). The generator is Philox4x32-10
+ * (Salmon et al., SC 2011; written out in the kernel file, no generator library): key = (low, high) 32-bit halves of `seed`, counter =
+ * (low half of the user id, high half of the user id, j / 4, 0), and word j % 4 of the output block x maps to (x >> 8) * 2^-24, an
+ * exact fp32 in [0, 1). A value depends on nothing but (seed, user id, j): not on the chunk, the launch geometry, ld or the row's
+ * place in the batch. Bu == 0 or n_items == 0 returns without a launch. One writer per element, no atomics: valid in deterministic
+ * mode. New (additive to ABI 4). */
+int sbr_uniform_rows_f32(unsigned long seed, const long* u_idx, long Bu, int n_items, float* out, long ld, void* stream);
+
 /* ---- P3alpha on 0/1 data (csrc/p3alpha.hip) --------------------------------------------------------------------------------------
  * The users x items block of the reference's P^3 (algorithms/graph_algs.py:35-65) is (D_u^-1 X)(D_i^-1 X^T)(D_u^-1 X); its last two
  * factors are the item-item model W [m, m], dense fp32 rows with leading dimension ld >= m — algorithms/graph_algs.py:35-59 (the

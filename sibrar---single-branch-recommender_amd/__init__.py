@@ -28,6 +28,7 @@ from .p3alpha import P3alpha                                                    
 from .als import AlternatingLeastSquare                                                     # noqa: F401
 from .svd import SVDAlgorithm                                                               # noqa: F401
 from .rbmf import RBMF                                                                      # noqa: F401
+from .naive import PopularItems, RandomItems                                                # noqa: F401
 from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCrossEntropy,   # noqa: F401
                      RecSampledSoftmaxLoss, RecommenderSystemLoss, RecommenderSystemLossesEnum)
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
@@ -54,10 +55,11 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
     ops.set_deterministic(deterministic)
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
-# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .slim / .p3alpha / .als / .svd / .rbmf -> class
+# .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .slim / .p3alpha / .als / .svd / .rbmf / .pop / .rand -> class
 # (algorithms/algorithms_utils.py)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
               'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ifknn': ItemFeatureKNN, 'ease': EASE,
-              'slim': SLIM, 'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF}
+              'slim': SLIM, 'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF,
+              'pop': PopularItems, 'rand': RandomItems}

@@ -25,7 +25,7 @@ class SibrarHipError(RuntimeError):
 
 _CTYPES = {
     'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
-    'unsigned long long': ctypes.c_ulonglong, 'unsigned int': ctypes.c_uint, 'signed char': ctypes.c_byte,
+    'unsigned long long': ctypes.c_ulonglong, 'unsigned long': ctypes.c_ulong, 'unsigned int': ctypes.c_uint, 'signed char': ctypes.c_byte,
 }
 
 

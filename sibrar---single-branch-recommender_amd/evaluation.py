@@ -12,7 +12,8 @@ Here the exclusion CSR and the label CSR are resident on the device; per user ba
 both fused routes for lists up to ``fused_max_k`` entries (default 32; up to 128 on request: the wide kernels), longer ones fall back,
 followed by the ranking-metric kernel (NDCG / recall / precision as defined in eval/metrics.py:4-105; ``rmet`` itself is
 absent offline, so w.r.t. ``rmet`` the metric arithmetic is parity-unpinned). ``eval_batch`` keeps the reference's
-dense-logits entry point for callers that already hold a score matrix.
+dense-logits entry point for callers that already hold a score matrix. A model with a callable ``topk_lists`` (``PopularItems``: one
+score row for all users) hands over a chunk's lists itself and none of the three routes runs.
 
 ``gather_recommender_algorithm_results`` / ``Gatherer`` (eval/eval.py:230-333) dump the per-user top-``max(top_k)`` lists next to the
 metrics; they run the same scoring loop as the evaluation.
@@ -35,6 +36,7 @@ SUPPORTED_METRICS = ('ndcg', 'precision', 'recall', 'f_score', 'hitrate', 'cover
 
 
 RANK_METRIC_MAX_KS = 8            # cut-offs per sbr_rank_metrics launch (METRIC_MAX_KS in csrc/topk.hip)
+_OWN_LISTS_LOGGED = set()         # model classes whose use of ``topk_lists`` has been logged (once per class)
 
 
 class _Cfg:
@@ -327,6 +329,17 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
         bs = int(getattr(eval_loader, 'batch_size', 256) or 256)
         if scorer not in ('fp32', 'fp16_fused', 'fp32_fused'):
             raise ValueError(f'unknown scorer {scorer!r}')
+        # a model that makes its own lists (PopularItems: every user has the same score row, so a list is the shared ranking minus the
+        # user's exclusions) provides ``topk_lists(u_idxs, items, excl_indptr, excl_indices, k) -> (val, idx)`` in the conventions of the
+        # routes below; unsharded evaluations take a chunk's lists from it and ``scorer`` has nothing to choose. Models without the hook
+        # are untouched.
+        own_lists = getattr(alg, 'topk_lists', None)
+        own_lists = own_lists if callable(own_lists) and not sharded else None
+        if own_lists is not None:
+            if type(alg) not in _OWN_LISTS_LOGGED:
+                _OWN_LISTS_LOGGED.add(type(alg))
+                logging.info(f'{getattr(alg, "name", type(alg).__name__)} makes its own top-k lists (topk_lists): scorer={scorer!r} is not used')
+            scorer = 'fp32'
         # the fused routes: (item operand made once per call, user operand made per chunk, call). fp16_fused is built for D in
         # {64, 128, 256}, fp32_fused for D in {64, 128} (D = 256 has kernels of its own, used with fused_max_d = 256); both serve lists up to
         # fused_max_k entries (ops.score_topk_fused_supported). Everything else — larger cut-offs (the reference's default evaluator
@@ -375,8 +388,10 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
             bs = max(bs, min(16384, max(1, (1 << 31) // max(hi - lo, 1))))      # <= 8 GiB of fp32 scores per chunk
         for s in range(0, len(users), bs):
             u_idxs = torch.from_numpy(users[s:s + bs].astype(np.int64)).to(device)
-            u_repr = alg.get_user_representations(u_idxs)
-            if fused and torch.is_tensor(u_repr):
+            u_repr = alg.get_user_representations(u_idxs) if own_lists is None else None
+            if own_lists is not None:
+                val, idx = own_lists(u_idxs, items, excl[0], excl[1], kmax)
+            elif fused and torch.is_tensor(u_repr):
                 # the split's exclusion mask in the scorer's layout, built once per (user chunk, item shard, D) and kept with the
                 # split like the resident CSR it is made from
                 cache = getattr(dataset, '_scorer_excl', None)

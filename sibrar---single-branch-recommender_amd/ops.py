@@ -1836,6 +1836,60 @@ def topk_rows(scores: torch.Tensor, k: int):
     return val, idx
 
 
+def _need_vec(who, name, t, dtype, n=None):
+    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        got = f'{t.dtype} {tuple(t.shape)}' if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f'{who}: {name} must be a contiguous {dtype} vector' + (f' of {n} entries' if n is not None else '') + f', got {got}')
+
+
+def shared_ranking(score: torch.Tensor) -> torch.Tensor:
+    """-> int32 [n]: the stable descending order of a finite float32 vector under the rule of ``sbr_topk_rows`` — equal scores and the two
+    zeros go in ascending index, which is what ``torch.sort(descending=True, stable=True)`` gives (include/sibrar_hip.h). The ranking
+    ``shared_rank_topk`` walks; made once per catalogue, not per user. Non-finite input raises ``ValueError``."""
+    _need_cuda(score)
+    _need_vec('shared_ranking', 'score', score, torch.float32)
+    if not bool(torch.isfinite(score).all()):
+        raise ValueError('shared_ranking: non-finite scores')
+    return torch.sort(score, descending=True, stable=True)[1].to(torch.int32)
+
+
+def shared_rank_topk(order: torch.Tensor, score: torch.Tensor, u_idx: torch.Tensor, excl_indptr: torch.Tensor, excl_indices: torch.Tensor,
+                     k: int):
+    """-> (val float32 [Bu, k], idx int32 [Bu, k]): per user the first ``k`` entries of the shared ranking ``order`` (int32, positions,
+    best first) that the user's exclusion row does not contain, with ``score`` (float32, by position) as their values; (-inf, -1) behind a
+    user's last scoreable item (``sbr_shared_rank_topk``). The exclusion CSR is the one ``mask_scores_`` takes."""
+    _need_cuda(order, score, u_idx, excl_indptr, excl_indices)
+    who = 'shared_rank_topk'
+    _need_vec(who, 'score', score, torch.float32)
+    _need_vec(who, 'order', order, torch.int32, score.numel())
+    _need_vec(who, 'u_idx', u_idx, torch.int64)
+    _need_vec(who, 'excl_indptr', excl_indptr, torch.int64)
+    _need_vec(who, 'excl_indices', excl_indices, torch.int32)
+    if int(k) != k or k < 1:
+        raise ValueError(f'{who}: k={k!r} must be an integer >= 1')
+    Bu, k = u_idx.numel(), int(k)
+    val = torch.empty(Bu, k, device=score.device, dtype=torch.float32)
+    idx = torch.empty(Bu, k, device=score.device, dtype=torch.int32)
+    call('sbr_shared_rank_topk', ptr(order), ptr(score), score.numel(), ptr(u_idx), ptr(excl_indptr), ptr(excl_indices), Bu, k, ptr(val),
+         ptr(idx), stream())
+    return val, idx
+
+
+def uniform_rows(seed: int, u_idx: torch.Tensor, n_items: int) -> torch.Tensor:
+    """-> float32 [Bu, n_items]: ``out[b, j] = U(seed, u_idx[b], j)`` in [0, 1), Philox4x32-10 keyed by ``seed`` with the counter
+    (user id, j / 4) (``sbr_uniform_rows_f32``): a value depends on the seed, the user id and the item position only."""
+    _need_cuda(u_idx)
+    _need_vec('uniform_rows', 'u_idx', u_idx, torch.int64)
+    if int(seed) != seed or not 0 <= seed < 1 << 64:
+        raise ValueError(f'uniform_rows: seed={seed!r} must be an integer in [0, 2^64)')
+    if int(n_items) != n_items or not 0 <= n_items < 1 << 31:
+        raise ValueError(f'uniform_rows: n_items={n_items!r} must be an integer in [0, 2^31)')
+    out = torch.empty(u_idx.numel(), int(n_items), device=u_idx.device, dtype=torch.float32)
+    call('sbr_uniform_rows_f32', int(seed), ptr(u_idx), u_idx.numel(), int(n_items), ptr(out), out.stride(0) if out.numel() else int(n_items),
+         stream())
+    return out
+
+
 def rank_metrics(topk_idx: torch.Tensor, u_idx, label_indptr, label_indices, ks: Sequence[int]):
     _need_cuda(topk_idx)
     Bu, kmax = topk_idx.shape
