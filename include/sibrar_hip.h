@@ -710,7 +710,8 @@ int sbr_spd_inverse_f32(float* A, int n, long ld, void* workspace, long workspac
 long sbr_spd_inverse_f32_workspace(int n);
 /* B[i][j] = P[i][j] / (-P[j][j]) for i != j, B[j][j] = 0, in place on P [n, n] with leading dimension ld —
  * algorithms/linear_algs.py:157-158 (`P / (-np.diag(P))` divides column j; B is not symmetric). One correctly rounded fp32
- * division per element. diag: n floats of scratch (the diagonal is read before it is overwritten). New (additive to ABI 4). */
+ * division per element. diag: n floats of scratch (the diagonal is read before it is overwritten; it holds the original diagonal
+ * afterwards). New (additive to ABI 4). */
 int sbr_ease_weights_f32(float* P, int n, long ld, float* diag, void* stream);
 
 /* ---- SLIM on 0/1 data (csrc/slim.hip) ------------------------------------------------------------------------------------------
@@ -871,8 +872,9 @@ int sbr_csr_times_dense_f32(const long* indptr, const int* indices, const float*
  * workgroup reads its 32 rows before it writes them). out[r][j] starts at +0.0f, receives fmaf(Y[r][k], W[k][j], .) in ascending k and
  * is multiplied once by 1.0f / s[j], with s[j] = sqrtf(max(lam[j], tiny)), tiny = max(lam[0] * 2^-46, FLT_MIN): a direction whose
  * eigenvalue drowned in the rounding of lam[0] is scaled by about 1 / (2^-23 sqrt(lam[0])) at the most instead of by 1 / 0. s [b] is
- * written too. lam NULL: the plain product Y W, s is not touched. An fp32 fmaf chain of its own, not the `ops` GEMM: that one picks
- * its kernel by shape (the bf16-split kernels from 4,096 rows at N = K = 128), which would tie the bits to n. New (additive to
+ * written too, also when n = 0 (Y and out may then be NULL). lam NULL: the plain product Y W, s is not touched. An fp32 fmaf chain of
+ * its own, not the `ops` GEMM: that one picks its kernel by shape (the bf16-split kernels from 4,096 rows at N = K = 128), which would
+ * tie the bits to n. New (additive to
  * ABI 4). */
 int sbr_rotate_cols_f32(const float* Y, long n, long ldy, int b, const float* W, long ldw, const float* lam, float* s, float* out, long ldo,
                         void* stream);

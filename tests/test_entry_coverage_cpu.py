@@ -1,0 +1,84 @@
+"""A ledger of which test reaches which entry point, from text alone (nothing is imported or run): every ``sbr_*`` function declared in
+include/sibrar_hip.h is named in some tests/test_*.py module, or stands in REACHED_THROUGH with the Python wrapper through which a
+named test module reaches it. For a table row the test checks the chain link by link: the test module names ``names``, the first
+wrapper's source names it too, every wrapper's source names the next wrapper, and the last one's source names the entry. An entry that
+a new kernel adds without a test, or a wrapper that stops calling its entry, fails here. No GPU."""
+import ast
+import glob
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TESTS = os.path.join(ROOT, 'tests')
+PACKAGE = os.path.dirname(glob.glob(os.path.join(ROOT, '*', '_lib.py'))[0])
+
+# entry -> (test module, the word it names, [(package file, function or class), ...] from the test's side to the entry's)
+_PRODUCER = ('test_hip_pinned.py', '_native', [('datasets.py', '_native_producer'), ('native_loader.py', 'NativeBatchProducer')])
+REACHED_THROUGH = {
+    'sbr_gemm_split_supported': ('test_hip_kernels.py', 'linear_nt', [('ops.py', 'linear_nt'), ('ops.py', '_mlp_kernel')]),
+    'sbr_gemm_wres_supported': ('test_hip_kernels.py', 'linear_nt', [('ops.py', 'linear_nt'), ('ops.py', '_wres_ok')]),
+    'sbr_infonce_max_n': ('test_hip_tail.py', 'infonce_max_n', [('ops.py', 'infonce_max_n')]),
+    'sbr_host_assemble_items': ('test_host_cpu.py', 'recbole_negative_collate', [('sampling.py', 'recbole_negative_collate')]),
+    'sbr_host_csr_contains': ('test_hip_pinned.py', 'DevicePositiveIndex', [('sampling.py', 'DevicePositiveIndex')]),
+    'sbr_host_mt19937_randint': ('test_host_cpu.py', 'legacy_randint', [('sampling.py', 'legacy_randint')]),
+    'sbr_producer_create': _PRODUCER, 'sbr_producer_set_entity': _PRODUCER, 'sbr_producer_start': _PRODUCER, 'sbr_producer_next': _PRODUCER,
+    'sbr_producer_wait': _PRODUCER, 'sbr_producer_release': _PRODUCER, 'sbr_producer_stop': _PRODUCER, 'sbr_producer_destroy': _PRODUCER,
+}
+# the dense-block entries that only model fits reached before tests/test_hip_block_edges.py: named there directly, not through a wrapper
+NAMED_IN_BLOCK_EDGES = ('sbr_rotate_cols_f32', 'sbr_col_residual_f32', 'sbr_ease_weights_f32')
+
+
+def _read(path):
+    with open(path) as fh:
+        return fh.read()
+
+
+def declared():
+    text = re.sub(r'/\*.*?\*/', ' ', _read(os.path.join(ROOT, 'include', 'sibrar_hip.h')), flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    return sorted(set(re.findall(r'\b(sbr_\w+)\s*\(', text)))
+
+
+def _test_modules():
+    return {os.path.basename(p): _read(p) for p in sorted(glob.glob(os.path.join(TESTS, 'test_*.py'))) if os.path.abspath(p) != os.path.abspath(__file__)}
+
+
+def names(text, word):
+    return re.search(r'(?<![A-Za-z0-9_])' + re.escape(word) + r'(?![A-Za-z0-9_])', text) is not None
+
+
+def source_of(file, name):
+    text = _read(os.path.join(PACKAGE, file))
+    found = [n for n in ast.walk(ast.parse(text)) if isinstance(n, (ast.FunctionDef, ast.ClassDef)) and n.name == name]
+    assert len(found) == 1, f'{file}: {len(found)} definitions of {name}'
+    return ast.get_source_segment(text, found[0])
+
+
+def test_every_declared_entry_is_reached_by_a_test():
+    entries, mods = declared(), _test_modules()
+    assert len(entries) >= 157 and 'sbr_last_error' in entries and all(e.startswith('sbr_') for e in entries)
+    unnamed = [e for e in entries if not any(names(text, e) for text in mods.values())]
+    unreached = sorted(set(unnamed) - set(REACHED_THROUGH))
+    print(f'{len(entries)} entries declared, {len(entries) - len(unnamed)} named in a test module, {len(unnamed)} reached through a wrapper, '
+          f'{len(unreached)} reached by nothing')
+    assert not unreached, f'declared in include/sibrar_hip.h and reached by no test: {unreached}'
+    stale = sorted(e for e in REACHED_THROUGH if e not in entries or e not in unnamed)
+    assert not stale, f'rows of REACHED_THROUGH that are not needed (named directly by now, or no longer declared): {stale}'
+
+
+def test_the_table_rows_hold_link_by_link():
+    mods = _test_modules()
+    for entry, (module, word, chain) in REACHED_THROUGH.items():
+        assert module in mods and names(mods[module], word), f'{entry}: tests/{module} does not name {word}'
+        sources = [source_of(file, name) for file, name in chain]
+        assert names(sources[0], word), f'{entry}: {chain[0]} does not name {word}'
+        for (file, name), src, nxt in zip(chain, sources, chain[1:]):
+            assert names(src, nxt[1]), f'{entry}: {file}:{name} does not name {nxt[1]}'
+        assert names(sources[-1], entry), f'{entry}: {chain[-1]} does not name the entry'
+
+
+def test_the_dense_block_entries_are_named_directly():
+    text = _read(os.path.join(TESTS, 'test_hip_block_edges.py'))
+    for entry in NAMED_IN_BLOCK_EDGES + ('sbr_gram_f32', 'sbr_als_gram_f32', 'sbr_als_solve_rows_f32', 'sbr_tri_solve_rows_f32', 'sbr_chol_f32'):
+        assert names(text, f"'{entry}'"), f'tests/test_hip_block_edges.py does not call {entry}'
+    assert 'pytestmark = pytest.mark.gpu' in text
