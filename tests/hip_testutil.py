@@ -1,7 +1,8 @@
 """Helpers shared by the kernel-level GPU tests (tests/test_hip_rowops.py, tests/test_hip_tail.py): the ctypes call wrapper, operands as
 strided / shifted views inside NaN-filled buffers with the "nothing outside the addressed rows was written" check, and the bound
 assertions. u = 2^-24 is the unit roundoff of fp32; see the header of test_hip_rowops.py for the conventions. A plain module: no
-fixtures, no pytest hooks."""
+fixtures, no pytest hooks. ``_BigLd`` (for tests/test_hip_big_ld.py) is the same kind of view at a leading dimension of 2^25 + 64
+elements inside one untouched 16.1 GiB buffer, with guard bands in place of the whole-buffer check."""
 import importlib
 
 import numpy as np
@@ -99,6 +100,87 @@ class _Buf:
         kept = torch.isnan(host[~may]) if host.dtype.is_floating_point else host[~may] == self.guard
         assert bool(kept.all()), f'{what}: {int((~kept).sum())} elements outside the addressed rows / columns were written'
         return self._view(host)
+
+
+LD_BIG = (1 << 25) + 64                     # a leading dimension that puts row 64 past element 2^31 and row 128 past element 2^32
+BIG_ROWS = 130                               # the most rows a _BigLd view may have
+BIG_ELEMS = (BIG_ROWS - 1) * LD_BIG + 256    # fp32 elements of the one buffer (about 16.1 GiB)
+BIG_HEADROOM = 4 << 30                       # free device memory asked for beyond the buffer
+NAN_BITS = 0x7FC00000                        # what torch writes for float('nan'): the fill pattern of _Buf, compared bit for bit
+_BIG = {'flat': None}
+
+
+def big_ld_crossings(rows):
+    """which wraps a view of ``rows`` rows at LD_BIG can show: the start of its last row lies past element 2^31 (an int product wraps
+    negative), past element 2^32 (an unsigned product wraps), past byte 2^32 (a 32-bit byte offset wraps)"""
+    last = (rows - 1) * LD_BIG
+    return {'2^31 elements': last >= 1 << 31, '2^32 elements': last >= 1 << 32, '2^32 bytes': 4 * last >= 1 << 32}
+
+
+class _BigLd:
+    """A [rows, cols] fp32 view with row stride LD_BIG into ONE lazily allocated, never filled buffer of BIG_ELEMS elements (module
+    level: a second _BigLd reuses it, so only one is in use at a time; ``release()`` frees it). rows <= 130: row 64 starts past
+    element 2^31, row 128 past element 2^32, every row from 32 on past byte 2^32. In place of _Buf's whole-buffer check there is a
+    guard band: the GUARD elements behind each row's ``cols`` and in front of each row start except row 0 (the view starts at the
+    buffer's first element) hold the NaN pattern and are compared bit for bit afterwards (the last row's band ends where the buffer
+    ends); the view itself is remembered as it was handed out, and rows the call must not write are compared with that bit for bit."""
+
+    def __init__(self, rows, cols, ld=None, off=0, data=None, fill=None):
+        assert ld in (None, LD_BIG) and off == 0 and 1 <= rows <= BIG_ROWS and 1 <= cols <= LD_BIG - 2 * GUARD
+        self.rows, self.cols, self.ld = rows, cols, LD_BIG
+        self.crossings = big_ld_crossings(rows)
+        if rows > 128:
+            assert all(self.crossings.values()), self.crossings
+        flat = self._flat()
+        self.t = flat.as_strided((rows, cols), (LD_BIG, 1))
+        tail = min(GUARD, BIG_ELEMS - ((rows - 1) * LD_BIG + cols))
+        assert tail > 0
+        self.bands = [flat.as_strided((rows - 1, GUARD), (LD_BIG, 1), cols), flat.as_strided((1, tail), (LD_BIG, 1), (rows - 1) * LD_BIG + cols)]
+        if rows > 1:
+            self.bands.append(flat.as_strided((rows - 1, GUARD), (LD_BIG, 1), LD_BIG - GUARD))
+        for b in self.bands:
+            b.fill_(NAN)
+        if data is not None:
+            self.t.copy_(data.to(DEV))
+        else:
+            self.t.fill_(NAN if fill is None else fill)
+        self.before = _bits(self.t.contiguous().cpu())
+        assert self.t.data_ptr() == flat.data_ptr() and self.t[rows - 1].data_ptr() - flat.data_ptr() == 4 * (rows - 1) * LD_BIG
+
+    @staticmethod
+    def _flat():
+        if _BIG['flat'] is None:
+            import pytest
+            free, _ = torch.cuda.mem_get_info()
+            if free < 4 * BIG_ELEMS + BIG_HEADROOM:
+                pytest.skip(f'{free} bytes of device memory free, {4 * BIG_ELEMS + BIG_HEADROOM} needed (the buffer and 4 GiB)')
+            _BIG['flat'] = torch.empty(BIG_ELEMS, device=DEV, dtype=torch.float32)
+        return _BIG['flat']
+
+    @staticmethod
+    def release():
+        _BIG['flat'] = None
+        torch.cuda.empty_cache()
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def host(self):
+        return self.t.contiguous().cpu()
+
+    def check_untouched(self, written_rows=None, what=''):
+        """the guard bands still hold the NaN pattern and every row outside ``written_rows`` (None: every row may be written) holds
+        the bits it was handed out with; -> the view on the host"""
+        for b in self.bands:
+            kept = _bits(b.contiguous().cpu()) == NAN_BITS
+            assert bool(kept.all()), f'{what}: {int((~kept).sum())} guard elements around the rows were written'
+        host = self.host()
+        may = torch.zeros(self.rows, dtype=torch.bool)
+        may[slice(None) if written_rows is None else written_rows] = True
+        same = _bits(host)[~may] == self.before[~may]
+        assert bool(same.all()), f'{what}: {int((~same).sum())} elements of rows outside the addressed ones were written'
+        return host
 
 
 def _i32(x):

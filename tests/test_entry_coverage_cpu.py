@@ -2,7 +2,9 @@
 include/sibrar_hip.h is named in some tests/test_*.py module, or stands in REACHED_THROUGH with the Python wrapper through which a
 named test module reaches it. For a table row the test checks the chain link by link: the test module names ``names``, the first
 wrapper's source names it too, every wrapper's source names the next wrapper, and the last one's source names the entry. An entry that
-a new kernel adds without a test, or a wrapper that stops calling its entry, fails here. No GPU."""
+a new kernel adds without a test, or a wrapper that stops calling its entry, fails here. A second ledger covers the entries that take a
+leading dimension (a parameter ``long ld...``): each is named in tests/test_hip_big_ld.py, which runs it with row offsets past 2^31
+and 2^32 elements, or stands in BIG_LD_EXEMPT with a reason, so that a new entry with an ld fails until someone decides. No GPU."""
 import ast
 import glob
 import os
@@ -26,6 +28,25 @@ REACHED_THROUGH = {
 }
 # the dense-block entries that only model fits reached before tests/test_hip_block_edges.py: named there directly, not through a wrapper
 NAMED_IN_BLOCK_EDGES = ('sbr_rotate_cols_f32', 'sbr_col_residual_f32', 'sbr_ease_weights_f32')
+
+
+# entries with a `long ld...` parameter that tests/test_hip_big_ld.py (an operand at a leading dimension past 2^25 elements) leaves out
+_OUT = 'out of scope of tests/test_hip_big_ld.py: '
+BIG_LD_EXEMPT = {
+    **{e: _OUT + 'the GEMM family' for e in (
+        'sbr_gemm_f32', 'sbr_gemm_nt_splitk_f32', 'sbr_gemm_split_wide_f32', 'sbr_gemm_tn_f32', 'sbr_gemm_tn_f32_slabs', 'sbr_gemm_wres_f32',
+        'sbr_gemm_split_f32', 'sbr_gemm_split_bnstats_f32', 'sbr_gemm_split_proj_f32')},
+    **{e: _OUT + 'a table addressed by row, crossing 2^31 needs the rows themselves' for e in (
+        'sbr_scatter_add_rows_det', 'sbr_gather_rows', 'sbr_lookup_rows_supported', 'sbr_lookup_rows', 'sbr_scatter_add_rows',
+        'sbr_scatter_add_rows_sorted', 'sbr_bag_mean_fwd', 'sbr_bag_mean_bwd', 'sbr_csr_project_fwd', 'sbr_csr_project_bwd',
+        'sbr_csr_project_bwd_gather')},
+    **{e: _OUT + 'a training-step tail kernel' for e in (
+        'sbr_act_grad_gather', 'sbr_act_grad_gather_colsum', 'sbr_colsum', 'sbr_infonce_fwd', 'sbr_infonce_bwd', 'sbr_infonce_gemm_fwd',
+        'sbr_infonce_gemm_bwd')},
+    **{e: _OUT + 'a scorer or fused model kernel' for e in (
+        'sbr_floor_scores', 'sbr_proto_sim_fwd', 'sbr_proto_sim_bwd', 'sbr_proto_score_fwd', 'sbr_proto_score_bwd', 'sbr_anchor_mix_fwd',
+        'sbr_anchor_mix_bwd', 'sbr_cluster_affil_fwd', 'sbr_cluster_affil_bwd', 'sbr_uniform_rows_f32')},
+}
 
 
 def _read(path):
@@ -75,6 +96,30 @@ def test_the_table_rows_hold_link_by_link():
         for (file, name), src, nxt in zip(chain, sources, chain[1:]):
             assert names(src, nxt[1]), f'{entry}: {file}:{name} does not name {nxt[1]}'
         assert names(sources[-1], entry), f'{entry}: {chain[-1]} does not name the entry'
+
+
+def entries_with_a_leading_dimension():
+    """every declared sbr_* function with a parameter of type ``long`` whose name matches ld\\w*"""
+    text = re.sub(r'/\*.*?\*/', ' ', _read(os.path.join(ROOT, 'include', 'sibrar_hip.h')), flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    found = []
+    for name, params in re.findall(r'\b(sbr_\w+)\s*\(([^)]*)\)', text):
+        if any(re.fullmatch(r'(?:const\s+)?long\s+ld\w*', p.strip()) for p in params.split(',')):
+            found.append(name)
+    return sorted(set(found))
+
+
+def test_every_entry_with_a_leading_dimension_is_pinned_past_2_to_31_or_exempt():
+    with_ld = entries_with_a_leading_dimension()
+    text = _read(os.path.join(TESTS, 'test_hip_big_ld.py'))
+    named = [e for e in with_ld if names(text, f"'{e}'")]
+    print(f'{len(with_ld)} entries take a leading dimension, {len(named)} named in tests/test_hip_big_ld.py, {len(BIG_LD_EXEMPT)} exempt')
+    assert len(with_ld) >= 61 and 'sbr_gram_dense' in with_ld and 'sbr_topk_rows' in with_ld and 'sbr_splitk_reduce_multi' not in with_ld
+    undecided = sorted(set(with_ld) - set(named) - set(BIG_LD_EXEMPT))
+    assert not undecided, f'take a leading dimension, and are neither in tests/test_hip_big_ld.py nor in BIG_LD_EXEMPT: {undecided}'
+    stale = sorted(e for e in BIG_LD_EXEMPT if e not in with_ld or e in named)
+    assert not stale, f'rows of BIG_LD_EXEMPT that are not needed (named in the module by now, or without a leading dimension): {stale}'
+    assert all(reason.strip() for reason in BIG_LD_EXEMPT.values()) and 'pytestmark = pytest.mark.gpu' in text
 
 
 def test_the_dense_block_entries_are_named_directly():
