@@ -562,6 +562,24 @@ int sbr_merge_topk(const float* vals, const int* idxs, int W, long Bu, int k, fl
 /* NDCG / recall / precision @ ks from top-k indices and CSR labels — eval/metrics.py:4-105. out: [3, n_ks, Bu]. */
 int sbr_rank_metrics(const int* topk_idx, int kmax, const long* u_idx, const long* label_indptr, const int* label_indices,
                      long Bu, const int* ks, int n_ks, float* out, void* stream);
+/* The rank-position metrics DCG / average precision / reciprocal rank @ ks: what `config.metrics` may name beyond the three above when
+ * the reference hands it to `rmet.calculate` (eval/eval.py:99-102; its analysis configuration asks for 'ap',
+ * utilities/analysis_utils.py:260). `rmet` is absent offline, so the definitions are this project's and parity-unpinned against it.
+ * Binary relevance; hit_r = [topk_idx[b, r] in labels(u_b)] (a slot holding -1 is never a hit; a repeated item counts again),
+ * h_r = the hits at ranks <= r, n_pos = the length of the label row:
+ *   dcg@k = sum_{r < k, hit_r} 1 / log2(r + 2)
+ *   ap@k  = (sum_{r < k, hit_r} h_r / (r + 1)) / min(k, n_pos)        (0 when n_pos == 0)
+ *   rr@k  = 1 / (r0 + 1), r0 the smallest r < k with hit_r             (0 without one)
+ * out: [3, n_ks, Bu] in the order (dcg, ap, rr). Operands and conventions of sbr_rank_metrics: CSR labels over user ids, columns
+ * ascending within a row, u_idx == NULL means row b, ks ascending and <= kmax, at most 8 cut-offs; any kmax >= 1. The float order is
+ * fixed: both sums run over the hits in ascending rank, one fp32 addition per hit starting from 0.f; a term is one correctly rounded
+ * fp32 division (1.f / log2f((float)(r + 2)), (float)h_r / (float)(r + 1)) of exactly converted integers, and so are the final
+ * apn / (float)min(k, n_pos) and 1.f / (float)(r0 + 1). One wave per user, 64 ranks per step: a coalesced load, a binary search per
+ * lane, a ballot for the hit mask, and a walk of its set bits (serial in the hits, not in kmax). No LDS, no atomics, one writer per
+ * element: the same bits on every run, valid in deterministic mode. A refused call writes nothing; Bu == 0 returns without a launch.
+ * New (additive to ABI 4). */
+int sbr_rank_metrics_pos(const int* topk_idx, int kmax, const long* u_idx, const long* label_indptr, const int* label_indices,
+                         long Bu, const int* ks, int n_ks, float* out, void* stream);
 /* fused scorer: fp16 MFMA  U[Bu, D] x I[I_s, D]^T  with the exclusion mask and the running per-user top-k kept on chip; the
  * [Bu, I_s] score matrix is never written (BASELINE config 5). D in {64, 128, 256}, 1 <= k <= 128 (k > 32 runs the wide
  * instantiation of the one-pass kernel: same contract, same score bits; the two-pass route takes k <= 32 only and answers a longer

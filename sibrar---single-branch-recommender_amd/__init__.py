@@ -34,7 +34,8 @@ from .losses import (InfoNCE, RecBayesianPersonalizedRankingLoss, RecBinaryCross
 from .optim import FlatParameters, FusedOptimizer                                           # noqa: F401
 from .trainer import Trainer                                                                # noqa: F401
 from .engine import FusedTrainStep                                                          # noqa: F401
-from .evaluation import FullEvaluator, Gatherer, evaluate_recommender_algorithm, gather_recommender_algorithm_results                       # noqa: F401
+from .evaluation import (FullEvaluator, Gatherer, evaluate_recommender_algorithm, gather_recommender_algorithm_results,   # noqa: F401
+                         paired_significance)
 from .datasets import NegativeSamplingDataLoader, SyntheticDataset                          # noqa: F401
 from .splitdata import SplitDataset, load_split_dataset                                     # noqa: F401
 from . import ops, parallel, sampling                                                       # noqa: F401

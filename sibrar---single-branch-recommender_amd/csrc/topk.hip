@@ -2,9 +2,12 @@
 //   sbr_mask_scores   out[b, excl(u_b)] = -inf          (eval.py:219-220, CSR rows instead of a dense bool matrix)
 //   sbr_topk_rows     exact top-k of every score row, sorted by (score desc, index asc)  (torch.topk, eval.py:320)
 //   sbr_rank_metrics  NDCG / recall / precision @k from the top-k indices and the CSR labels (eval/metrics.py:4-105)
+//   sbr_rank_metrics_pos  DCG / average precision / reciprocal rank @k, the metrics that depend on where a hit stands
+//                     (what config.metrics may name beyond the three above: eval/eval.py:99-102, utilities/analysis_utils.py:260)
 // Integer / ordering work: results are exact (no tolerance); the only freedom is the order of exactly tied scores,
 // which torch.topk leaves unspecified and which is fixed here to "lower index first" (NaN first, -0 == +0: the rule at f2key).
 #include "common.h"
+#include "csr_walk.h"
 
 __global__ void mask_scores_kernel(float* __restrict__ S, long ld, const long* __restrict__ u_idx,
                                    const long* __restrict__ indptr, const int* __restrict__ indices, long Bu, int item_offset, int n_cols) {
@@ -411,5 +414,92 @@ extern "C" int sbr_rank_metrics(const int* topk_idx, int kmax, const long* u_idx
   }
   rank_metrics_kernel<<<sbr_cdiv(Bu, 256), 256, 0, (hipStream_t)stream>>>(topk_idx, kmax, u_idx, label_indptr, label_indices, Bu, kl, out);
   SBR_CHECK_LAUNCH("sbr_rank_metrics");
+  return SBR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the rank-position metrics (eval/eval.py:99-102 hands config.metrics to rmet.calculate; utilities/analysis_utils.py:260 asks for 'ap'):
+// with hit_r = [topk[b, r] in labels(u_b)] (a slot holding -1 is never a hit) and h_r = the hits at ranks <= r,
+//   dcg@k = sum_{r<k, hit_r} 1 / log2(r + 2)
+//   ap@k  = (sum_{r<k, hit_r} h_r / (r + 1)) / min(k, n_pos)          (0 when n_pos == 0)
+//   rr@k  = 1 / (r0 + 1), r0 the first r < k with hit_r                (0 without one)
+// out: [3, n_ks, Bu] (dcg, ap, rr). One wave per user, four users per workgroup. A step takes 64 ranks: lane l loads topk[b, base + l]
+// (coalesced) and searches the label row, a ballot gives the step's hit mask, and the sums walk the mask's set bits in ascending rank,
+// one fp32 addition per hit from 0.f: the serial length is the number of hits, not kmax. A cut-off inside the step splits the walk: the
+// bits below it are taken, the cut-off is written, the walk goes on. Every lane carries the same sums; lane 0 stores. No LDS, no
+// atomics, any kmax >= 1; lanes past kmax in the last step stay out of the ballot.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int klist_at(const KList& ks, int q) {      // ks.k[q] by selects: a run-time index into a by-value argument
+  int k = ks.k[0];                                                      // would put the list into scratch memory
+#pragma unroll
+  for (int i = 1; i < METRIC_MAX_KS; ++i) k = (i == q) ? ks.k[i] : k;
+  return k;
+}
+
+__global__ __launch_bounds__(256) void rank_metrics_pos_kernel(const int* __restrict__ topk, int kmax, const long* __restrict__ u_idx,
+                                                               const long* __restrict__ indptr, const int* __restrict__ indices, long Bu,
+                                                               KList ks, float* __restrict__ out) {
+  const long b = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (b >= Bu) return;                                          // uniform per wave
+  const int lane = threadIdx.x & 63;
+  const long u = u_idx ? u_idx[b] : b;
+  const long beg = indptr[u], end = indptr[u + 1];
+  const long npos = end - beg;
+  const int* __restrict__ row = topk + b * (long)kmax;
+  float dcg = 0.f, apn = 0.f;
+  int hits = 0, q = 0;
+  long first = -1;
+  for (long base = 0; base < kmax && q < ks.n; base += 64) {        // long: base + 64 may pass 2^31 when kmax is close to it
+    bool hit = false;
+    if (lane < kmax - base) {
+      const int item = row[base + lane];
+      if (item >= 0 && npos > 0) {
+        const long lo = sbr_csr_lower_bound(indices, beg, end, item);
+        hit = lo < end && indices[lo] == item;
+      }
+    }
+    const unsigned long long mask = __ballot(hit);
+    int done = 0;                                               // ranks of this step already walked
+    while (done < 64) {
+      const int kq = q < ks.n ? klist_at(ks, q) : 0x7FFFFFFF;
+      const bool emit = kq - base <= 64;                        // the next cut-off ends inside this step (kq > base + done always)
+      const int lim = emit ? (int)(kq - base) : 64;
+      unsigned long long m = mask & (lim < 64 ? (1ull << lim) - 1ull : ~0ull) & ~((1ull << done) - 1ull);
+      while (m) {                                               // the hits of [base + done, base + lim) in ascending rank
+        const long r = base + __ffsll((long long)m) - 1;
+        m &= m - 1ull;
+        ++hits;
+        dcg += 1.f / log2f((float)(r + 2));
+        apn += (float)hits / (float)(r + 1);
+        if (first < 0) first = r;
+      }
+      if (!emit) break;
+      if (lane == 0) {
+        const long den = kq < npos ? kq : npos;
+        out[(0L * ks.n + q) * Bu + b] = dcg;
+        out[(1L * ks.n + q) * Bu + b] = npos > 0 ? apn / (float)den : 0.f;
+        out[(2L * ks.n + q) * Bu + b] = first >= 0 ? 1.f / (float)(first + 1) : 0.f;
+      }
+      ++q;
+      done = lim;
+    }
+  }
+}
+
+extern "C" int sbr_rank_metrics_pos(const int* topk_idx, int kmax, const long* u_idx, const long* label_indptr,
+                                    const int* label_indices, long Bu, const int* ks, int n_ks, float* out, void* stream) {
+  SBR_REQUIRE(n_ks >= 1 && n_ks <= METRIC_MAX_KS, "sbr_rank_metrics_pos: n_ks=%d outside [1, %d]", n_ks, METRIC_MAX_KS);
+  if (Bu == 0) return SBR_OK;
+  SBR_REQUIRE(topk_idx && label_indptr && label_indices && ks && out, "sbr_rank_metrics_pos: null operand");
+  SBR_REQUIRE(Bu > 0 && Bu <= 4L * 0x7FFFFFFF, "sbr_rank_metrics_pos: Bu=%ld outside what one launch takes", Bu);
+  KList kl;
+  kl.n = n_ks;
+  for (int i = 0; i < METRIC_MAX_KS; ++i) kl.k[i] = 0x7FFFFFFF;
+  for (int i = 0; i < n_ks; ++i) {
+    SBR_REQUIRE(ks[i] >= 1 && ks[i] <= kmax && (i == 0 || ks[i] > ks[i - 1]), "sbr_rank_metrics_pos: ks must be ascending and <= kmax");
+    kl.k[i] = ks[i];
+  }
+  rank_metrics_pos_kernel<<<sbr_cdiv(Bu, 4), 256, 0, (hipStream_t)stream>>>(topk_idx, kmax, u_idx, label_indptr, label_indices, Bu, kl, out);
+  SBR_CHECK_LAUNCH("sbr_rank_metrics_pos");
   return SBR_OK;
 }

@@ -11,12 +11,17 @@ Here the exclusion CSR and the label CSR are resident on the device; per user ba
     matrix; D in {64, 128} (D = 256 with ``fused_max_d=256``) and finite item values, anything else falls back to ``'fp32'``,
 both fused routes for lists up to ``fused_max_k`` entries (default 32; up to 128 on request: the wide kernels), longer ones fall back,
 followed by the ranking-metric kernel (NDCG / recall / precision as defined in eval/metrics.py:4-105; ``rmet`` itself is
-absent offline, so w.r.t. ``rmet`` the metric arithmetic is parity-unpinned). ``eval_batch`` keeps the reference's
+absent offline, so w.r.t. ``rmet`` the metric arithmetic is parity-unpinned) and, when ``config.metrics`` names one of them, by the
+rank-position kernel (``dcg``, ``ap``, ``rr``: defined in include/sibrar_hip.h at ``sbr_rank_metrics_pos``, equally unpinned against
+``rmet``). ``eval_batch`` keeps the reference's
 dense-logits entry point for callers that already hold a score matrix. A model with a callable ``topk_lists`` (``PopularItems``: one
 score row for all users) hands over a chunk's lists itself and none of the three routes runs.
 
 ``gather_recommender_algorithm_results`` / ``Gatherer`` (eval/eval.py:230-333) dump the per-user top-``max(top_k)`` lists next to the
 metrics; they run the same scoring loop as the evaluation.
+
+``paired_significance`` (eval/stat_tests.py:15-38) is the paired t-test with Bonferroni correction over the per-user arrays that
+``get_results(return_raw_results=True)`` returns; it runs on the host.
 """
 from __future__ import annotations
 
@@ -32,17 +37,19 @@ import torch
 
 from . import ops, parallel
 
-SUPPORTED_METRICS = ('ndcg', 'precision', 'recall', 'f_score', 'hitrate', 'coverage')
+DEFAULT_METRICS = ('ndcg', 'precision', 'recall', 'f_score', 'hitrate', 'coverage')      # what an evaluator without a config reports
+POSITION_METRICS = ('dcg', 'ap', 'rr')             # sbr_rank_metrics_pos, in the order of its output; computed only when asked for
+SUPPORTED_METRICS = DEFAULT_METRICS + POSITION_METRICS
 
 
-RANK_METRIC_MAX_KS = 8            # cut-offs per sbr_rank_metrics launch (METRIC_MAX_KS in csrc/topk.hip)
+RANK_METRIC_MAX_KS = 8            # cut-offs per sbr_rank_metrics / sbr_rank_metrics_pos launch (METRIC_MAX_KS in csrc/topk.hip)
 _OWN_LISTS_LOGGED = set()         # model classes whose use of ``topk_lists`` has been logged (once per class)
 
 
 class _Cfg:
     """The fields of the reference's EvalConfig (data/config_classes.py:183-198) with its defaults."""
 
-    def __init__(self, top_k=(1, 3, 5, 10, 20, 50, 100), metrics=SUPPORTED_METRICS, calculate_std=True,
+    def __init__(self, top_k=(1, 3, 5, 10, 20, 50, 100), metrics=DEFAULT_METRICS, calculate_std=True,
                  calculate_group_metrics=False, user_group_features=None):
         self.top_k, self.metrics, self.calculate_std = list(top_k), list(metrics), calculate_std
         self.calculate_group_metrics, self.user_group_features = calculate_group_metrics, user_group_features
@@ -148,6 +155,9 @@ class FullEvaluator:
         # [3, n_ks, Bu]; the kernel takes up to RANK_METRIC_MAX_KS cut-offs per launch
         m = torch.cat([ops.rank_metrics(topk_idx, u_long, indptr, indices, ks[c:c + RANK_METRIC_MAX_KS])
                        for c in range(0, len(ks), RANK_METRIC_MAX_KS)], dim=1) if ks else None
+        wanted_pos = [name for name in POSITION_METRICS if name in self.config.metrics]
+        mp = torch.cat([ops.rank_metrics_pos(topk_idx, u_long, indptr, indices, ks[c:c + RANK_METRIC_MAX_KS])
+                        for c in range(0, len(ks), RANK_METRIC_MAX_KS)], dim=1) if ks and wanted_pos else None
         for name in (self._user_features or ()):
             gmap = self._group_map(name, topk_idx.device)[0]
             # ids beyond the map (only possible when the dataset does not state n_users): category -1 -> KeyError in get_results
@@ -167,6 +177,8 @@ class FullEvaluator:
             if 'f_score' in self.config.metrics:
                 den = pr + rc
                 self._results[self._key('f_score', k)].append(torch.where(den > 0, 2 * pr * rc / den.clamp_min(1e-30), den))
+            for name in wanted_pos:
+                self._results[self._key(name, k)].append(mp[POSITION_METRICS.index(name), qi])
         if 'coverage' in self.config.metrics:
             self._topk.append(topk_idx)
 
@@ -432,6 +444,33 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
         if hasattr(alg, 'check_index_errors'):
             alg.check_index_errors()
     return kmax
+
+
+def paired_significance(raw_by_model: dict, threshold: float = 0.05) -> dict:
+    """eval/stat_tests.py:15-38 as a function: ``raw_by_model`` maps a model name to the per-user array of ONE metric (what
+    ``get_results(return_raw_results=True)`` returns under that metric's key), all over the same users in the same order. The best model
+    is the one with the largest mean (NaNs left out of the mean); every other model is compared with it by the paired two-sided t-test
+    ``scipy.stats.ttest_rel(best, other, nan_policy='omit')`` (a pair with a NaN on either side is dropped), and the significance
+    threshold is Bonferroni-corrected by the number of comparisons. ->
+
+      ``best``        the best model's name,
+      ``threshold``   ``threshold / (n_models - 1)``,
+      ``p_values``    {other model: p-value},
+      ``significant`` {other model: p-value <= the corrected threshold}.
+
+    Fewer than two models or arrays of unequal lengths raise ``ValueError``. Host only."""
+    from scipy import stats
+    if len(raw_by_model) < 2:
+        raise ValueError(f'paired_significance: {len(raw_by_model)} model(s) given, a comparison needs at least two')
+    arrays = {name: np.asarray(v, dtype=np.float64).reshape(-1) for name, v in raw_by_model.items()}
+    lengths = {name: a.size for name, a in arrays.items()}
+    if len(set(lengths.values())) != 1:
+        raise ValueError(f'paired_significance: the arrays must cover the same users, got lengths {lengths}')
+    best = max(arrays, key=lambda name: np.nanmean(arrays[name]))
+    corrected = threshold / (len(arrays) - 1)
+    p_values = {name: float(stats.ttest_rel(arrays[best], a, nan_policy='omit').pvalue) for name, a in arrays.items() if name != best}
+    return {'best': best, 'threshold': corrected, 'p_values': p_values,
+            'significant': {name: bool(p <= corrected) for name, p in p_values.items()}}
 
 
 class Gatherer:

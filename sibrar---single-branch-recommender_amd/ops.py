@@ -1901,6 +1901,18 @@ def rank_metrics(topk_idx: torch.Tensor, u_idx, label_indptr, label_indices, ks:
     return out
 
 
+def rank_metrics_pos(topk_idx: torch.Tensor, u_idx, label_indptr, label_indices, ks: Sequence[int]):
+    """-> float32 [3, n_ks, Bu]: dcg, ap and rr at every cut-off of ``ks`` (``sbr_rank_metrics_pos``; the operands of ``rank_metrics``)"""
+    _need_cuda(topk_idx)
+    Bu, kmax = topk_idx.shape
+    import ctypes
+    ks_arr = (ctypes.c_int * len(ks))(*ks)
+    out = torch.empty(3, len(ks), Bu, device=topk_idx.device, dtype=torch.float32)
+    call('sbr_rank_metrics_pos', ptr(topk_idx), kmax, ptr(u_idx), ptr(label_indptr), ptr(label_indices), Bu,
+         ctypes.cast(ks_arr, ctypes.c_void_p), len(ks), ptr(out), stream())
+    return out
+
+
 def cast_f16(x: torch.Tensor) -> torch.Tensor:
     _need_cuda(x)
     x = _f32c(x)
