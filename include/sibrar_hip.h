@@ -807,6 +807,28 @@ int sbr_p3_walk_dense(const long* indptr, const int* indices, const long* t_indp
 int sbr_p3_score_rows(const long* indptr, const int* indices, const long* rows, long B, const float* W, long ldw, int m, float alpha,
                       float* out, long ldo, void* stream);
 
+/* ---- LightGCN's propagation on 0/1 data (csrc/graph_prop.hip) --------------------------------------------------------------------------
+ * y = A^ x with A^ = D^-1/2 A D^-1/2 the normalised adjacency of the bipartite user-item graph (He et al., SIGIR 2020, equation 7), over
+ * the joint row space [0, n_users + n_items): joint row r < n_users is user r, whose neighbours are the joint rows n_users + i for the
+ * items i of row r of (u_indptr, u_indices), the users x items matrix; joint row r >= n_users is item r - n_users, whose neighbours are
+ * the users of row r - n_users of (i_indptr, i_indices), its transpose (both binary CSR in the forms sbr_p3_walk_dense takes: indices
+ * ascending and unique; n_users, n_items <= 2^24, so every degree converts to fp32 exactly). x, y and sum are contiguous fp32 tables
+ * [n_users + n_items, D] with row stride D (no leading dimension), 1 <= D <= 512. For every row r of [r0, r1) and every d < D:
+ *   deg_r = the indptr difference of r's own side;  s_r = 1.0f / sqrtf((float)deg_r): one correctly rounded square root, then one
+ *     correctly rounded division (no rsqrt), and s_r = +0.0f when deg_r == 0; s_c likewise from the neighbour's side;
+ *   acc starts at +0.0f and takes acc = fmaf(s_c, x[c][d], acc) over the neighbours c of r in ascending CSR order;
+ *   y[r][d] = s_r * acc: one multiplication, not fused with an addition;
+ *   if sum is not NULL: sum[r][d] = (sum[r][d] + y[r][d]) * sum_scale: one addition, then one multiplication, not fused (the running
+ *     layer sum of LightGCN: 1.0f on inner layers, 1 / (L + 1) on the last).
+ * A row without neighbours writes +0.0f to y. Every element has one owner, a lane that takes the whole chain: no atomics, no reduction
+ * across lanes, so the bits do not depend on the run or on the split of the rows into ranges. Only the rows of [r0, r1) of y and sum
+ * are written. Rows are read from other rows, so x must not overlap y or sum (y and sum must not overlap either): refused, like a D
+ * outside [1, 512], a range outside [0, n_users + n_items] and a NULL u_indptr, i_indptr, x or y, before any launch. An empty range
+ * returns at once. A^ is symmetric: the same call on the incoming gradient is the backward pass. Valid in deterministic mode. New
+ * (additive to ABI 4). */
+int sbr_graph_propagate_f32(const long* u_indptr, const int* u_indices, const long* i_indptr, const int* i_indices, int n_users,
+                            int n_items, long r0, long r1, const float* x, float* y, float* sum, float sum_scale, int D, void* stream);
+
 /* ---- implicit-feedback ALS (csrc/als.hip) ------------------------------------------------------------------------------------------
  * One half-sweep of algorithms/mf_algs.py:69-142 (Hu, Koren and Volinsky 2008) recomputes every row of one factor matrix X from the
  * other one, Y [n_y, f] fp32 with leading dimension ldy, 1 <= f <= 128. The confidence of an observed entry is c = alpha * r, of every

@@ -1430,6 +1430,82 @@ def p3_score_rows(csr, rows: Optional[torch.Tensor], W: torch.Tensor, alpha: flo
     return out
 
 
+# ---- LightGCN's propagation (csrc/graph_prop.hip) -------------------------------------------------------------------------------------
+GRAPH_MAX_D = 512
+
+
+def _graph_table(who, name, t, shape):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f'{who}: {name} must be a contiguous float32 {list(shape)} table, got {t.dtype} {tuple(t.shape)} strides {t.stride()}')
+
+
+def graph_propagate(csr, x: torch.Tensor, out=None, sum=None, sum_scale: float = 1.0, rows=None) -> torch.Tensor:
+    """``y = A^ x`` with ``A^ = D^-1/2 A D^-1/2`` the normalised adjacency of the bipartite graph of a binary resident
+    ``features.DeviceCSR`` [n_users, n_items], over the joint row space (users first, then items): ``x`` and the result are contiguous
+    float32 [n_users + n_items, D], D <= 512 — ``sbr_graph_propagate_f32``: one fmaf chain per element in ascending CSR order, the same
+    bits on every run and for every split of the rows. ``sum``: a table of the same shape that becomes ``(sum + y) * sum_scale`` in the
+    same launch (LightGCN's running layer sum). ``rows=(r0, r1)`` computes that range of joint rows only; ``out``: a table to write into
+    (the rows outside the range keep what they hold; those of a new result are zero). ``x`` may not be ``out`` or ``sum``."""
+    if csr.data is not None:
+        raise ValueError('graph_propagate: the normalised adjacency is stated for 0/1 data only (degrees are entry counts); this matrix has values')
+    _need_cuda(csr.indptr, x, out, sum)
+    n_users, n_items = csr.shape
+    n = n_users + n_items
+    if x.dim() != 2:
+        raise ValueError(f'graph_propagate: x must be a table [{n}, D], got shape {tuple(x.shape)}')
+    shape = (n, int(x.shape[1]))
+    _graph_table('graph_propagate', 'x', x, shape)
+    r0, r1, whole = _row_range(rows, n)
+    if out is None:
+        out = (torch.empty if whole else torch.zeros)(shape, device=x.device, dtype=torch.float32)
+    _graph_table('graph_propagate', 'out', out, shape)
+    if sum is not None:
+        _graph_table('graph_propagate', 'sum', sum, shape)
+    t_indptr, t_indices, _ = csr.transposed()
+    call('sbr_graph_propagate_f32', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n_users, n_items, r0, r1, ptr(x), ptr(out),
+         ptr(sum), float(sum_scale), shape[1], stream())
+    return out
+
+
+_GRAPH_WS = ({}, {})              # slot -> device -> the ping-pong tables of LightGCNPropagateFn
+
+
+def _lightgcn_mean(csr, e0: torch.Tensor, n_layers: int) -> torch.Tensor:
+    """``(1 / (L + 1)) sum_{k=0..L} A^^k e0`` for L >= 1: the sum is seeded with ``e0``, layer k reads one scratch table and writes the
+    other, and every launch adds its layer to the sum (the last one also scales it)"""
+    acc = e0.clone()
+    x = e0
+    for k in range(1, n_layers + 1):
+        y = _device_ws(_GRAPH_WS[k & 1], e0.device, e0.numel(), torch.float32)[:e0.numel()].view(e0.shape)
+        graph_propagate(csr, x, out=y, sum=acc, sum_scale=1.0 if k < n_layers else 1.0 / (n_layers + 1))
+        x = y
+    return acc
+
+
+class LightGCNPropagateFn(Function):
+    """LightGCN's layer combination (He et al., SIGIR 2020, equations 8 and 10 with alpha_k = 1 / (L + 1)):
+    ``E = (1 / (L + 1)) sum_{k=0..L} A^^k E0`` for the joint table ``E0`` [n_users + n_items, D] — L launches of
+    ``sbr_graph_propagate_f32``. ``A^`` is symmetric, so the backward pass is the same computation on the incoming gradient. ``L = 0``
+    returns ``E0`` and launches nothing. Fixed order, no atomics: valid in deterministic mode."""
+
+    @staticmethod
+    def forward(ctx, csr, e0, n_layers: int):
+        n_layers = int(n_layers)
+        if n_layers < 0:
+            raise ValueError(f'LightGCNPropagateFn: n_layers={n_layers} is negative')
+        ctx.csr, ctx.n_layers = csr, n_layers
+        if n_layers == 0:
+            return e0.view_as(e0)
+        _need_cuda(e0)
+        return _lightgcn_mean(csr, _f32c(e0), n_layers)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.n_layers == 0:
+            return None, g, None
+        return None, _lightgcn_mean(ctx.csr, _f32c(g), ctx.n_layers), None
+
+
 # ---- implicit-feedback ALS (csrc/als.hip) -------------------------------------------------------------------------------------------
 def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
     """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a

@@ -73,6 +73,9 @@ class FusedOptimizer:
         self.deferred = None         # engine.DeferredTable of a fused step that updates one lookup table row by row
         self.name, self._lr, self._wd = name, float(lr), float(weight_decay)
         self.fp = FlatParameters(module)
+        # a model that keeps tables derived from its parameters (LightGCN's propagated table of eval() mode) names the call that drops
+        # them: the update below writes through raw pointers, which no version counter of a parameter sees
+        self._drop_derived = getattr(module, 'drop_propagated', None)
         self.step_count = 0
         n, dev = self.fp.total, self.fp.flat.device
         self.m = torch.zeros(n, device=dev, dtype=torch.float32)
@@ -121,6 +124,8 @@ class FusedOptimizer:
         ``rows`` (with ``zero_grad``): ids / rows of the deferred table that received gradient -> one launch for everything.
         ``skip`` = (lo, hi): leave that range of the flat buffers alone — a lookup table whose rows the fused step updates
         itself, deferred row by row (engine.DeferredTable). A step without ``skip`` first brings such a table up to date."""
+        if self._drop_derived is not None:
+            self._drop_derived()
         if rows is not None and self.deferred is not None and zero_grad and skip is None:
             # ``rows``: the rows of the deferred lookup table that received gradient in this step — the table is updated row by
             # row inside the same launch that steps every other parameter densely (engine.DeferredTable.step)
