@@ -829,6 +829,36 @@ int sbr_p3_score_rows(const long* indptr, const int* indices, const long* rows, 
 int sbr_graph_propagate_f32(const long* u_indptr, const int* u_indices, const long* i_indptr, const int* i_indices, int n_users,
                             int n_items, long r0, long r1, const float* x, float* y, float* sum, float sum_scale, int D, void* stream);
 
+/* ---- the multinomial log-likelihood of Mult-VAE / Mult-DAE on 0/1 data (csrc/multinomial.hip) ----------------------------------------
+ * The loss of Liang et al. (WWW 2018, equation 2) for a logit matrix [B, n_items] against the users' rows of a users x items binary
+ * CSR matrix (indptr int64, indices int32 ascending and unique within a row and below n_items), with its gradient, in one launch.
+ * rows[b] is the user of logits row b. logits and dlogits are contiguous fp32 with row stride n_items (no leading dimension; row offsets
+ * are (long)b * n_items). For row b with u = rows[b], n = indptr[u + 1] - indptr[u] and z = logits[b]:
+ *   m = max_j z_j,  s = sum_j expf(z_j - m),  lse = m + logf(s);   pos = the sum of z_i over the items i of row u;
+ *   row_loss[b] = (float)n * lse - pos;   row_lse[b] = lse (row_lse may be NULL);
+ *   dlogits[b][j] = grad_scale * ((float)n * expf(z_j - lse) - [j in row u]).
+ * A row with n == 0 writes +0.0f to row_loss[b] and to every element of its gradient row (its row_lse is still lse). The mean over the
+ * batch and its 1 / B (grad_scale) are the caller's. dlogits == NULL: forward only; dlogits == logits: in place, the logit matrix
+ * becomes its own gradient; otherwise a disjoint [B, n_items] matrix, and logits is not written.
+ * Order of the operations. The row is cut into chunks of four consecutive elements; chunk c belongs to thread c % T of the T threads
+ * that own the row (T = 64, a wave, for n_items <= 1024; T = 256, a workgroup, above; up to n_items = 12,288 the workgroup keeps the
+ * row in LDS between its two passes, above it reads the row again), whether the chunk is loaded as one float4 (n_items % 4 == 0 and
+ * 16-byte aligned bases) or as four floats. A thread keeps a pair (m_t, s_t), from (-inf, 0): for each of its chunks in ascending
+ * order, m' = max(m_t, the four), s_t = s_t * e(m_t, m') and then + expf(z - m') for the four in ascending order (e(a, b) = expf(a - b),
+ * and exactly 1 where a == b). Pairs merge as (max, s_a * e(m_a, max) + s_b * e(m_b, max)), not fused: by an xor butterfly over the
+ * lanes of a wave (offsets 1, 2, .. 32), then over the waves in ascending order. pos: thread t adds the row's entries t, t + T, ... in
+ * that order from +0, and the partial sums are added by the same butterfly and wave order. The dense part of the gradient is
+ * grad_scale * ((float)n * expf(z_j - lse)); grad_scale is then subtracted once at each item of the row (a plain read-modify-write by
+ * one owner per element, behind the owner's dense write of the row). None of this depends on B, b, the run or the other rows; no float
+ * atomics; the entry never counts as a nondeterministic launch and is valid in deterministic mode.
+ * Refused before any launch: a NULL indptr, rows, logits or row_loss; n_items < 1; B < 0; dlogits overlapping logits in part; row_loss
+ * or row_lse overlapping a matrix or each other. B == 0 returns at once. A row id outside the matrix cannot be checked without a
+ * synchronisation: rows[b] in [0, users) is the caller's contract (ops.multinomial_nll checks it). Finite logits are the defined
+ * domain; for any logit values, and for indices outside [0, n_items) (which are skipped), nothing outside the operands is read or
+ * written. New (additive to ABI 4). */
+int sbr_multinomial_nll_f32(const long* indptr, const int* indices, const long* rows, long B, int n_items, const float* logits,
+                            float* dlogits, float grad_scale, float* row_loss, float* row_lse, void* stream);
+
 /* ---- implicit-feedback ALS (csrc/als.hip) ------------------------------------------------------------------------------------------
  * One half-sweep of algorithms/mf_algs.py:69-142 (Hu, Koren and Volinsky 2008) recomputes every row of one factor matrix X from the
  * other one, Y [n_y, f] fp32 with leading dimension ldy, 1 <= f <= 128. The confidence of an observed entry is c = alpha * r, of every

@@ -26,6 +26,7 @@ from .ease import EASE                                                          
 from .slim import SLIM                                                                      # noqa: F401
 from .p3alpha import P3alpha                                                                # noqa: F401
 from .lightgcn import LightGCN                                                              # noqa: F401
+from .multvae import MultDAE, MultVAE                                                       # noqa: F401
 from .als import AlternatingLeastSquare                                                     # noqa: F401
 from .svd import SVDAlgorithm                                                               # noqa: F401
 from .rbmf import RBMF                                                                      # noqa: F401
@@ -58,10 +59,11 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
 # .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .slim / .p3alpha / .als / .svd / .rbmf / .pop / .rand -> class
-# (algorithms/algorithms_utils.py); 'lightgcn' is this package's own: the reference has no trained graph model
+# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae' and 'multdae' are this package's own: the reference has no trained graph model and
+# no autoencoder over the interaction row
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
               'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ifknn': ItemFeatureKNN, 'ease': EASE,
               'slim': SLIM, 'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF,
-              'pop': PopularItems, 'rand': RandomItems, 'lightgcn': LightGCN}
+              'pop': PopularItems, 'rand': RandomItems, 'lightgcn': LightGCN, 'multvae': MultVAE, 'multdae': MultDAE}

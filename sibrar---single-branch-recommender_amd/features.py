@@ -216,6 +216,7 @@ class DeviceCSR(nn.Module):
             data = data / torch.sqrt(sq).clamp(min=1e-8)[row_of]
         self.register_buffer('data', None if bool((data == 1).all()) else data, persistent=False)
         self._transposed = None
+        self._t_order = None
         self._grad_ws = None              # [n_rows, C] per-entity gradient rows (ops.SparseLinearActFn, gather form)
 
     def dense_rows(self, ent: torch.Tensor) -> torch.Tensor:
@@ -238,6 +239,34 @@ class DeviceCSR(nn.Module):
             t_indptr[1:] = torch.cumsum(torch.bincount(cols, minlength=n_cols), 0)
             row_of = torch.repeat_interleave(torch.arange(n_rows, device=dev), self.indptr[1:] - self.indptr[:-1])
             order = torch.sort(cols, stable=True).indices
+            self._t_order = order             # entry k of the transposed matrix is entry order[k] of this one (value_view)
             self._transposed = (t_indptr, row_of[order].to(torch.int32).contiguous(),
                                 None if self.data is None else self.data[order].contiguous())
         return self._transposed
+
+    def value_view(self) -> 'DeviceCSR':
+        """A matrix of the same structure whose values can be replaced (``replace_values``): it shares ``indptr``, ``indices`` and the
+        transposed structure with this one, on this one's device, and starts with this one's values (ones for a 0/1 matrix). Mult-VAE's
+        input dropout acts on the stored values of the rows; the zeros of a row stay zeros."""
+        t_indptr, t_indices, _ = self.transposed()
+        v = DeviceCSR.__new__(DeviceCSR)
+        nn.Module.__init__(v)
+        v.shape = self.shape
+        v.register_buffer('indptr', self.indptr, persistent=False)
+        v.register_buffer('indices', self.indices, persistent=False)
+        v.register_buffer('data', None, persistent=False)
+        v._grad_ws = None
+        v._t_order = self._t_order
+        v._transposed = (t_indptr, t_indices, None)
+        return v.replace_values(self.data if self.data is not None else torch.ones(self.indices.numel(), device=self.indices.device))
+
+    def replace_values(self, data: torch.Tensor) -> 'DeviceCSR':
+        """(a ``value_view`` only) take ``data``, float32 [nnz] on the matrix's device, as the stored values, in CSR order"""
+        if getattr(self, '_t_order', None) is None or self._transposed is None:
+            raise RuntimeError('DeviceCSR.replace_values: only a value_view() has replaceable values')
+        if data.dtype != torch.float32 or tuple(data.shape) != (self.indices.numel(),) or data.device != self.indices.device:
+            raise ValueError(f'DeviceCSR.replace_values: need float32 [{self.indices.numel()}] on {self.indices.device}, got {data.dtype} '
+                             f'{tuple(data.shape)} on {data.device}')
+        self.data = data
+        self._transposed = (self._transposed[0], self._transposed[1], data[self._t_order])
+        return self

@@ -1506,6 +1506,72 @@ class LightGCNPropagateFn(Function):
         return None, _lightgcn_mean(ctx.csr, _f32c(g), ctx.n_layers), None
 
 
+# ---- the multinomial log-likelihood of Mult-VAE / Mult-DAE (csrc/multinomial.hip) ------------------------------------------------------
+def _multinomial_nll(who, csr, rows, logits, grad_scale, inplace):
+    """the launch behind ``multinomial_nll`` and ``MultinomialNLLFn``; nothing here synchronises"""
+    if csr.data is not None:
+        raise ValueError(f'{who}: the multinomial likelihood is stated for 0/1 data only (the targets are the rows\' entries); this matrix has values')
+    _need_cuda(csr.indptr, rows, logits)
+    n_users, n_items = csr.shape
+    if rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_contiguous():
+        raise ValueError(f'{who}: rows must be a contiguous int64 vector, got {rows.dtype} {tuple(rows.shape)}')
+    B = rows.numel()
+    if logits.dtype != torch.float32 or tuple(logits.shape) != (B, n_items) or not logits.is_contiguous():
+        raise ValueError(f'{who}: logits must be a contiguous float32 [{B}, {n_items}] matrix, got {logits.dtype} {tuple(logits.shape)} '
+                         f'strides {logits.stride()}')
+    if inplace and grad_scale is None:
+        raise ValueError(f'{who}: inplace=True writes the gradient over the logits and needs a grad_scale')
+    row_loss = torch.empty(B, device=logits.device, dtype=torch.float32)
+    row_lse = torch.empty(B, device=logits.device, dtype=torch.float32)
+    dlogits = None if grad_scale is None else (logits if inplace else torch.empty_like(logits))
+    call('sbr_multinomial_nll_f32', ptr(csr.indptr), ptr(csr.indices), ptr(rows), B, n_items, ptr(logits), ptr(dlogits),
+         0.0 if grad_scale is None else float(grad_scale), ptr(row_loss), ptr(row_lse), stream())
+    return row_loss, row_lse, dlogits
+
+
+def multinomial_nll(csr, rows: torch.Tensor, logits: torch.Tensor, grad_scale: Optional[float] = None, inplace: bool = False):
+    """The multinomial log-likelihood of Mult-VAE / Mult-DAE (Liang et al., WWW 2018) of the logit rows ``logits`` [B, n_items] against
+    the rows ``rows`` (int64 [B]) of a binary resident ``features.DeviceCSR`` [n_users, n_items] — ``sbr_multinomial_nll_f32``, one
+    launch: ``row_loss[b] = n_b * logsumexp(logits[b]) - sum of logits[b] at the user's items`` and ``row_lse[b]`` the logsumexp. With a
+    ``grad_scale`` the gradient ``grad_scale * (n_b * softmax(logits[b]) - the user's 0/1 row)`` comes back as a third result: a new
+    matrix, or ``logits`` itself, overwritten, with ``inplace=True``. A user without items gives a zero loss and a zero gradient row.
+    Fixed order (it depends on n_items alone), no atomics: valid in deterministic mode. The row ids are checked here (one
+    synchronisation); ``MultinomialNLLFn`` does not check them."""
+    if rows.numel() and not (0 <= int(rows.min()) and int(rows.max()) < csr.shape[0]):
+        raise ValueError(f'multinomial_nll: row ids outside [0, {csr.shape[0]})')
+    row_loss, row_lse, dlogits = _multinomial_nll('multinomial_nll', csr, rows, logits, grad_scale, inplace)
+    return (row_loss, row_lse) if grad_scale is None else (row_loss, row_lse, dlogits)
+
+
+class MultinomialNLLFn(Function):
+    """``mean_b row_loss[b]`` of ``multinomial_nll`` as a scalar on the autograd tape. One launch of ``sbr_multinomial_nll_f32`` in the
+    forward pass computes the loss and, when the logits need a gradient, the gradient ``(1 / B) (n_b softmax - targets)`` with it; the
+    backward pass launches nothing. ``inplace=True`` is the caller's promise that nothing reads the logits after this call, the backward
+    pass of their producer included (``LinearActFn`` without an activation does not): the gradient is then written over them
+    (``dlogits == logits``). Otherwise, and whenever the logits need no gradient, the logits are left as they are and the gradient, if
+    any, is a new matrix. ``unit_upstream=True`` is the promise that the result enters the objective with weight 1: the backward pass
+    then hands the stored gradient on as it is; otherwise it is multiplied by the upstream gradient (no synchronisation either way).
+    The row ids must lie inside the matrix; they are not checked here (that would synchronise)."""
+
+    @staticmethod
+    def forward(ctx, csr, rows, logits, inplace: bool = False, unit_upstream: bool = False):
+        need = ctx.needs_input_grad[2]
+        B = rows.numel()
+        if B == 0:
+            raise ValueError('MultinomialNLLFn: an empty batch has no mean')
+        row_loss, _, dlogits = _multinomial_nll('MultinomialNLLFn', csr, rows, logits.detach() if logits.is_contiguous() else _f32c(logits.detach()),
+                                                1.0 / B if need else None, bool(inplace) and need and logits.is_contiguous())
+        ctx.dlogits, ctx.unit_upstream = dlogits, bool(unit_upstream)
+        return row_loss.sum() / B
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, ctx.dlogits = ctx.dlogits, None
+        if dl is not None and not ctx.unit_upstream:
+            dl = dl.mul_(g)
+        return None, None, dl, None, None
+
+
 # ---- implicit-feedback ALS (csrc/als.hip) -------------------------------------------------------------------------------------------
 def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
     """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a
