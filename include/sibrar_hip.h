@@ -859,6 +859,52 @@ int sbr_graph_propagate_f32(const long* u_indptr, const int* u_indices, const lo
 int sbr_multinomial_nll_f32(const long* indptr, const int* indices, const long* rows, long B, int n_items, const float* logits,
                             float* dlogits, float grad_scale, float* row_loss, float* row_lse, void* stream);
 
+/* ---- DirectAU's loss terms: uniformity and alignment (csrc/directau.hip) --------------------------------------------------------------
+ * Uniformity (Wang and Isola, ICML 2020; Wang et al., KDD 2022) of the rows of a contiguous fp32 x [n, D] with row stride D (no leading
+ * dimension), 2 <= n, 1 <= D <= 256, t > 0. The rows need not be normalised. With
+ *   sq_i = |x_i|^2,  g_ij = x_i . x_j,  d_ij^2 = max(0, (sq_i + sq_j) - 2 g_ij),  w_ij = expf(-(t * d_ij^2)):
+ *   S = sum_{i<j} w_ij (fp32),   loss = log(S * 2 / (n (n - 1))) (fp32).
+ * A pair (i, i) is never counted; two equal rows are an ordinary pair (its w is the exponential of the rounding error of d^2, at most 1).
+ * Order of the operations. Rows are cut into tiles of 64; a workgroup of 256 threads owns a row tile and takes the column tiles from its
+ * own upwards in ascending order. sq_i: 32 fmaf chains from +0, chain s over d = s, s + 32, .., added by an xor butterfly with offsets
+ * 16, 8, 4, 2, 1: the same bits wherever the row is used. g_ij: one fmaf chain from +0 over d = 0 .. D - 1. A thread holds the 4 x 4
+ * pairs (rows 4 rg .. + 3 of the row tile, columns 4 cg .. + 3 of the column tile, thread = 16 rg + cg), excluded pairs as +0, adds
+ * them as ((w0 + w1) + (w2 + w3)) per row and ((r0 + r1) + (r2 + r3)) over its rows in fp32, and adds that to a double that it keeps
+ * over the column tiles. The 256 doubles of a row tile are added by an xor butterfly (offsets 32 .. 1) within a wave and as
+ * ((w0 + w1) + (w2 + w3)) over the waves: the row tile's partial, ws[tile]. A second launch adds the partials in tile order in double
+ * and rounds once: S. loss is computed from that fp32 S in double and rounded once. ws: sbr_uniformity_workspace(n, D) bytes (one
+ * double per row tile), written before it is read: it needs no zeroing; calls that share it must not overlap in time.
+ * max_wg: the most workgroups to launch, 0 for the default (one per row tile up to 1,024); further row tiles are taken by a
+ * grid-stride loop. The bits of S and loss depend on (x, n, D, t) alone: not on the run, max_wg, or which workgroup took which tile.
+ * Defined domain: t * max d^2 < 80 (no term underflows; unit rows with t <= 16 are inside it).
+ * Refused before any launch: n < 2, D outside [1, 256], t <= 0 or not finite, a negative max_wg, a NULL x, S, loss or ws, ws_bytes below
+ * sbr_uniformity_workspace(n, D). No float atomics; never counts as a nondeterministic launch; valid in deterministic mode. New
+ * (additive to ABI 4). */
+long sbr_uniformity_workspace(long n, int D);
+int sbr_uniformity_fwd(const float* x, long n, int D, float t, float* S, float* loss, void* ws, long ws_bytes, int max_wg, void* stream);
+/* The gradient of that loss, from x, the forward pass's S and the upstream gradient grad, both read from device memory (fp32 scalars: no
+ * host read-back), with w recomputed as above:
+ *   coef = grad * (-2 * t / S);   dx[i][d] = coef * (x[i][d] * rs_i - acc_i[d]),   rs_i = sum_{j != i} w_ij,  acc_i = sum_{j != i} w_ij x_j.
+ * Order. The workgroup that owns a row tile takes EVERY column tile in ascending order. rs_i: per column tile the thread's four weights
+ * of the row as (w0 + w1) + (w2 + w3), the row's 16 threads by an xor butterfly (offsets 1, 2, 4, 8), then added to the running fp32 sum.
+ * acc_i[d]: one fmaf chain from +0 over j = 0 .. n - 1 (w_ii enters as +0), in registers for the whole pass (a thread holds 4 x 4 per 64
+ * columns of D: hence D <= 256). The last line is two multiplications and a subtraction, not fused. Every dx element has one owner; the
+ * bits depend on (x, n, D, t, S, grad) alone. dx is contiguous [n, D] and must not overlap x. Refused before any launch: what
+ * sbr_uniformity_fwd refuses of n, D, t and max_wg, a NULL x, S, grad or dx, dx overlapping x. No workspace. Valid in deterministic
+ * mode. New (additive to ABI 4). */
+int sbr_uniformity_bwd(const float* x, long n, int D, float t, const float* S, const float* grad, float* dx, int max_wg, void* stream);
+/* Alignment as a row loss on logits [B, N] (contiguous fp32) and labels (float64 0 / 1), with the conventions of sbr_rec_loss_fwd / _bwd:
+ *   loss_out = scale * sum over the elements with label == 1 of (2 - 2 z)   (float64);   dlogits = -2 * scale * g there, +0 elsewhere.
+ * On cosine logits with one positive per row and scale = 1 / B this is mean_b |u^_b - i^_b|^2. Negative columns are ignored. Order: one
+ * thread per row adds its positives in column order in double; a block of 256 rows adds its threads by an xor butterfly (offsets 32 .. 1)
+ * and its waves in order, times scale; the block partials (library scratch) are added in a fixed pattern by one workgroup. No double
+ * atomics in either mode; never counts as a nondeterministic launch. g: the upstream gradient in device memory, float64 when
+ * grad_out_is_double, else fp32; the gradient is rounded to fp32 once. Refused: a NULL operand, B < 0, N < 1. B == 0: loss_out = 0,
+ * nothing else is written. New (additive to ABI 4). */
+int sbr_align_fwd(const float* logits, const double* labels, long B, int N, double scale, double* loss_out, void* stream);
+int sbr_align_bwd(const double* labels, long B, int N, double scale, const void* grad_out, int grad_out_is_double, float* dlogits,
+                  void* stream);
+
 /* ---- implicit-feedback ALS (csrc/als.hip) ------------------------------------------------------------------------------------------
  * One half-sweep of algorithms/mf_algs.py:69-142 (Hu, Koren and Volinsky 2008) recomputes every row of one factor matrix X from the
  * other one, Y [n_y, f] fp32 with leading dimension ldy, 1 <= f <= 128. The confidence of an observed entry is c = alpha * r, of every

@@ -591,6 +591,10 @@ class FusedTrainStep:
                  deterministic: Optional[bool] = None):
         if not isinstance(net.item_embedding_module, SingleBranchNetEntity):
             raise NotImplementedError('FusedTrainStep needs a SingleBranchNetEntity item side')
+        kinds = {RecBinaryCrossEntropy: 0, RecBayesianPersonalizedRankingLoss: 1, RecSampledSoftmaxLoss: 2}
+        if type(rec_loss) not in kinds:              # a loss without a fused kernel (RecAlignmentLoss): Trainer takes the autograd step
+            raise NotImplementedError(f'FusedTrainStep has no fused kernel for {type(rec_loss).__name__}')
+        self.kind = kinds[type(rec_loss)]
         # ``deterministic`` (default None: env ``SBR_DETERMINISTIC=1`` turns it on, else the current process-wide setting stays):
         # True / False switch the library's deterministic mode (``ops.set_deterministic``). The mode is process-wide — a captured
         # graph and the kernels behind an entry point cannot differ per object — and every step follows the CURRENT setting: with it
@@ -604,7 +608,6 @@ class FusedTrainStep:
         self.user = (_EntityRun if net.is_user_sb_module else _PlainRun)(net.user_embedding_module, self.arena)
         self.item = _EntityRun(net.item_embedding_module, self.arena)
         self.item.fuse_tail = True   # the trailing BatchNorm runs inside the scorer whenever a step draws one modality per slot
-        self.kind = {RecBinaryCrossEntropy: 0, RecBayesianPersonalizedRankingLoss: 1, RecSampledSoftmaxLoss: 2}[type(rec_loss)]
         self.one64 = torch.ones((), device=dev, dtype=torch.float64)
         self.one32 = torch.ones((), device=dev, dtype=torch.float32)
         self.n_steps = 0

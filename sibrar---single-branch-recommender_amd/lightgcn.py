@@ -41,10 +41,14 @@ class LightGCN(SGDBasedRecommenderAlgorithm):
         self.user_embeddings = nn.Embedding(n_users, embedding_dim)
         self.item_embeddings = nn.Embedding(n_items, embedding_dim)
         self.apply(general_weight_init)
-        self._graph = DeviceCSR(train_matrix)                     # non-persistent buffers: moves with .to(), stays out of the state_dict
-        if tuple(self._graph.shape) != (n_users, n_items):
+        if train_matrix is None and self.n_layers > 0:
+            raise ValueError(f'LightGCN: n_layers={n_layers} needs the training matrix')
+        # non-persistent buffers: moves with .to(), stays out of the state_dict. Without layers there is nothing to propagate over, and
+        # a model built on this one (DirectAU) may then come without a matrix
+        self._graph = None if train_matrix is None else DeviceCSR(train_matrix)
+        if self._graph is not None and tuple(self._graph.shape) != (n_users, n_items):
             raise ValueError(f'LightGCN: the training matrix is {tuple(self._graph.shape)}, not [{n_users}, {n_items}]')
-        if self._graph.data is not None:
+        if self._graph is not None and self._graph.data is not None:
             raise ValueError('LightGCN: the normalised adjacency is stated for 0/1 interaction data; this matrix has values')
         self._propagated = None                                   # (key, user table, item table) of eval() mode
         self.name = 'LightGCN'

@@ -66,10 +66,26 @@ class RecSampledSoftmaxLoss(RecommenderSystemLoss):
         return ops.RecLossFn.apply(logits, labels, ops.LOSS_CODES['sampled_softmax'], scale, shift)
 
 
+class RecAlignmentLoss(RecommenderSystemLoss):
+    """DirectAU's alignment term (Wang et al., KDD 2022) as a recommendation loss: ``sum over the positives of (2 - 2 z)``, divided by the
+    number of positives for ``'mean'``. On the cosine logits that ``DirectAU`` returns in training mode it is ``mean |u^ - i^|^2``. The
+    negative columns are ignored, so ``n_negative_samples`` can be anything the loader accepts. Not part of the reference."""
+
+    def compute_loss(self, logits, labels):
+        total = ops.AlignLossFn.apply(logits, labels, 1.0)
+        if self.aggregator != 'mean':
+            return total
+        # scale = 1 / (number of positives), applied on the device: the count is not read back, so a step does not synchronise, and the
+        # kernel's backward pass receives 1 / count as its upstream gradient
+        n_pos = (labels.to(total.device) == 1).sum().clamp_(min=1)
+        return total / n_pos
+
+
 class RecommenderSystemLossesEnum(Enum):
     bce = RecBinaryCrossEntropy
     bpr = RecBayesianPersonalizedRankingLoss
     sampled_softmax = RecSampledSoftmaxLoss
+    align = RecAlignmentLoss
 
 
 class InfoNCE(nn.Module):

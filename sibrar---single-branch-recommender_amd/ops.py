@@ -1572,6 +1572,90 @@ class MultinomialNLLFn(Function):
         return None, None, dl, None, None
 
 
+# ---- DirectAU's loss terms (csrc/directau.hip) -----------------------------------------------------------------------------------------
+UNIFORMITY_MAX_D = 256            # the backward pass keeps a row tile's [64, D] accumulator in registers
+
+
+def _uniformity_x(who, x, t):
+    """-> (x as contiguous float32, n, D, t) of the operand of the uniformity entries; the shape and range refusals are the library's"""
+    _need_cuda(x)
+    if x.dim() != 2:
+        raise ValueError(f'{who}: x must be a matrix [n, D], got shape {tuple(x.shape)}')
+    return _f32c(x), int(x.shape[0]), int(x.shape[1]), float(t)
+
+
+def _uniformity_fwd(who, x, t, max_wg):
+    x, n, D, t = _uniformity_x(who, x, t)
+    out = torch.empty(2, device=x.device, dtype=torch.float32)                # (S, loss)
+    ws, ws_bytes = _entry_ws(x.device, 'sbr_uniformity', n, D, dtype=torch.float64)
+    call('sbr_uniformity_fwd', ptr(x), n, D, t, ptr(out), ptr(out) + 4, ws, ws_bytes, int(max_wg), stream())
+    return x, out[1], out[0]
+
+
+def _uniformity_bwd(x, t, S, g, max_wg):
+    dx = torch.empty_like(x)
+    g = g.reshape(()).to(torch.float32).contiguous()
+    call('sbr_uniformity_bwd', ptr(x), x.shape[0], x.shape[1], float(t), ptr(S), ptr(g), ptr(dx), int(max_wg), stream())
+    return dx
+
+
+def uniformity(x: torch.Tensor, t: float = 2.0, max_wg: int = 0):
+    """``(loss, S)`` of the uniformity term of DirectAU (Wang et al., KDD 2022) over the rows of ``x`` [n, D], n >= 2, D <= 256, t > 0:
+    ``S = sum_{i<j} exp(-t |x_i - x_j|^2)`` and ``loss = log(S * 2 / (n (n - 1)))``, two float32 scalars on the device —
+    ``sbr_uniformity_fwd``: the pair weights are formed on chip from 64 x 64 Gram tiles and nothing of size n x n is written. torch's
+    ``pdist(x).pow(2).mul(-t).exp().mean().log()``. Equal rows are ordinary pairs; the rows need not be normalised, but ``t * max d^2``
+    must stay below 80. ``max_wg``: the most workgroups (0: the default); the bits do not depend on it, on the run or on the mode."""
+    _, loss, S = _uniformity_fwd('uniformity', x, t, max_wg)
+    return loss, S
+
+
+class UniformityFn(Function):
+    """``ops.uniformity``'s loss on the autograd tape. The forward pass saves ``x`` and ``S``; the backward pass recomputes the pair
+    weights (``sbr_uniformity_bwd``) and reads the upstream gradient from device memory: no synchronisation. Fixed order, no atomics:
+    valid in deterministic mode."""
+
+    @staticmethod
+    def forward(ctx, x, t: float = 2.0, max_wg: int = 0):
+        xc, loss, S = _uniformity_fwd('UniformityFn', x.detach(), t, max_wg)
+        ctx.t, ctx.max_wg = float(t), int(max_wg)
+        ctx.save_for_backward(xc, S)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        x, S = ctx.saved_tensors
+        return _uniformity_bwd(x, ctx.t, S, g, ctx.max_wg), None, None
+
+
+class AlignLossFn(Function):
+    """``scale * sum over the positives (label == 1) of (2 - 2 z)`` for logits [B, N] and float64 labels, a float64 scalar —
+    ``sbr_align_fwd`` / ``sbr_align_bwd``. On cosine logits with ``scale = 1 / B`` it is DirectAU's alignment term
+    ``mean_b |u^_b - i^_b|^2``. Negative columns get a zero gradient. Block partials are added in block order in either mode."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, scale: float):
+        _need_cuda(logits)
+        logits = _f32c(logits)
+        B, N = logits.shape
+        lab = labels.to(device=logits.device, dtype=torch.float64).contiguous()
+        if tuple(lab.shape) != (B, N):
+            raise ValueError(f'AlignLossFn: labels {tuple(lab.shape)} do not match the logits [{B}, {N}]')
+        out = torch.empty((), device=logits.device, dtype=torch.float64)
+        call('sbr_align_fwd', ptr(logits), ptr(lab), B, N, float(scale), ptr(out), stream())
+        ctx.scale = float(scale)
+        ctx.save_for_backward(lab)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lab, = ctx.saved_tensors
+        B, N = lab.shape
+        g = g.contiguous()
+        d = torch.empty((B, N), device=lab.device, dtype=torch.float32)
+        call('sbr_align_bwd', ptr(lab), B, N, ctx.scale, ptr(g), 1 if g.dtype == torch.float64 else 0, ptr(d), stream())
+        return d, None, None
+
+
 # ---- implicit-feedback ALS (csrc/als.hip) -------------------------------------------------------------------------------------------
 def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
     """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a
