@@ -775,7 +775,7 @@ int sbr_shared_rank_topk(const int* order, const float* score, int n_items, cons
 /* RandomItems (algorithms/naive_algs.py:11-32: `torch.rand(i_idxs.shape)` from the CPU's global generator, so a list there depends on
  * the batch size, the order of the batches and whatever drew before) as a pure function: out[b, j] = U(seed, u_idx[b], j) for j in
  * [0, n_items), out fp32 with leading dimension ld >= n_items, u_idx int64 [Bu] (NULL = identity). The generator is Philox4x32-10
- * (Salmon et al., SC 2011; written out in the kernel file, no generator library): key = (low, high) 32-bit halves of `seed`, counter =
+ * (Salmon et al., SC 2011; written out in csrc/philox.h, no generator library): key = (low, high) 32-bit halves of `seed`, counter =
  * (low half of the user id, high half of the user id, j / 4, 0), and word j % 4 of the output block x maps to (x >> 8) * 2^-24, an
  * exact fp32 in [0, 1). A value depends on nothing but (seed, user id, j): not on the chunk, the launch geometry, ld or the row's
  * place in the batch. Bu == 0 or n_items == 0 returns without a launch. One writer per element, no atomics: valid in deterministic
@@ -828,6 +828,30 @@ int sbr_p3_score_rows(const long* indptr, const int* indices, const long* rows, 
  * (additive to ABI 4). */
 int sbr_graph_propagate_f32(const long* u_indptr, const int* u_indices, const long* i_indptr, const int* i_indices, int n_users,
                             int n_items, long r0, long r1, const float* x, float* y, float* sum, float sum_scale, int D, void* stream);
+/* The propagation of SimGCL / XSimGCL (Yu et al., SIGIR 2022 and TKDE 2023): the same y, perturbed by a random direction of length eps
+ * in the orthant of y before it is stored and summed. Operands, tables (contiguous, row stride D, no leading dimension, 1 <= D <= 512)
+ * and row range as for sbr_graph_propagate_f32. For every row r of [r0, r1) and every d < D:
+ *   p[r][d] = y[r][d] of sbr_graph_propagate_f32, bit for bit: the same scales, the same fmaf chain in ascending CSR order, the same
+ *     final multiplication;
+ *   u[r][d] = Philox4x32-10 as in sbr_uniform_rows_f32 (one block function, csrc/philox.h): key = (low, high) 32-bit halves of `seed`,
+ *     counter = (r, d / 4, low half of stream_id, high half of stream_id), word d % 4 of the output block x mapped to (x >> 8) * 2^-24;
+ *   n_r = fmaxf(sqrtf(q_r), 1e-12f), with q_r the sum of u[r][d]^2 over d < D in this order, a function of D alone: take the row in
+ *     blocks of four columns b = 0 .. ceil(D / 4) - 1 and G4 = the smallest power of two >= ceil(D / 4), 64 at the most. Partial sum
+ *     l (0 <= l < G4) starts at +0.0f and takes t = t + u * u (one multiplication, then one addition, not fused) over the columns of
+ *     its blocks l, l + G4, ... in ascending column order; columns past D and partial sums without a block contribute +0.0f. The G4
+ *     partial sums then combine by an xor butterfly from the widest offset down: for o = G4 / 2, G4 / 4, ..., 1 every t_l becomes
+ *     t_l + t_(l xor o) (all of a step at once); t_0 is q_r. One correctly rounded square root;
+ *   y[r][d] = p + sgn(p) * ((eps * u) / n_r) where p is not a zero: one multiplication, one correctly rounded division, the sign, one
+ *     addition, nothing fused; sgn is torch.sign's, so where p is +-0.0f, y = p: a row without neighbours stays +0.0f and gets no noise;
+ *   if sum is not NULL: sum[r][d] = (sum[r][d] + y[r][d]) * sum_scale on the perturbed y, as above.
+ * eps == 0 writes exactly p (and the sum of sbr_graph_propagate_f32). The noise is a pure function of (seed, stream_id, r, d): it does
+ * not depend on r0, r1, the launch geometry, the alignment of the tables or the run. An element has one owner and the butterfly runs
+ * inside the owner's lane group: no atomics, valid in deterministic mode. Refused before any launch: what sbr_graph_propagate_f32
+ * refuses, and an eps that is negative or not finite. The derivative of y with respect to x is A^ (the noise is a constant, sgn has
+ * derivative zero): the backward pass is sbr_graph_propagate_f32 on the incoming gradient. New (additive to ABI 4). */
+int sbr_graph_propagate_noise_f32(const long* u_indptr, const int* u_indices, const long* i_indptr, const int* i_indices, int n_users,
+                                  int n_items, long r0, long r1, const float* x, float* y, float* sum, float sum_scale, int D, float eps,
+                                  unsigned long seed, unsigned long stream_id, void* stream);
 
 /* ---- the multinomial log-likelihood of Mult-VAE / Mult-DAE on 0/1 data (csrc/multinomial.hip) ----------------------------------------
  * The loss of Liang et al. (WWW 2018, equation 2) for a logit matrix [B, n_items] against the users' rows of a users x items binary

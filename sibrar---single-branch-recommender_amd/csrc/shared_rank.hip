@@ -4,6 +4,7 @@
 //   sbr_uniform_rows_f32   RandomItems: U(seed, user id, item position) by a counter-based generator, a pure function of the three
 // No LDS, no atomics, one writer per output element: the same bits on every run, valid in deterministic mode.
 #include "common.h"
+#include "philox.h"
 
 // One wave per user walks `order` 64 ranks at a time. Lane l of a step holds rank r + l and keeps it when the item is not in the user's
 // exclusion row (a binary search in the CSR row); the ballot of the kept lanes numbers them in rank order, so the first k kept items
@@ -62,27 +63,7 @@ extern "C" int sbr_shared_rank_topk(const int* order, const float* score, int n_
   return SBR_OK;
 }
 
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC 2011): ten rounds of two 32 x 32 -> 64
-// bit products over a 128-bit counter, the 64-bit key bumped by the Weyl constants between the rounds.
-#define PHILOX_M0 0xD2511F53u
-#define PHILOX_M1 0xCD9E8D57u
-#define PHILOX_W0 0x9E3779B9u
-#define PHILOX_W1 0xBB67AE85u
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned int k0, unsigned int k1) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const unsigned long long m0 = (unsigned long long)PHILOX_M0 * c.x, m1 = (unsigned long long)PHILOX_M1 * c.z;
-    c = make_uint4((unsigned int)(m1 >> 32) ^ c.y ^ k0, (unsigned int)m1, (unsigned int)(m0 >> 32) ^ c.w ^ k1, (unsigned int)m0);
-    k0 += PHILOX_W0;
-    k1 += PHILOX_W1;
-  }
-  return c;
-}
-
-// the top 24 bits of a word, times 2^-24: every value is exact in fp32 and lies in [0, 1)
-__device__ __forceinline__ float philox_unit(unsigned int x) { return (float)(x >> 8) * 5.9604644775390625e-08f; }
-
+// The generator (Philox4x32-10 and the [0, 1) mapping) is philox.h's.
 #define UNIFORM_MAX_GRID 65536L         // workgroups of a launch: 2^24 threads keep every CU busy, a larger output is walked in grid strides
 
 // One thread per (row, block of four columns): the block's counter is (user id low, user id high, j / 4, 0), so an element's value

@@ -1439,6 +1439,33 @@ def _graph_table(who, name, t, shape):
         raise ValueError(f'{who}: {name} must be a contiguous float32 {list(shape)} table, got {t.dtype} {tuple(t.shape)} strides {t.stride()}')
 
 
+def _graph_propagate(who, csr, x, out, sum, sum_scale, rows, noise=None):
+    """the launch behind ``graph_propagate`` and ``graph_propagate_noise`` (``noise``: (eps, seed, stream_id))"""
+    if csr.data is not None:
+        raise ValueError(f'{who}: the normalised adjacency is stated for 0/1 data only (degrees are entry counts); this matrix has values')
+    _need_cuda(csr.indptr, x, out, sum)
+    n_users, n_items = csr.shape
+    n = n_users + n_items
+    if x.dim() != 2:
+        raise ValueError(f'{who}: x must be a table [{n}, D], got shape {tuple(x.shape)}')
+    shape = (n, int(x.shape[1]))
+    _graph_table(who, 'x', x, shape)
+    r0, r1, whole = _row_range(rows, n)
+    if out is None:
+        out = (torch.empty if whole else torch.zeros)(shape, device=x.device, dtype=torch.float32)
+    _graph_table(who, 'out', out, shape)
+    if sum is not None:
+        _graph_table(who, 'sum', sum, shape)
+    t_indptr, t_indices, _ = csr.transposed()
+    args = (ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n_users, n_items, r0, r1, ptr(x), ptr(out), ptr(sum),
+            float(sum_scale), shape[1])
+    if noise is None:
+        call('sbr_graph_propagate_f32', *args, stream())
+    else:
+        call('sbr_graph_propagate_noise_f32', *args, *noise, stream())
+    return out
+
+
 def graph_propagate(csr, x: torch.Tensor, out=None, sum=None, sum_scale: float = 1.0, rows=None) -> torch.Tensor:
     """``y = A^ x`` with ``A^ = D^-1/2 A D^-1/2`` the normalised adjacency of the bipartite graph of a binary resident
     ``features.DeviceCSR`` [n_users, n_items], over the joint row space (users first, then items): ``x`` and the result are contiguous
@@ -1446,25 +1473,21 @@ def graph_propagate(csr, x: torch.Tensor, out=None, sum=None, sum_scale: float =
     bits on every run and for every split of the rows. ``sum``: a table of the same shape that becomes ``(sum + y) * sum_scale`` in the
     same launch (LightGCN's running layer sum). ``rows=(r0, r1)`` computes that range of joint rows only; ``out``: a table to write into
     (the rows outside the range keep what they hold; those of a new result are zero). ``x`` may not be ``out`` or ``sum``."""
-    if csr.data is not None:
-        raise ValueError('graph_propagate: the normalised adjacency is stated for 0/1 data only (degrees are entry counts); this matrix has values')
-    _need_cuda(csr.indptr, x, out, sum)
-    n_users, n_items = csr.shape
-    n = n_users + n_items
-    if x.dim() != 2:
-        raise ValueError(f'graph_propagate: x must be a table [{n}, D], got shape {tuple(x.shape)}')
-    shape = (n, int(x.shape[1]))
-    _graph_table('graph_propagate', 'x', x, shape)
-    r0, r1, whole = _row_range(rows, n)
-    if out is None:
-        out = (torch.empty if whole else torch.zeros)(shape, device=x.device, dtype=torch.float32)
-    _graph_table('graph_propagate', 'out', out, shape)
-    if sum is not None:
-        _graph_table('graph_propagate', 'sum', sum, shape)
-    t_indptr, t_indices, _ = csr.transposed()
-    call('sbr_graph_propagate_f32', ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n_users, n_items, r0, r1, ptr(x), ptr(out),
-         ptr(sum), float(sum_scale), shape[1], stream())
-    return out
+    return _graph_propagate('graph_propagate', csr, x, out, sum, sum_scale, rows)
+
+
+def graph_propagate_noise(csr, x: torch.Tensor, eps: float, seed: int, stream_id: int, out=None, sum=None, sum_scale: float = 1.0,
+                          rows=None) -> torch.Tensor:
+    """``graph_propagate`` with the perturbation of SimGCL / XSimGCL applied in the same launch (``sbr_graph_propagate_noise_f32``):
+    ``y = p + sign(p) * eps * u / |u_row|`` with ``p = A^ x`` and ``u = U(seed, stream_id, row, column)`` in [0, 1) from Philox4x32-10,
+    generated in registers — a pure function of its four arguments, so the same bits on every run and for every split of the rows.
+    ``sum`` takes the perturbed ``y``. ``eps = 0`` is ``graph_propagate`` bit for bit. ``seed`` and ``stream_id`` are integers in
+    [0, 2^64); the other arguments are ``graph_propagate``'s."""
+    who = 'graph_propagate_noise'
+    for name, v in (('seed', seed), ('stream_id', stream_id)):
+        if int(v) != v or not 0 <= v < 1 << 64:
+            raise ValueError(f'{who}: {name}={v!r} must be an integer in [0, 2^64)')
+    return _graph_propagate(who, csr, x, out, sum, sum_scale, rows, noise=(float(eps), int(seed), int(stream_id)))
 
 
 _GRAPH_WS = ({}, {})              # slot -> device -> the ping-pong tables of LightGCNPropagateFn
@@ -1504,6 +1527,81 @@ class LightGCNPropagateFn(Function):
         if ctx.n_layers == 0:
             return None, g, None
         return None, _lightgcn_mean(ctx.csr, _f32c(g), ctx.n_layers), None
+
+
+GRAPH_NOISE_MAX_LAYERS, GRAPH_NOISE_MAX_VIEWS = 64, 4             # stream_id = step * 256 + view * 64 + layer
+
+
+def noise_stream_id(step: int, view: int, layer: int) -> int:
+    """the ``stream_id`` from which layer ``layer`` of view ``view`` of training step ``step`` draws its noise"""
+    if not 0 <= layer < GRAPH_NOISE_MAX_LAYERS or not 0 <= view < GRAPH_NOISE_MAX_VIEWS or not 0 <= step < 1 << 56:
+        raise ValueError(f'noise_stream_id: layer={layer} outside [0, {GRAPH_NOISE_MAX_LAYERS}), view={view} outside '
+                         f'[0, {GRAPH_NOISE_MAX_VIEWS}) or step={step} outside [0, 2^56)')
+    return step * 256 + view * 64 + layer
+
+
+def _graph_scratch(slot, like):
+    return _device_ws(_GRAPH_WS[slot], like.device, like.numel(), torch.float32)[:like.numel()].view(like.shape)
+
+
+class NoisyPropagateFn(Function):
+    """The layer stack of SimGCL / XSimGCL: ``E_k = perturb_k(A^ E_(k-1))`` with ``E_0 = e0`` [n_users + n_items, D] and ``perturb_k`` the
+    noise of ``graph_propagate_noise`` drawn from ``stream_id = step * 256 + view * 64 + k`` -> ``(mean, kept)`` with
+    ``mean = (1 / L) sum_{k=1..L} E_k`` (layer 0 is left out, as in the authors' code) and ``kept = E_keep_layer`` (``keep_layer=None``:
+    None). L launches: the running sum starts at zero and every launch adds its perturbed layer (the last one also scales by 1 / L).
+    ``eps = 0`` runs ``sbr_graph_propagate_f32``, which gives the same bits as the noisy entry at eps = 0.
+
+    Backward: the noise is a constant and the sign has derivative zero, so the derivative is the linear operator alone. With
+    ``c_k = g_mean * (1 / L) + [k == keep_layer] g_kept``, ``dE0 = A^(c_1 + A^(c_2 + ... A^ c_L))``, by Horner: ``t = c_L``; for
+    k = L .. 2, ``t = (c_(k-1) + A^ t) * 1`` through the ``sum`` epilogue of ``sbr_graph_propagate_f32``; ``dE0 = A^ t`` — L launches of
+    the existing entry, no kernel of its own. Fixed order, no atomics: valid in deterministic mode."""
+
+    @staticmethod
+    def forward(ctx, csr, e0, n_layers: int, eps: float, seed: int, step: int, view: int, keep_layer=None):
+        n_layers = int(n_layers)
+        if n_layers < 1:
+            raise ValueError(f'NoisyPropagateFn: n_layers={n_layers}: with no layer there is nothing to perturb')
+        if keep_layer is not None and not 1 <= keep_layer <= n_layers:
+            raise ValueError(f'NoisyPropagateFn: keep_layer={keep_layer} outside [1, {n_layers}]')
+        if not float(eps) >= 0:
+            raise ValueError(f'NoisyPropagateFn: eps={eps} is negative')
+        ids = [noise_stream_id(int(step), int(view), k) for k in range(1, n_layers + 1)]
+        _need_cuda(e0)
+        x = _f32c(e0)
+        ctx.csr, ctx.n_layers, ctx.keep_layer = csr, n_layers, keep_layer
+        ctx.set_materialize_grads(False)
+        acc, kept = torch.zeros_like(x), None
+        for k in range(1, n_layers + 1):
+            y = torch.empty_like(x) if k == keep_layer else _graph_scratch(k & 1, x)
+            scale = 1.0 if k < n_layers else 1.0 / n_layers
+            if eps == 0:
+                graph_propagate(csr, x, out=y, sum=acc, sum_scale=scale)
+            else:
+                graph_propagate_noise(csr, x, eps, seed, ids[k - 1], out=y, sum=acc, sum_scale=scale)
+            x = y
+            if k == keep_layer:
+                kept = y
+        return acc, kept
+
+    @staticmethod
+    def backward(ctx, g_mean, g_kept=None):
+        if g_mean is None and g_kept is None:
+            return (None,) * 8
+        L, keep = ctx.n_layers, ctx.keep_layer
+        gm = None if g_mean is None else _f32c(g_mean) * (1.0 / L)
+        gk = None if g_kept is None else _f32c(g_kept)
+
+        def c(k):                                                    # a table of its own: it becomes the launch's running sum
+            if gk is not None and k == keep:
+                return gk.clone() if gm is None else gm + gk
+            return torch.zeros_like(gk) if gm is None else gm.clone()
+
+        t = c(L)
+        for k in range(L, 1, -1):
+            s = c(k - 1)
+            graph_propagate(ctx.csr, t, out=_graph_scratch(k & 1, t), sum=s, sum_scale=1.0)
+            t = s
+        return (None, graph_propagate(ctx.csr, t)) + (None,) * 6
 
 
 # ---- the multinomial log-likelihood of Mult-VAE / Mult-DAE (csrc/multinomial.hip) ------------------------------------------------------
@@ -1992,16 +2090,18 @@ def _infonce_ws(device, N, D):
     return _device_ws(_INFONCE_WS, device, lib().sbr_infonce_gemm_workspace(N, D), torch.uint8)
 
 
-def infonce_fwd(a_ptr, b_ptr, ld, G, N, D, tau, scale, loss_out, device):
-    if infonce_uses_gemm(G, N):
+def infonce_fwd(a_ptr, b_ptr, ld, G, N, D, tau, scale, loss_out, device, gemm=None):
+    """``gemm``: None chooses by ``infonce_uses_gemm``; False asks for the one-workgroup-per-group entry, which has a fixed-order form
+    and takes N <= ``infonce_max_n()``"""
+    if infonce_uses_gemm(G, N) if gemm is None else gemm:
         ws = _infonce_ws(device, N, D)
         call('sbr_infonce_gemm_fwd', a_ptr, b_ptr, ld, G, N, D, tau, scale, ptr(loss_out), ptr(ws), ws.numel(), stream())
     else:
         call('sbr_infonce_fwd', a_ptr, b_ptr, ld, G, N, D, tau, scale, ptr(loss_out), stream())
 
 
-def infonce_bwd(a_ptr, b_ptr, ld, G, N, D, tau, scale, gout, da_ptr, db_ptr, ldg, device):
-    if infonce_uses_gemm(G, N):
+def infonce_bwd(a_ptr, b_ptr, ld, G, N, D, tau, scale, gout, da_ptr, db_ptr, ldg, device, gemm=None):
+    if infonce_uses_gemm(G, N) if gemm is None else gemm:
         ws = _infonce_ws(device, N, D)
         call('sbr_infonce_gemm_bwd', a_ptr, b_ptr, ld, G, N, D, tau, scale, ptr(gout), da_ptr, db_ptr, ldg, ptr(ws), ws.numel(),
              stream())
@@ -2010,30 +2110,31 @@ def infonce_bwd(a_ptr, b_ptr, ld, G, N, D, tau, scale, gout, da_ptr, db_ptr, ldg
 
 
 class InfoNCEFn(Function):
-    """train/regularization_losses.py:14-43 on two [G, N, D] views that may be strided slices of one [G*N, 2, D] tensor."""
+    """train/regularization_losses.py:14-43 on two [G, N, D] views that may be strided slices of one [G*N, 2, D] tensor. ``gemm``: the
+    route, as in ``infonce_fwd`` (None: by ``infonce_uses_gemm``)."""
 
     @staticmethod
-    def forward(ctx, e, tau: float, mean: bool, G: int, N: int):
+    def forward(ctx, e, tau: float, mean: bool, G: int, N: int, gemm=None):
         # e: [G*N, 2, D] contiguous; a = e[:, 0], b = e[:, 1]
         _need_cuda(e)
         e = _f32c(e)
         D = e.shape[-1]
         out = torch.empty((), device=e.device, dtype=torch.float64)
         scale = 1.0 / (G * N) if mean else 1.0
-        infonce_fwd(e[:, 0].data_ptr(), e[:, 1].data_ptr(), 2 * D, G, N, D, tau, scale, out, e.device)
-        ctx.args = (tau, scale, G, N, D)
+        infonce_fwd(e[:, 0].data_ptr(), e[:, 1].data_ptr(), 2 * D, G, N, D, tau, scale, out, e.device, gemm)
+        ctx.args = (tau, scale, G, N, D, gemm)
         ctx.save_for_backward(e)
         return out.float()
 
     @staticmethod
     def backward(ctx, g):
         (e,) = ctx.saved_tensors
-        tau, scale, G, N, D = ctx.args
+        tau, scale, G, N, D, gemm = ctx.args
         g = g.float().contiguous()
         de = torch.empty_like(e)
         infonce_bwd(e[:, 0].data_ptr(), e[:, 1].data_ptr(), 2 * D, G, N, D, tau, scale, g, de[:, 0].data_ptr(),
-                    de[:, 1].data_ptr(), 2 * D, e.device)
-        return de, None, None, None, None
+                    de[:, 1].data_ptr(), 2 * D, e.device, gemm)
+        return de, None, None, None, None, None
 
 
 def infonce_max_n() -> int:
