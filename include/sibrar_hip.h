@@ -883,6 +883,55 @@ int sbr_graph_propagate_noise_f32(const long* u_indptr, const int* u_indices, co
 int sbr_multinomial_nll_f32(const long* indptr, const int* indices, const long* rows, long B, int n_items, const float* logits,
                             float* dlogits, float grad_scale, float* row_loss, float* row_lse, void* stream);
 
+/* ---- RecVAE's row-wise tails: swish + LayerNorm, and the composite-prior KL (csrc/recvae.hip) --------------------------------------------
+ * Every operand is a contiguous fp32 matrix with row stride equal to its width (row offsets are (long)b * width), or a vector; operands
+ * must not overlap. One wave owns a row: element j belongs to lane j % 64, a lane walks its elements in ascending order, and a sum over
+ * a row is the lanes' partial sums (from +0) added by an xor butterfly with the offsets 32, 16, .. 1. No product and sum is fused. The
+ * bits of a row's results depend on the row and the width alone: not on B, b, the run or the other rows. No atomics; none of these
+ * entries ever counts as a nondeterministic launch; all are valid in deterministic mode. New (additive to ABI 4).
+ *
+ * sbr_swish_ln_fwd: a [B, H], r_in [B, H] or NULL (read as zero, nothing added), gamma, beta [H], eps > 0 finite, 1 <= H <= 1024.
+ *   s = a + r_in;  y = s * (1 / (1 + expf(-s)));  mean = sum_j(y) / H;  d = y - mean;  rstd = 1 / sqrtf(sum_j(d * d) / H + eps);
+ *   h = ((d * rstd) * gamma) + beta;  r_out = r_in + h (h itself where r_in is NULL; r_out may be NULL: nothing is written).
+ *   Written: s, h [B, H], mean, rstd [B], r_out. The mean is taken first and the squares are those of the centred values.
+ *   Refused before any launch: H outside [1, 1024], B < 0, eps not positive and finite, a NULL a, gamma, beta, s, h, mean or rstd.
+ *   B == 0 returns at once.
+ * sbr_swish_ln_bwd: s, mean, rstd as the forward pass wrote them, gamma [H], dh and dr_out [B, H] (either may be NULL, not both).
+ *   g = dh + dr_out (the one given where the other is NULL);  sig, y as above;  xhat = (y - mean) * rstd;  gg = g * gamma;
+ *   c1 = sum_j(gg) / H;  c2 = sum_j(gg * xhat) / H;  ds = (rstd * ((gg - c1) - xhat * c2)) * (sig + y * (1 - sig));
+ *   da = ds;  dr_in = ds + dr_out (ds where dr_out is NULL; dr_in may be NULL);  dgamma = sum_b g * xhat;  dbeta = sum_b g.
+ *   The column sums: workgroup w is slab w and owns the rows [4 rps w, 4 rps (w + 1)), rps = max(1, ceil(B / 4096)); wave q adds its
+ *   rows first + q, first + q + 4, .. in that order from +0, the four waves are added in ascending order, and the slab's two rows of H
+ *   sums go to partials [sbr_swish_ln_slabs(B)][2][H] (written before it is read: no zeroing). A second launch adds the slabs in
+ *   ascending order in double and rounds once. dgamma, dbeta and partials are given together or all NULL (no column sums).
+ *   Refused before any launch: H outside [1, 1024], B < 0, a NULL s, mean, rstd, gamma or da, dh and dr_out both NULL, dgamma, dbeta
+ *   and partials not given together. B == 0 returns at once (dgamma and dbeta are then not written).
+ * sbr_swish_ln_slabs: the number of slabs for B rows (0 for B <= 0, at most 1,024): a count, not a status. */
+int sbr_swish_ln_fwd(const float* a, const float* r_in, const float* gamma, const float* beta, float eps, long B, int H, float* s, float* h,
+                     float* r_out, float* mean, float* rstd, void* stream);
+int sbr_swish_ln_bwd(const float* s, const float* mean, const float* rstd, const float* gamma, const float* dh, const float* dr_out, long B,
+                     int H, float* da, float* dr_in, float* dgamma, float* dbeta, float* partials, void* stream);
+int sbr_swish_ln_slabs(long B);
+/* sbr_prior_kl_fwd: mu, logvar, eps, mu_old, logvar_old [B, L], weight [B], 1 <= L <= 1024. Per element, with LOG2PI = log(2 pi):
+ *   z = mu + eps * E(0.5 * logvar), E the correctly rounded fp32 exponential (the double one, rounded once);
+ *   lq = -0.5 * (logvar + LOG2PI + eps * eps)             (log N(z; mu, logvar): (z - mu)^2 / exp(logvar) is eps^2)
+ *   l0 = log(3/20) - 0.5 * (LOG2PI + z * z);   l1 = log(3/4) - 0.5 * (logvar_old + LOG2PI + (z - mu_old)^2 / expf(logvar_old));
+ *   l2 = log(1/10) - 0.5 * (10 + LOG2PI + z * z / exp(10));   mx = max(l0, l1, l2);   se = expf(l0 - mx) + expf(l1 - mx) + expf(l2 - mx);
+ *   lp = mx + logf(se);   row_kl[b] = weight[b] * sum_j (lq - lp).
+ *   The largest of the three exponents is exactly 0, so se lies in [1, 3] whatever z and logvar_old are (finite l's).
+ *   Written: z [B, L], row_kl [B]. The mean over the batch is the caller's.
+ *   Refused before any launch: L outside [1, 1024], B < 0, a NULL operand. B == 0 returns at once.
+ * sbr_prior_kl_bwd: logvar, eps, mu_old, logvar_old, weight as above, z as the forward pass wrote it, dz [B, L] or NULL (the gradient that
+ *   reaches z from elsewhere), upstream: one fp32 on the device or NULL (read as 1), scale (the caller's 1 / B). c = upstream * scale *
+ *   weight[b];  e_c = expf(l_c - mx);  dlp = -((e_0 * z + e_1 * ((z - mu_old) / expf(logvar_old)) + e_2 * (z / exp(10))) / se);
+ *   t = dz - c * dlp;   dmu = t;   dlogvar = t * (0.5 * (eps * E(0.5 * logvar))) - 0.5 * c.   (lq gives mu nothing and logvar -c / 2.)
+ *   No gradient goes to mu_old, logvar_old or weight. Refused before any launch: L outside [1, 1024], B < 0, a NULL logvar, eps, mu_old,
+ *   logvar_old, weight, z, dmu or dlogvar. B == 0 returns at once. */
+int sbr_prior_kl_fwd(const float* mu, const float* logvar, const float* eps, const float* mu_old, const float* logvar_old, const float* weight,
+                     long B, int L, float* z, float* row_kl, void* stream);
+int sbr_prior_kl_bwd(const float* logvar, const float* eps, const float* mu_old, const float* logvar_old, const float* weight, const float* z,
+                     const float* dz, const float* upstream, float scale, long B, int L, float* dmu, float* dlogvar, void* stream);
+
 /* ---- DirectAU's loss terms: uniformity and alignment (csrc/directau.hip) --------------------------------------------------------------
  * Uniformity (Wang and Isola, ICML 2020; Wang et al., KDD 2022) of the rows of a contiguous fp32 x [n, D] with row stride D (no leading
  * dimension), 2 <= n, 1 <= D <= 256, t > 0. The rows need not be normalised. With

@@ -27,6 +27,7 @@ from .slim import SLIM                                                          
 from .p3alpha import P3alpha                                                                # noqa: F401
 from .lightgcn import LightGCN                                                              # noqa: F401
 from .multvae import MultDAE, MultVAE                                                       # noqa: F401
+from .recvae import RecVAE                                                                  # noqa: F401
 from .directau import DirectAU                                                              # noqa: F401
 from .simgcl import SimGCL, XSimGCL                                                         # noqa: F401
 from .als import AlternatingLeastSquare                                                     # noqa: F401
@@ -61,12 +62,12 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
 # .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .slim / .p3alpha / .als / .svd / .rbmf / .pop / .rand -> class
-# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae', 'multdae', 'directau', 'simgcl' and 'xsimgcl' are this package's own: the reference has
+# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae', 'multdae', 'recvae', 'directau', 'simgcl' and 'xsimgcl' are this package's own: the reference has
 # no trained graph model, no autoencoder over the interaction row, no model trained on alignment and uniformity and no contrastive one
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
               'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ifknn': ItemFeatureKNN, 'ease': EASE,
               'slim': SLIM, 'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF,
-              'pop': PopularItems, 'rand': RandomItems, 'lightgcn': LightGCN, 'multvae': MultVAE, 'multdae': MultDAE,
+              'pop': PopularItems, 'rand': RandomItems, 'lightgcn': LightGCN, 'multvae': MultVAE, 'multdae': MultDAE, 'recvae': RecVAE,
               'directau': DirectAU, 'simgcl': SimGCL, 'xsimgcl': XSimGCL}

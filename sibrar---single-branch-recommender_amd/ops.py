@@ -1670,6 +1670,114 @@ class MultinomialNLLFn(Function):
         return None, None, dl, None, None
 
 
+# ---- RecVAE's row-wise tails (csrc/recvae.hip) -------------------------------------------------------------------------------------------
+ROW_TAIL_MAX_W = 1024             # the widest row of the swish-LayerNorm and prior-KL kernels (a wave keeps the row in registers)
+
+
+def _row_tail_matrix(who, name, t, shape=None):
+    """``t`` as the kernels take it: a contiguous float32 [B, W] matrix on the device (the width's range is the library's refusal)"""
+    _need_cuda(t)
+    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = 'matrix' if shape is None else f'{list(shape)} matrix'
+        raise ValueError(f'{who}: {name} must be a contiguous float32 {want}, got {t.dtype} {tuple(t.shape)} strides {t.stride()}')
+    return t
+
+
+def _row_tail_vector(who, name, t, n):
+    _need_cuda(t)
+    if t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f'{who}: {name} must be a contiguous float32 [{n}] vector, got {t.dtype} {tuple(t.shape)}')
+    return t
+
+
+def swish_ln_slabs(B: int) -> int:
+    """how many slabs of column partials ``sbr_swish_ln_bwd`` writes for ``B`` rows (``sbr_swish_ln_slabs``)"""
+    return int(lib().sbr_swish_ln_slabs(int(B)))
+
+
+class SwishLayerNormFn(Function):
+    """One layer tail of RecVAE's encoder, ``sbr_swish_ln_fwd`` / ``sbr_swish_ln_bwd``: with ``s = a + r_in`` (``r_in`` None: ``s = a``),
+    ``h = LayerNorm(s * sigmoid(s))`` over the row (biased variance, ``gamma``, ``beta``, ``eps``) and ``r_out = r_in + h``, the running
+    sum of the layers' outputs -> ``(h, r_out)``; ``want_sum=False``: ``r_out`` is None and is not computed. One launch forward; two
+    backward (the rows, then the slabs of ``d gamma`` / ``d beta`` in slab order). Fixed order, no atomics: valid in deterministic mode.
+    ``a`` and ``r_in`` are contiguous float32 [B, H] with 1 <= H <= 1024 (the library refuses other widths)."""
+
+    @staticmethod
+    def forward(ctx, a, r_in, gamma, beta, eps: float = 0.1, want_sum: bool = True):
+        who = 'SwishLayerNormFn'
+        a = _row_tail_matrix(who, 'a', _f32c(a.detach()))
+        B, H = a.shape
+        if r_in is not None:
+            r_in = _row_tail_matrix(who, 'r_in', _f32c(r_in.detach()), (B, H))
+        gamma, beta = _row_tail_vector(who, 'gamma', gamma.detach(), H), _row_tail_vector(who, 'beta', beta.detach(), H)
+        s, h = torch.empty_like(a), torch.empty_like(a)
+        r_out = torch.empty_like(a) if want_sum else None
+        mean, rstd = (torch.empty(B, device=a.device, dtype=torch.float32) for _ in range(2))
+        call('sbr_swish_ln_fwd', ptr(a), ptr(r_in), ptr(gamma), ptr(beta), float(eps), B, H, ptr(s), ptr(h), ptr(r_out), ptr(mean), ptr(rstd),
+             stream())
+        ctx.save_for_backward(s, mean, rstd, gamma)
+        ctx.has_sum_in = r_in is not None
+        ctx.set_materialize_grads(False)
+        return h, r_out
+
+    @staticmethod
+    def backward(ctx, dh, dr_out):
+        s, mean, rstd, gamma = ctx.saved_tensors
+        if dh is None and dr_out is None:
+            return (None,) * 6
+        B, H = s.shape
+        dh, dr_out = (None if t is None else _f32c(t) for t in (dh, dr_out))
+        da = torch.empty_like(s)
+        dr_in = torch.empty_like(s) if (ctx.has_sum_in and ctx.needs_input_grad[1] and dr_out is not None) else None
+        dgamma = dbeta = part = None
+        if B and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3]):
+            dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+            part = torch.empty(swish_ln_slabs(B) * 2 * H, device=s.device, dtype=torch.float32)
+        call('sbr_swish_ln_bwd', ptr(s), ptr(mean), ptr(rstd), ptr(gamma), ptr(dh), ptr(dr_out), B, H, ptr(da), ptr(dr_in), ptr(dgamma),
+             ptr(dbeta), ptr(part), stream())
+        if ctx.has_sum_in and dr_in is None:
+            dr_in = da                                                     # no dr_out: dr_in is ds itself
+        return da, dr_in if ctx.has_sum_in else None, dgamma, dbeta, None, None
+
+
+class CompositePriorKLFn(Function):
+    """RecVAE's reparameterisation and KL term against its composite prior, ``sbr_prior_kl_fwd`` / ``sbr_prior_kl_bwd`` (one launch each):
+    ``z = mu + eps * exp(logvar / 2)`` and ``kl = mean_b weight_b * sum_j (log N(z; mu, logvar) - log p(z))`` with ``p`` the mixture
+    3/20 N(0, 1) + 3/4 N(mu_old, exp(logvar_old)) + 1/10 N(0, exp(10)) -> ``(z, kl)``. Gradients go to ``mu`` and ``logvar`` only, from
+    the ``z`` that the decoder used and from ``kl``; the upstream gradient of ``kl`` is read on the device (no synchronisation). All
+    operands are contiguous float32 [B, L] (``weight``: [B]) with 1 <= L <= 1024. Fixed order, no atomics: valid in deterministic mode."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, mu_old, logvar_old, weight):
+        who = 'CompositePriorKLFn'
+        mu = _row_tail_matrix(who, 'mu', _f32c(mu.detach()))
+        B, L = mu.shape
+        if B == 0:
+            raise ValueError('CompositePriorKLFn: an empty batch has no mean')
+        logvar, eps, mu_old, logvar_old = (_row_tail_matrix(who, n, _f32c(t.detach()), (B, L)) for n, t in (
+            ('logvar', logvar), ('eps', eps), ('mu_old', mu_old), ('logvar_old', logvar_old)))
+        weight = _row_tail_vector(who, 'weight', weight.detach(), B)
+        z = torch.empty_like(mu)
+        row_kl = torch.empty(B, device=mu.device, dtype=torch.float32)
+        call('sbr_prior_kl_fwd', ptr(mu), ptr(logvar), ptr(eps), ptr(mu_old), ptr(logvar_old), ptr(weight), B, L, ptr(z), ptr(row_kl), stream())
+        ctx.save_for_backward(logvar, eps, mu_old, logvar_old, weight, z)
+        ctx.set_materialize_grads(False)
+        return z, row_kl.sum() / B
+
+    @staticmethod
+    def backward(ctx, dz, dkl):
+        logvar, eps, mu_old, logvar_old, weight, z = ctx.saved_tensors
+        if dz is None and dkl is None:
+            return (None,) * 6
+        B, L = z.shape
+        dz = None if dz is None else _f32c(dz)
+        dkl = None if dkl is None else dkl.to(torch.float32).reshape(1)
+        dmu, dlogvar = torch.empty_like(z), torch.empty_like(z)
+        call('sbr_prior_kl_bwd', ptr(logvar), ptr(eps), ptr(mu_old), ptr(logvar_old), ptr(weight), ptr(z), ptr(dz), ptr(dkl),
+             1.0 / B if dkl is not None else 0.0, B, L, ptr(dmu), ptr(dlogvar), stream())
+        return dmu, dlogvar, None, None, None, None
+
+
 # ---- DirectAU's loss terms (csrc/directau.hip) -----------------------------------------------------------------------------------------
 UNIFORMITY_MAX_D = 256            # the backward pass keeps a row tile's [64, D] accumulator in registers
 
