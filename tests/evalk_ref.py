@@ -121,6 +121,14 @@ def mask_ref(scores, u_idx, csr, item_offset=None):
     return torch.from_numpy(out)
 
 
+def floor_ref(scores, mu):
+    """scores -> a copy with x[x < mu] = mu (the floor of the all-pairs evaluation form, applied before the mask); a NaN is not below mu
+    and stays, mu in fp32"""
+    out = _np(scores, np.float32).copy()
+    out[out < np.float32(mu)] = np.float32(mu)
+    return torch.from_numpy(out)
+
+
 def merge_ref(vals, idxs, k):
     """vals / idxs [W, Bu, k'] -> (values [Bu, k] fp32, indices [Bu, k] int32): the W lists of a user concatenated; idx < 0 marks an
     empty slot; score descending (the keys of (a)), then item index ascending; empty slots last, as (-inf, -1)"""

@@ -32,6 +32,33 @@ def ref_act(pre, act):
     return pre
 
 
+def ref_act_grad_from_out(y, act):
+    """d act / d pre-activation through the activation's OUTPUT (float64), with the fp32 selu constants of the kernels"""
+    if act == 1:
+        return (y > 0).double()
+    if act == 2:
+        return 1 - y * y
+    if act == 3:
+        return y * (1 - y)
+    if act == 4:
+        return torch.where(y > 0, torch.full_like(y, SELU_SF), y + SELU_SF * SELU_AF)
+    return torch.ones_like(y)
+
+
+def act_grad_err(y, act):
+    """bound of the fp32 evaluation of act'(y) on an fp32 y: relu / selu(y > 0) / none exact; 1 - y y: two roundings, each relative to
+    at most max(y^2, |1 - y^2|) <= y^2 + |g|; y (1 - y): two roundings relative to |g|; y + c: one rounding, and c = scale * alpha is
+    itself the fp32 product of the two fp32 constants (u c)"""
+    g = ref_act_grad_from_out(y, act).abs()
+    if act == 2:
+        return 2 * U32 * (g + y * y)
+    if act == 3:
+        return 2 * U32 * g
+    if act == 4:
+        return torch.where(y > 0, torch.zeros_like(g), U32 * (g + SELU_SF * SELU_AF))
+    return torch.zeros_like(g)
+
+
 def S():
     import sibrar_amd
     return sibrar_amd
@@ -104,7 +131,7 @@ class _Buf:
 
 LD_BIG = (1 << 25) + 64                     # a leading dimension that puts row 64 past element 2^31 and row 128 past element 2^32
 BIG_ROWS = 130                               # the most rows a _BigLd view may have
-BIG_ELEMS = (BIG_ROWS - 1) * LD_BIG + 256    # fp32 elements of the one buffer (about 16.1 GiB)
+BIG_ELEMS = (BIG_ROWS - 1) * LD_BIG + 1024   # fp32 elements of the one buffer (about 16.1 GiB); the last row may be up to 960 wide
 BIG_HEADROOM = 4 << 30                       # free device memory asked for beyond the buffer
 NAN_BITS = 0x7FC00000                        # what torch writes for float('nan'): the fill pattern of _Buf, compared bit for bit
 _BIG = {'flat': None}

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import deepmf_ref
+import evalk_ref
 from golden_util import GOLDEN, I, close, host_dataset, load, state_dict, world
 from oracle import losses_ref
 import scorer_truth_util as T
@@ -172,8 +173,7 @@ def test_floor_scores_in_place():
     x = torch.randn(37, 50, device=DEV)
     x[3, 4], x[5, 6] = float('nan'), -float('inf')
     view = x[:, :41]
-    ref = view.clone()
-    ref[ref < 0.1] = 0.1
+    ref = evalk_ref.floor_ref(view.cpu(), 0.1).to(DEV)
     keep = x[:, 41:].clone()
     S().ops.floor_scores_(view, 0.1)
     assert torch.equal(view.nan_to_num(7.0), ref.nan_to_num(7.0)) and bool(torch.isnan(view[3, 4])) and float(view[5, 6]) == np.float32(0.1)

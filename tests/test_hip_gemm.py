@@ -17,8 +17,7 @@ import pytest
 import torch
 
 import gemm_ref as R
-from hip_testutil import DEV, GUARD, S, _L, _assert_bits, _Buf, _i32, _p, call, stream
-from test_hip_tail import act_grad_err, ref_act_grad_from_out
+from hip_testutil import DEV, GUARD, S, _L, _assert_bits, _Buf, _i32, _p, act_grad_err, call, ref_act_grad_from_out, stream
 
 pytestmark = pytest.mark.gpu
 RATIOS = {}

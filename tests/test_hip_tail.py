@@ -21,8 +21,8 @@ import numpy as np
 import pytest
 import torch
 
-from hip_testutil import (DEV, EXP_ULP, LIP, NAN, SELU_A, SELU_AF, SELU_S, SELU_SF, U32, S, _L, _assert_bits, _assert_bound, _Buf, _p, _rand, call,
-                          ref_act, stream)
+from hip_testutil import (DEV, EXP_ULP, LIP, NAN, SELU_A, SELU_AF, SELU_S, SELU_SF, U32, S, _L, _assert_bits, _assert_bound, _Buf, _p, _rand, act_grad_err, call,
+                          ref_act, ref_act_grad_from_out, stream)
 
 pytestmark = pytest.mark.gpu
 U64 = 2.0 ** -53
@@ -74,33 +74,6 @@ def _err(fn, *args):
 # =================================================================================================================================
 # float64 references and bounds (imported by tests/test_tail_refs_cpu.py)
 # =================================================================================================================================
-def ref_act_grad_from_out(y, act):
-    """d act / d pre-activation through the activation's OUTPUT (float64), with the fp32 selu constants of the kernels"""
-    if act == 1:
-        return (y > 0).double()
-    if act == 2:
-        return 1 - y * y
-    if act == 3:
-        return y * (1 - y)
-    if act == 4:
-        return torch.where(y > 0, torch.full_like(y, SELU_SF), y + SELU_SF * SELU_AF)
-    return torch.ones_like(y)
-
-
-def act_grad_err(y, act):
-    """bound of the fp32 evaluation of act'(y) on an fp32 y: relu / selu(y > 0) / none exact; 1 - y y: two roundings, each relative to
-    at most max(y^2, |1 - y^2|) <= y^2 + |g|; y (1 - y): two roundings relative to |g|; y + c: one rounding, and c = scale * alpha is
-    itself the fp32 product of the two fp32 constants (u c)"""
-    g = ref_act_grad_from_out(y, act).abs()
-    if act == 2:
-        return 2 * U32 * (g + y * y)
-    if act == 3:
-        return 2 * U32 * g
-    if act == 4:
-        return torch.where(y > 0, torch.zeros_like(g), U32 * (g + SELU_SF * SELU_AF))
-    return torch.zeros_like(g)
-
-
 def ref_bn_stats(x, eps=EPS32):
     """x float64 [n, D] -> mean, biased var, rstd (float64)"""
     m = x.mean(0)
