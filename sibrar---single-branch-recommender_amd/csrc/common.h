@@ -90,6 +90,12 @@ __device__ __forceinline__ float sbr_wave_max(float v) {
 
 static inline int sbr_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// the byte ranges [a, a + na) and [b, b + nb) meet
+static inline bool sbr_overlap(const void* a, long na, const void* b, long nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb ? pb - pa < (uintptr_t)na : pa - pb < (uintptr_t)nb;
+}
+
 // 160 KiB of LDS per CU, all of which one workgroup may use
 #define SBR_LDS_MAX 163840
 

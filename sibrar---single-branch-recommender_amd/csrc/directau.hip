@@ -171,12 +171,6 @@ __global__ __launch_bounds__(UNI_THREADS) void uni_bwd_kernel(const float* __res
   }
 }
 
-// the byte ranges [a, a + na) and [b, b + nb) meet
-static inline bool uni_overlap(const void* a, long na, const void* b, long nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb ? pb - pa < (uintptr_t)na : pa - pb < (uintptr_t)nb;
-}
-
 static inline size_t uni_lds_bytes(int D) { return 2 * (size_t)((D + T64_KC - 1) / T64_KC * T64_KC) * T64_LD * sizeof(float); }
 
 static int uni_check(const char* who, long n, int D, float t, int max_wg) {
@@ -212,7 +206,7 @@ extern "C" int sbr_uniformity_bwd(const float* x, long n, int D, float t, const 
                                   void* stream) {
   if (int rc = uni_check("sbr_uniformity_bwd", n, D, t, max_wg)) return rc;
   SBR_REQUIRE(x && S && grad && dx, "sbr_uniformity_bwd: null operand (x, S, grad or dx)");
-  SBR_REQUIRE(!uni_overlap(x, 4L * n * D, dx, 4L * n * D), "sbr_uniformity_bwd: dx overlaps x (rows are read while other rows are written)");
+  SBR_REQUIRE(!sbr_overlap(x, 4L * n * D, dx, 4L * n * D), "sbr_uniformity_bwd: dx overlaps x (rows are read while other rows are written)");
   const size_t lds = uni_lds_bytes(D);
   hipStream_t st = (hipStream_t)stream;
   const int wgs = t64_wgs(n, max_wg > 0 ? max_wg : T64_MAX_WG);

@@ -191,12 +191,6 @@ __global__ __launch_bounds__(GP_THREADS) void graph_prop_kernel(const long* __re
   }
 }
 
-// the byte ranges [a, a + bytes) and [b, b + bytes) meet
-static inline bool gp_overlap(const void* a, const void* b, long bytes) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb ? pb - pa < (uintptr_t)bytes : pa - pb < (uintptr_t)bytes;
-}
-
 template <int V, int C, bool NOISE>
 static void gp_launch(const long* u_indptr, const int* u_indices, const long* i_indptr, const int* i_indices, int n_users, long r0, long r1,
                       const float* x, float* y, float* sum, float sum_scale, int D, int gshift, const GpNoise& nz, hipStream_t stream) {
@@ -216,10 +210,11 @@ static int gp_run(const char* who, const long* u_indptr, const int* u_indices, c
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= n, "%s: row range [%ld, %ld) outside [0, %ld]", who, r0, r1, n);
   SBR_REQUIRE(!nz || (nz->eps >= 0.f && nz->eps <= FLT_MAX), "%s: eps=%g must be finite and not negative", who, nz ? (double)nz->eps : 0.);
   const long bytes = 4 * n * D;
-  SBR_REQUIRE(!(x && y && gp_overlap(x, y, bytes)), "%s: x aliases y: a row reads other rows, so the input table cannot be an output", who);
-  SBR_REQUIRE(!(x && sum && gp_overlap(x, sum, bytes)), "%s: x aliases sum: a row reads other rows, so the input table cannot be an output",
+  SBR_REQUIRE(!(x && y && sbr_overlap(x, bytes, y, bytes)), "%s: x aliases y: a row reads other rows, so the input table cannot be an output",
               who);
-  SBR_REQUIRE(!(y && sum && gp_overlap(y, sum, bytes)), "%s: y aliases sum: both are written", who);
+  SBR_REQUIRE(!(x && sum && sbr_overlap(x, bytes, sum, bytes)), "%s: x aliases sum: a row reads other rows, so the input table cannot be an "
+              "output", who);
+  SBR_REQUIRE(!(y && sum && sbr_overlap(y, bytes, sum, bytes)), "%s: y aliases sum: both are written", who);
   if (r0 == r1) return SBR_OK;
   SBR_REQUIRE(u_indptr && i_indptr && x && y, "%s: null operand", who);                               // (a matrix without entries has no indices)
   // float4 chunks where every row of every table starts on a 16-byte boundary, single floats otherwise; the group is the smallest

@@ -158,25 +158,19 @@ __global__ __launch_bounds__(MN_THREADS) void mn_block_kernel(const long* __rest
   }
 }
 
-// the byte ranges [a, a + na) and [b, b + nb) meet
-static inline bool mn_overlap(const void* a, long na, const void* b, long nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb ? pb - pa < (uintptr_t)na : pa - pb < (uintptr_t)nb;
-}
-
 extern "C" int sbr_multinomial_nll_f32(const long* indptr, const int* indices, const long* rows, long B, int n_items, const float* logits,
                                        float* dlogits, float grad_scale, float* row_loss, float* row_lse, void* stream) {
   SBR_REQUIRE(n_items >= 1, "sbr_multinomial_nll_f32: n_items=%d is not positive", n_items);
   SBR_REQUIRE(B >= 0, "sbr_multinomial_nll_f32: B=%ld is negative", B);
   SBR_REQUIRE(indptr && rows && logits && row_loss, "sbr_multinomial_nll_f32: null operand (indptr, rows, logits or row_loss)");
   const long mat = 4L * B * n_items, vec = 4L * B;
-  SBR_REQUIRE(!(dlogits && dlogits != logits && mn_overlap(logits, mat, dlogits, mat)), "sbr_multinomial_nll_f32: dlogits overlaps logits "
+  SBR_REQUIRE(!(dlogits && dlogits != logits && sbr_overlap(logits, mat, dlogits, mat)), "sbr_multinomial_nll_f32: dlogits overlaps logits "
               "in part: it is logits itself (in place) or a disjoint matrix");
-  SBR_REQUIRE(!mn_overlap(row_loss, vec, logits, mat) && !(dlogits && mn_overlap(row_loss, vec, dlogits, mat)),
+  SBR_REQUIRE(!sbr_overlap(row_loss, vec, logits, mat) && !(dlogits && sbr_overlap(row_loss, vec, dlogits, mat)),
               "sbr_multinomial_nll_f32: row_loss overlaps logits or dlogits");
-  SBR_REQUIRE(!(row_lse && (mn_overlap(row_lse, vec, logits, mat) || (dlogits && mn_overlap(row_lse, vec, dlogits, mat)))),
+  SBR_REQUIRE(!(row_lse && (sbr_overlap(row_lse, vec, logits, mat) || (dlogits && sbr_overlap(row_lse, vec, dlogits, mat)))),
               "sbr_multinomial_nll_f32: row_lse overlaps logits or dlogits");
-  SBR_REQUIRE(!(row_lse && mn_overlap(row_lse, vec, row_loss, vec)), "sbr_multinomial_nll_f32: row_lse overlaps row_loss");
+  SBR_REQUIRE(!(row_lse && sbr_overlap(row_lse, vec, row_loss, vec)), "sbr_multinomial_nll_f32: row_lse overlaps row_loss");
   if (B == 0) return SBR_OK;
   // float4 where every row of both matrices starts on a 16-byte boundary, four floats per chunk otherwise: the same chunks, the same order
   const bool v4 = n_items % 4 == 0 && ((uintptr_t)logits | (uintptr_t)dlogits) % 16 == 0;

@@ -23,12 +23,6 @@
 #define RV_V2 10.f                     // the wide component's log-variance
 #define RV_EXP_V2 22026.465794806718f  // exp(10)
 
-__device__ __forceinline__ float rv_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ float rv_sigmoid(float s) { return 1.f / (1.f + expf(-s)); }
 
 // the float32 exponential, correctly rounded (through the double one): z has the same bits as a host restatement that does the same
@@ -63,7 +57,7 @@ __global__ __launch_bounds__(RV_THREADS) void rv_swish_ln_fwd_kernel(const float
         sum = sum + y[k];
       }
     }
-    const float m = rv_wave_sum(sum) / fh;
+    const float m = sbr_wave_sum(sum) / fh;
     float ss = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -72,7 +66,7 @@ __global__ __launch_bounds__(RV_THREADS) void rv_swish_ln_fwd_kernel(const float
         ss = ss + y[k] * y[k];
       }
     }
-    const float rs = 1.f / sqrtf(rv_wave_sum(ss) / fh + eps);
+    const float rs = 1.f / sqrtf(sbr_wave_sum(ss) / fh + eps);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = lane + 64 * k;
@@ -131,7 +125,7 @@ __global__ __launch_bounds__(RV_THREADS) void rv_swish_ln_bwd_kernel(const float
         pb[k] = pb[k] + g;
       }
     }
-    const float c1 = rv_wave_sum(sum1) / fh, c2 = rv_wave_sum(sum2) / fh;
+    const float c1 = sbr_wave_sum(sum1) / fh, c2 = sbr_wave_sum(sum2) / fh;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int j = lane + 64 * k;
@@ -211,7 +205,7 @@ __global__ __launch_bounds__(RV_THREADS) void rv_prior_kl_fwd_kernel(const float
         acc = acc + (lq - (x.mx + logf(x.se)));
       }
     }
-    acc = rv_wave_sum(acc);
+    acc = sbr_wave_sum(acc);
     if (lane == 0) row_kl[b] = weight[b] * acc;
   }
 }

@@ -29,19 +29,13 @@ two kernels of this model have no other form.
 """
 from __future__ import annotations
 
-import logging
-import math
 from types import SimpleNamespace
 
-import numpy as np
-import scipy.sparse as sp
 import torch
-from torch import nn
 
 from . import ops
 from .features import DeviceCSR
-from .matrix_models import ResidentMatrixAlgorithm
-from .optim import FusedOptimizer
+from .row_autoencoder import RowAutoencoder
 
 N_LAYERS = 5
 LN_EPS = 0.1
@@ -49,44 +43,6 @@ ENCODER_PARAMS = tuple(f'{kind}{k}' for k in range(1, N_LAYERS + 1) for kind in 
     ('mu_w', 'mu_b', 'logvar_w', 'logvar_b')
 DECODER_PARAMS = ('dec_w', 'dec_b')
 PARAMS = ENCODER_PARAMS + DECODER_PARAMS
-HYPER = ('hidden', 'latent', 'dropout', 'gamma', 'beta', 'lr', 'batch_size', 'n_epochs', 'n_enc_epochs', 'n_dec_epochs', 'weight_decay', 'seed')
-
-
-def encoder_shapes(n_items: int, hidden: int, latent: int) -> dict:
-    shapes = {}
-    for k in range(1, N_LAYERS + 1):
-        shapes[f'fc_w{k}'], shapes[f'fc_b{k}'] = (hidden, n_items if k == 1 else hidden), (hidden,)
-        shapes[f'ln_w{k}'] = shapes[f'ln_b{k}'] = (hidden,)
-    shapes.update(mu_w=(latent, hidden), mu_b=(latent,), logvar_w=(latent, hidden), logvar_b=(latent,))
-    return shapes
-
-
-class RecVAEEncoder(nn.Module):
-    """``fc_w1`` [hidden, I] stored column-major (``SparseLinearActFn``'s layout), ``fc_w2..5`` [hidden, hidden], the LayerNorms'
-    ``ln_w`` = 1 and ``ln_b`` = 0, and the two heads [latent, hidden]. Weights are Xavier-normal, biases normal with std 0.001, drawn on
-    the host from ``generator`` in the order of ``ENCODER_PARAMS``."""
-
-    def __init__(self, n_items: int, hidden: int, latent: int, generator: torch.Generator):
-        super().__init__()
-        for name, shape in encoder_shapes(n_items, hidden, latent).items():
-            if name.startswith('ln_'):
-                t = torch.ones(shape) if name.startswith('ln_w') else torch.zeros(shape)
-            elif len(shape) == 2:
-                t = torch.randn(*shape, generator=generator) * math.sqrt(2.0 / (shape[0] + shape[1]))
-                if name == 'fc_w1':
-                    t = t.t().contiguous().t()
-            else:
-                t = torch.randn(*shape, generator=generator) * 0.001
-            setattr(self, name, nn.Parameter(t))
-
-
-class RecVAEDecoder(nn.Module):
-    """``dec_w`` [I, latent] Xavier-normal and ``dec_b`` [I] normal with std 0.001, drawn after the encoder's from the same generator"""
-
-    def __init__(self, n_items: int, latent: int, generator: torch.Generator):
-        super().__init__()
-        self.dec_w = nn.Parameter(torch.randn(n_items, latent, generator=generator) * math.sqrt(2.0 / (n_items + latent)))
-        self.dec_b = nn.Parameter(torch.randn(n_items, generator=generator) * 0.001)
 
 
 def encode(p, csr: DeviceCSR, u: torch.Tensor):
@@ -99,63 +55,64 @@ def encode(p, csr: DeviceCSR, u: torch.Tensor):
     return ops.LinearActFn.apply(h, p.mu_w, p.mu_b, 0), ops.LinearActFn.apply(h, p.logvar_w, p.logvar_b, 0)
 
 
-class RecVAE(ResidentMatrixAlgorithm):
+class RecVAE(RowAutoencoder):
     """``kwargs``: ``device``. ``fit(matrix)`` trains; ``encoder`` and ``decoder`` hold the weights afterwards (None: not fitted)."""
-    KEY, WHAT = 'dec_w', 'weights'
+    KEY, INPUT = 'dec_w', 'fc_w1'
     STORES = 'the encoder\'s and the decoder\'s weight arrays'
     BINARY_ONLY = 'RecVAE: the multinomial likelihood takes the 0/1 rows as its targets'
+    HYPER = ('hidden', 'latent', 'dropout', 'gamma', 'beta', 'lr', 'batch_size', 'n_epochs', 'n_enc_epochs', 'n_dec_epochs', 'weight_decay', 'seed')
+    OPTIONAL = ('gamma', 'beta')
+    PARTS = {'encoder': ENCODER_PARAMS, 'decoder': DECODER_PARAMS}
+    CONSTANTS = {f'ln_{kind}{k}': value for k in range(1, N_LAYERS + 1) for kind, value in (('w', 1.), ('b', 0.))}       # the LayerNorms' start
 
     def __init__(self, hidden: int = 600, latent: int = 200, dropout: float = 0.5, gamma: float = 0.005, beta: float = None, lr: float = 5e-4,
                  batch_size: int = 500, n_epochs: int = 50, n_enc_epochs: int = 3, n_dec_epochs: int = 1, weight_decay: float = 0.,
                  seed: int = 0, **kwargs):
-        super().__init__(kwargs.get('device'))
-        if hidden < 1 or latent < 1 or batch_size < 1 or n_epochs < 0 or n_enc_epochs < 0 or n_dec_epochs < 0:
-            raise ValueError(f'hidden={hidden}, latent={latent}, batch_size={batch_size} must be positive and n_epochs={n_epochs}, '
-                             f'n_enc_epochs={n_enc_epochs}, n_dec_epochs={n_dec_epochs} not negative')
-        if not 0 <= dropout < 1:
-            raise ValueError(f'dropout={dropout!r} outside [0, 1)')
+        super().__init__(hidden, latent, dropout, lr, batch_size, n_epochs, weight_decay, seed, kwargs.get('device'))
+        if n_enc_epochs < 0 or n_dec_epochs < 0:
+            raise ValueError(f'n_enc_epochs={n_enc_epochs}, n_dec_epochs={n_dec_epochs} must not be negative')
         if gamma is None and beta is None:
             raise ValueError('RecVAE: gamma and beta are both unset: the KL term needs its weight (gamma * interactions, or the constant beta)')
-        self.hidden, self.latent, self.dropout, self.lr, self.batch_size = int(hidden), int(latent), float(dropout), float(lr), int(batch_size)
         self.gamma, self.beta = None if gamma is None else float(gamma), None if beta is None else float(beta)
         if not self.gamma and self.beta is None:
             raise ValueError('RecVAE: gamma is 0 and beta is unset: the KL term needs its weight')
-        self.n_epochs, self.n_enc_epochs, self.n_dec_epochs = int(n_epochs), int(n_enc_epochs), int(n_dec_epochs)
-        self.weight_decay, self.seed = float(weight_decay), int(seed)
-        self.encoder = self.decoder = self.old = None
-        self._input = self._dropped = self._weight = None
-        self.epoch_losses = []
-        self.name = 'RecVAE'
-        logging.info(f'Built {self.name} module \n- hidden: {self.hidden} \n- latent: {self.latent} \n- dropout: {self.dropout} \n- gamma: {self.gamma} ')
+        self.n_enc_epochs, self.n_dec_epochs = int(n_enc_epochs), int(n_dec_epochs)
+        self.old = None
 
     @classmethod
-    def build_from_conf(cls, conf: dict, dataset=None):
-        return cls(**{k: conf[k] for k in HYPER if k in conf})
+    def shapes(cls, n_items: int, hidden: int, latent: int) -> dict:
+        """the encoder's arrays in the order of ``ENCODER_PARAMS``: ``fc_w1`` [hidden, I] stored column-major (``SparseLinearActFn``'s
+        layout), ``fc_w2..5`` [hidden, hidden], the LayerNorms' ``ln_w`` = 1 and ``ln_b`` = 0, and the two heads [latent, hidden]; then the
+        decoder's ``dec_w`` [I, latent] and ``dec_b`` [I], drawn after the encoder's from the same generator"""
+        shapes = {}
+        for k in range(1, N_LAYERS + 1):
+            shapes[f'fc_w{k}'], shapes[f'fc_b{k}'] = (hidden, n_items if k == 1 else hidden), (hidden,)
+            shapes[f'ln_w{k}'] = shapes[f'ln_b{k}'] = (hidden,)
+        shapes.update(mu_w=(latent, hidden), mu_b=(latent,), logvar_w=(latent, hidden), logvar_b=(latent,), dec_w=(n_items, latent), dec_b=(n_items,))
+        return shapes
 
     @property
     def dec_w(self):
         return None if self.decoder is None else self.decoder.dec_w
 
+    @property
+    def _opt_enc(self):
+        return self._opts['encoder']
+
     # ---- residency ---------------------------------------------------------------------------------------------------------------
-    def _resident(self, m: sp.csr_matrix) -> DeviceCSR:
-        self._input = DeviceCSR(m, l2_normalize_rows=True).to(self.device)
-        self._dropped = self._weight = None
-        return DeviceCSR(m)
+    def _forget_views(self):
+        super()._forget_views()
+        self._weight = None                    # kl_weight's per-user table
 
     def to(self, device):
         super().to(device)
-        if self._input is not None:
-            self._input, self._dropped, self._weight = self._input.to(self.device), None, None
-        if self.encoder is not None:
-            self.encoder, self.decoder = self.encoder.to(self.device), self.decoder.to(self.device)
         if self.old is not None:
             self.old = SimpleNamespace(**{k: v.to(self.device) for k, v in vars(self.old).items()})
         return self
 
-    def _build(self, n_items: int):
-        g = torch.Generator().manual_seed(self.seed)
-        self.encoder = RecVAEEncoder(n_items, self.hidden, self.latent, g).to(self.device)
-        self.decoder = RecVAEDecoder(n_items, self.latent, g).to(self.device)
+    def _set_weights(self, tensors: dict):
+        super()._set_weights(tensors)
+        self._weight = None
         self.update_prior()
 
     # ---- the network ---------------------------------------------------------------------------------------------------------------
@@ -166,12 +123,8 @@ class RecVAE(ResidentMatrixAlgorithm):
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         return ops.LinearActFn.apply(z, self.decoder.dec_w, self.decoder.dec_b, 0)
 
-    def dropped_input(self, seed: int) -> DeviceCSR:
-        """the normalised rows with ``sbr_dropout(p = dropout, seed)`` applied to their stored values"""
-        if self._dropped is None:
-            self._dropped = self._input.value_view()
-            self._kept_values = self._dropped.data
-        return self._dropped.replace_values(ops.DropoutFn.apply(self._kept_values, self.dropout, int(seed)))
+    def _network(self, u: torch.Tensor) -> torch.Tensor:
+        return self.decode(encode(self.encoder, self._input, u)[0])
 
     def kl_weight(self, u: torch.Tensor) -> torch.Tensor:
         """``gamma * n_b`` of the users ``u``, from the resident matrix's ``indptr``; the constant ``beta`` when ``gamma`` is None or 0"""
@@ -184,7 +137,7 @@ class RecVAE(ResidentMatrixAlgorithm):
         """-> (loss, nll, kld, logits) of the batch of users ``u`` (int64 [B] on the device) with the noise ``eps`` [B, latent];
         ``dropout_seed`` None: no input dropout. With ``inplace`` the logits are overwritten by their gradient when they need one.
         ``encoder_grad=False``: the encoder runs under ``no_grad`` (a decoder pass)."""
-        csr = self.dropped_input(dropout_seed) if dropout_seed is not None and self.dropout > 0 else self._input
+        csr = self._rows_in(dropout_seed)
         with torch.set_grad_enabled(encoder_grad and torch.is_grad_enabled()):
             mu, logvar = encode(self.encoder, csr, u)
         with torch.no_grad():
@@ -195,101 +148,30 @@ class RecVAE(ResidentMatrixAlgorithm):
         return nll + kld, nll, kld, logits
 
     # ---- training ------------------------------------------------------------------------------------------------------------------
-    def fit(self, matrix: sp.spmatrix, **kwargs):
-        """:param matrix: user x item sparse matrix, 0/1"""
-        self.attach(matrix)
-        self.encoder = self.decoder = self.old = None
-        self._build(self.n_items)
-        self._opt_enc = FusedOptimizer(self.encoder, 'adam', self.lr, self.weight_decay)
-        self._opt_dec = FusedOptimizer(self.decoder, 'adam', self.lr, self.weight_decay)
-        self.update_prior()
-        self._gen = torch.Generator(device=self.device).manual_seed(self.seed)
-        counts = self._matrix.indptr[1:] - self._matrix.indptr[:-1]
-        self._active = torch.nonzero(counts > 0).reshape(-1)
-        self._step, self.epoch_losses = 0, []
-        for epoch in range(self.n_epochs):
-            self.train_epoch()
-            logging.info(f'{self.name}: epoch {epoch} loss {self.epoch_losses[-1]:.6f}')
-        return self
+    def _batch_loss(self, part: str, u: torch.Tensor, dropout_seed: int) -> torch.Tensor:
+        enc = part == 'encoder'
+        eps = torch.randn(u.numel(), self.latent, generator=self._gen, device=self.device)
+        return self.loss(u, eps, dropout_seed if enc else None, encoder_grad=enc)[0]
 
     def train_pass(self, part: str) -> torch.Tensor:
-        """One pass over a fresh permutation of the users that have an interaction, updating the encoder (``part='encoder'``, input
-        dropout) or the decoder (``'decoder'``, no dropout, the encoder without gradients) -> the sum of the batch losses times the
-        batch sizes, on the device (no synchronisation)."""
-        enc = part == 'encoder'
-        if not enc and part != 'decoder':
+        """A pass that updates the encoder (``part='encoder'``, input dropout) or the decoder (``'decoder'``, no dropout, the encoder
+        without gradients)."""
+        if part not in self.PARTS:
             raise ValueError(f'train_pass: part={part!r} is neither encoder nor decoder')
-        opt, gen = (self._opt_enc if enc else self._opt_dec), self._gen
         for p in self.decoder.parameters():
-            p.requires_grad_(not enc)
-        order = self._active[torch.randperm(self._active.numel(), generator=gen, device=self.device)]
-        total = torch.zeros((), device=self.device)
+            p.requires_grad_(part == 'decoder')
         try:
-            for lo in range(0, order.numel(), self.batch_size):
-                u = order[lo:lo + self.batch_size].contiguous()
-                eps = torch.randn(u.numel(), self.latent, generator=gen, device=self.device)
-                loss = self.loss(u, eps, dropout_seed=(self.seed << 32) + self._step if enc else None, encoder_grad=enc)[0]
-                loss.backward()
-                opt.step()
-                opt.zero_grad()
-                total += loss.detach() * u.numel()
-                self._step += 1
+            return super().train_pass(part)
         finally:
             for p in self.decoder.parameters():
                 p.requires_grad_(True)
-        return total
 
-    def train_epoch(self) -> float:
-        """``n_enc_epochs`` encoder passes, ``update_prior()``, ``n_dec_epochs`` decoder passes (after ``fit`` has set the training state
-        up, also with ``n_epochs=0``) -> the mean loss of the epoch's last pass, also appended to ``epoch_losses``: the epoch's one
-        synchronisation."""
+    def _epoch(self) -> torch.Tensor:
+        """``n_enc_epochs`` encoder passes, ``update_prior()``, ``n_dec_epochs`` decoder passes"""
         last = torch.zeros((), device=self.device)
         for _ in range(self.n_enc_epochs):
             last = self.train_pass('encoder')
         self.update_prior()
         for _ in range(self.n_dec_epochs):
             last = self.train_pass('decoder')
-        self.epoch_losses.append(float(last) / max(self._active.numel(), 1))
-        return self.epoch_losses[-1]
-
-    # ---- scoring -------------------------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def _score_rows(self, u: torch.Tensor) -> torch.Tensor:
-        if self.encoder.fc_w1.shape[1] != self.n_items:
-            raise ValueError(f'{self.name}: weights for {self.encoder.fc_w1.shape[1]} items do not fit the {self.n_items} items of the matrix')
-        return self.decode(encode(self.encoder, self._input, u.long().contiguous())[0])
-
-    # ---- persistence ---------------------------------------------------------------------------------------------------------------
-    def _arrays(self) -> dict:
-        return {**{k: getattr(self.encoder, k) for k in ENCODER_PARAMS}, **{k: getattr(self.decoder, k) for k in DECODER_PARAMS}}
-
-    def _npz_fields(self) -> dict:
-        hyper = {h: np.array(np.nan if getattr(self, h) is None else getattr(self, h)) for h in HYPER}       # None (gamma, beta) is stored as NaN
-        return {**{k: v.detach().cpu().numpy() for k, v in self._arrays().items()}, **hyper}
-
-    def _read_npz(self, f):
-        missing = [k for k in PARAMS + HYPER if k not in f.files]
-        if missing:
-            raise ValueError(f'model.npz: no {missing}')
-        hyper = {h: f[h].item() for h in HYPER}
-        w = {k: f[k] for k in PARAMS}
-        hidden, latent = int(hyper['hidden']), int(hyper['latent'])
-        n_items = w['fc_w1'].shape[1] if w['fc_w1'].ndim == 2 else -1
-        want = {**encoder_shapes(n_items, hidden, latent), 'dec_w': (n_items, latent), 'dec_b': (n_items,)}
-        bad = {k: w[k].shape for k in PARAMS if tuple(w[k].shape) != want[k]}
-        if bad:
-            raise ValueError(f'model.npz: arrays of shapes {bad} do not belong to a {self.name} with hidden={hidden}, latent={latent}')
-        g = torch.Generator().manual_seed(0)
-        encoder, decoder = RecVAEEncoder(n_items, hidden, latent, g), RecVAEDecoder(n_items, latent, g)
-        with torch.no_grad():
-            for k in PARAMS:
-                getattr(encoder if k in ENCODER_PARAMS else decoder, k).copy_(torch.from_numpy(w[k].astype(np.float32)))
-        for h in HYPER:
-            v = hyper[h]
-            if h in ('gamma', 'beta'):
-                setattr(self, h, None if math.isnan(v) else float(v))
-            else:
-                setattr(self, h, type(getattr(self, h))(v))
-        self.encoder, self.decoder = encoder.to(self.device), decoder.to(self.device)
-        self._weight = None
-        self.update_prior()
+        return last

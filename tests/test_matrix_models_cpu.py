@@ -1,6 +1,6 @@
 """The base of the fit(matrix) models (sibrar_amd.matrix_models) without a GPU: a toy model whose score rows are a fixed table on the host
 goes through the hooks, predict, attach and model.npz as ResidentMatrixAlgorithm writes them once; and UserKNN, ItemKNN, EASE and P3alpha
-stand on that base without a copy of their own."""
+stand on that base without a copy of their own; the model.npz fields of the row autoencoders (row_autoencoder.py) round-trip on the host."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -120,6 +120,48 @@ def test_foreign_model_files_are_refused(tmp_path):
     np.savez(tmp_path / 'model.npz', B=np.zeros((2, 2)), name=np.array('Toy'))       # the model's own array is missing
     with pytest.raises(ValueError, match='is not a model of this package'):
         toy().load_model_from_path(str(tmp_path))
+
+
+def test_row_autoencoder_fields_round_trip(tmp_path):
+    """RowAutoencoder's field logic alone, on the host: ``_npz_fields`` -> ``np.savez`` -> ``_read_npz`` on models whose arrays were set by
+    hand; None -> NaN -> None for RecVAE's ``gamma`` and ``beta``; a missing key and a wrong shape refused, the model left as it was."""
+    Sm = S()
+    I, H, L = 7, 4, 3
+
+    def by_hand(cls):
+        return {k: torch.arange(float(np.prod(s))).reshape(s) * 0.01 + n for n, (k, s) in enumerate(cls.shapes(I, H, L).items())}
+
+    for cls, kw in ((Sm.RecVAE, dict(gamma=None, beta=0.25)), (Sm.RecVAE, dict(gamma=0.02, beta=None)), (Sm.MultVAE, dict(anneal_cap=0.5)),
+                    (Sm.MultDAE, dict(total_anneal_steps=9))):
+        m = cls(hidden=H, latent=L, dropout=0.25, lr=3e-3, batch_size=7, n_epochs=2, weight_decay=1e-4, seed=8, device='cpu', **kw)
+        arrays = by_hand(cls)
+        m._set_weights(arrays)
+        fields = m._npz_fields()
+        assert set(fields) == set(arrays) | set(cls.HYPER)
+        for h in cls.OPTIONAL:
+            assert np.isnan(fields[h]) == (getattr(m, h) is None)
+        np.savez(tmp_path / 'model.npz', **fields)
+        back = cls(device='cpu')
+        with np.load(tmp_path / 'model.npz', allow_pickle=False) as f:
+            back._read_npz(f)
+        for h in cls.HYPER:
+            assert getattr(back, h) == getattr(m, h) and type(getattr(back, h)) is type(getattr(m, h)), h
+        for part, names in cls.PARTS.items():
+            for k in names:
+                assert torch.equal(getattr(getattr(back, part), k).detach(), arrays[k]), k
+        assert getattr(getattr(back, next(iter(cls.PARTS))), cls.INPUT).t().is_contiguous()
+        for drop in (cls.INPUT, 'seed', cls.HYPER[-2]):
+            np.savez(tmp_path / 'less.npz', **{k: v for k, v in fields.items() if k != drop})
+            fresh = cls(device='cpu')
+            with np.load(tmp_path / 'less.npz', allow_pickle=False) as f, pytest.raises(ValueError, match=f"model.npz: no \\['{drop}'\\]"):
+                fresh._read_npz(f)
+            assert getattr(fresh, cls.KEY) is None and fresh.hidden == 600
+        for k in (cls.INPUT, next(reversed(arrays))):
+            np.savez(tmp_path / 'bad.npz', **{**fields, k: fields[k][:-1]})
+            fresh = cls(device='cpu')
+            with np.load(tmp_path / 'bad.npz', allow_pickle=False) as f, pytest.raises(ValueError, match=f'do not belong to a {cls.__name__} with hidden={H}'):
+                fresh._read_npz(f)
+            assert getattr(fresh, cls.KEY) is None and fresh.hidden == 600
 
 
 def test_the_four_models_stand_on_the_base():

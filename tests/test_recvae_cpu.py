@@ -2,7 +2,8 @@
 closed-form float64 forward and backward formulas (the value halves of the bound pairs) against float64 autograd of the definitions; the
 float32 restatement in the kernels' order inside the derived bound, the measured ratio printed; the LayerNorm invariants; the
 log-sum-exp at the extremes; the float32-CPU error of the model, which tests/test_hip_recvae.py takes 8 times as its allowance; and the
-package's side that needs no GPU (the registry, the constructor's refusals, the declared entries)."""
+package's side that needs no GPU (the registry, the constructor's refusals, the declared entries, the autoencoders' shared initialiser)."""
+import math
 import os
 import re
 
@@ -116,6 +117,58 @@ def test_model_float32_error_on_the_cpu():
     print(f'loss {float(out64[0]):.6f} (nll {float(out64[1]):.6f}, kld {float(out64[2]):.6f}); largest gradient error {max(v for k, v in errs.items() if k != "loss"):.3e}')
     assert all(v > 0 for v in errs.values()), 'a float32 error of exactly 0 would make the GPU test\'s allowance 0'
     assert errs['loss'] <= 1e-4 * abs(float(out64[0]))
+
+
+@pytest.mark.parametrize('seed', [0, 5])
+def test_the_shared_initialiser_draws_in_the_stated_order(seed):
+    """row_autoencoder.init_weights on the Mult-VAE, Mult-DAE and RecVAE tables at (n_items, hidden, latent) = (7, 4, 3): a matrix
+    [out, in] is randn * sqrt(2 / (out + in)), a vector randn * 0.001, drawn in the table's order from one generator; the first layer
+    is column-major; the LayerNorm constants draw nothing. The expected tensors are written out with torch.randn."""
+    from importlib import import_module
+    import sibrar_amd as S
+    pkg = S.ops.__name__.rsplit('.', 1)[0]
+    init_weights, multvae = import_module(pkg + '.row_autoencoder').init_weights, import_module(pkg + '.multvae')
+    I, H, L = 7, 4, 3
+
+    def gen():
+        return torch.Generator().manual_seed(seed)
+
+    def mat(g, out, inp):
+        return torch.randn(out, inp, generator=g) * math.sqrt(2.0 / (out + inp))
+
+    def vec(g, n):
+        return torch.randn(n, generator=g) * 0.001
+
+    for cls, code in ((S.MultVAE, 2 * L), (S.MultDAE, L)):
+        g = gen()
+        want = {}
+        for layer, (out, inp) in zip(('enc1', 'enc2', 'dec1', 'dec2'), ((H, I), (code, H), (H, L), (I, H))):
+            want['w_' + layer] = mat(g, out, inp)
+            want['b_' + layer] = vec(g, out)
+        got = init_weights(cls.shapes(I, H, L), gen(), (cls.INPUT,), cls.CONSTANTS)
+        assert tuple(got) == tuple(want) == multvae.PARAMS
+        for k in want:
+            assert got[k].dtype == torch.float32 and torch.equal(got[k], want[k]), f'{cls.__name__}: {k}'
+        assert got['w_enc1'].t().is_contiguous() and got['w_dec2'].is_contiguous()
+        net = multvae.AutoencoderWeights(I, H, L, code, seed)
+        assert [k for k, _ in net.named_parameters()] == list(want) and all(torch.equal(getattr(net, k), want[k]) for k in want)
+        assert net.w_enc1.t().is_contiguous()
+
+    g = gen()
+    want = {}
+    for k in range(1, 6):
+        want[f'fc_w{k}'] = mat(g, H, I if k == 1 else H)
+        want[f'fc_b{k}'] = vec(g, H)
+        want[f'ln_w{k}'], want[f'ln_b{k}'] = torch.ones(H), torch.zeros(H)
+    want['mu_w'], want['mu_b'] = mat(g, L, H), vec(g, L)
+    want['logvar_w'], want['logvar_b'] = mat(g, L, H), vec(g, L)
+    want['dec_w'], want['dec_b'] = mat(g, I, L), vec(g, I)               # the draw that follows logvar_b: the ln_* took none
+    got = init_weights(S.RecVAE.shapes(I, H, L), gen(), (S.RecVAE.INPUT,), S.RecVAE.CONSTANTS)
+    assert tuple(got) == tuple(want) == R.PARAMS
+    for k in want:
+        assert got[k].dtype == torch.float32 and torch.equal(got[k], want[k]), f'RecVAE: {k}'
+    assert got['fc_w1'].t().is_contiguous() and got['fc_w2'].is_contiguous()
+    assert S.RecVAE.PARTS == {'encoder': R.ENCODER_PARAMS, 'decoder': R.DECODER_PARAMS}
 
 
 def test_package_side_without_a_gpu():
