@@ -1129,6 +1129,58 @@ int sbr_maxvol_swap_step_f32(float* B, long n, long ldb, int r, float tol, int s
  * is then unspecified). New (additive to ABI 4). */
 int sbr_chol_f32(const float* K, int n, long ldk, float* R, long ldr, int* info, void* stream);
 
+/* ---- UltraGCN (csrc/ultragcn.hip) -------------------------------------------------------------------------------------------------
+ * Mao et al., CIKM 2021; the reference has no such model. The definitions are the authors' code as remembered.
+ *
+ * sbr_cooc_weight_topk: X [n, m] binary CSR and X^T in the form of sbr_knn_topk; m <= 2^24. For every row i of [r0, r1) the
+ * candidates are the rows j with c = |row i & row j| > 0 (j = i among them when include_self != 0) and
+ *   value = (float(c) * row_scale[i]) * col_scale[j]        two rounded fp32 multiplications, nothing contracted, c converted exactly;
+ * a value that is not > 0 is no candidate. row_scale, col_scale: fp32 [n]. The list of row i is the first min(k, candidates) by (value
+ * descending, index ascending): nbr_idx int32 [n, k], nbr_val fp32 [n, k], nbr_len int32 [n], (-1, 0) behind the length; only the rows
+ * of [r0, r1) are written. 1 <= k <= 64. tile_cols as for sbr_knn_topk. The counting and the selection are sbr_knn_topk's device code
+ * (csrc/csr_walk.h, csrc/cooc_topk.h). Nothing of size n x n exists. Integer LDS atomics only: the same bits on every run and for
+ * every split of the rows, valid in deterministic mode. UltraGCN's item-item lists: X^T as the matrix, row_scale[i] = sqrt(g_i + 1) / g_i,
+ * col_scale[j] = 1 / sqrt(g_j + 1), g = the row sums of X^T X. New (additive to ABI 4). */
+int sbr_cooc_weight_topk(const long* indptr, const int* indices, const long* t_indptr, const int* t_indices, int n, int m, int r0, int r1,
+                         const float* row_scale, const float* col_scale, int include_self, int k, int tile_cols, int* nbr_idx,
+                         float* nbr_val, int* nbr_len, void* stream);
+/* sbr_ultragcn_loss_fwd_bwd: the loss of a batch, its gradient by the user rows and its gradient by the scores, in one pass.
+ * Ub fp32 [B, D]: the users' rows (contiguous). V fp32 [n_items, D]: the item table, contiguous, row j at (long)j * D. u_idxs int32 [B],
+ * i_idxs int32 [B, 1 + N]: the positive in column 0, N negatives behind it. beta_u fp32 [n_users], beta_i fp32 [n_items]. nbr_idx /
+ * nbr_val / nbr_len: lists [n_items, K] in the form sbr_cooc_weight_topk writes. Batch row b has the slots c = 0 (item p = i_idxs[b, 0]),
+ * 1 .. N (the negatives), 1 + N + k (nbr_idx[p, k], k < K). With s = <Ub[b], V[item of the slot]>, sp(x) = max(x, 0) + log1pf(expf(-|x|)),
+ * sig(x) = x >= 0 ? 1 / (1 + e) : e / (1 + e), e = expf(-|x|), every product and sum below one rounded fp32 operation in the order written:
+ *   slot 0        w = w1 + w2 * (beta_u[u] * beta_i[p])      term w * sp(-s)   coef = -(w * sig(-s))
+ *   slot 1 .. N   w = w3 + w4 * (beta_u[u] * beta_i[j])      term w * sp(s)    coef = (fl(negative_weight / N) * w) * sig(s)
+ *   neighbour k   w = nbr_val[p, k], k < nbr_len[p]          term w * sp(-s)   coef = -((lam * w) * sig(-s))
+ * A neighbour slot at or behind nbr_len[p], and any slot whose item index lies outside [0, n_items), has coef +0, adds nothing and
+ * reads no table row (an index of -1 never addresses the table). A user index outside [0, n_users) takes beta_u = 0.
+ * The row belongs to a group of G lanes: V = 4 columns per chunk when D % 4 == 0 (Ub, V, dUb must then start on a 16-byte boundary),
+ * else 1; G = the smallest power of two with G * V >= D, 64 at the most; lane l owns the chunks l, l + G, ... . s is the lane's fmaf
+ * chain over its columns in ascending order from +0, then an xor butterfly over the group from offset G / 2 down to 1. dUb[b, d] is one
+ * fmaf chain from +0 of coef * V[item][d] over the slots in ascending c. The terms of a row are added in double in ascending c per part;
+ * the negatives' sum is divided by N. The rows' partials (workspace: 24 B bytes, sbr_ultragcn_loss_workspace) are folded in double by a
+ * second, one-wave launch: lane l adds the rows l, l + 64, ... in ascending order, then an xor butterfly from offset 32 down to 1.
+ * All orders are functions of (D, N, K, B) alone. parts fp32 [4] = (pos, neg, nbr, pos + negative_weight * neg + lam * nbr), each
+ * rounded once; dUb fp32 [B, D]; coef fp32 [B, 1 + N + K]; scores fp32 [B, 1 + N] = s of the first 1 + N slots (may be NULL; 0 where the
+ * index lies outside the table). 1 <= D <= 256, N >= 1, 1 <= K <= 64, B (1 + N + K) < 2^31. No atomics:
+ * valid in deterministic mode. New (additive to ABI 4). */
+long sbr_ultragcn_loss_workspace(int B);
+int sbr_ultragcn_loss_fwd_bwd(const float* Ub, const float* V, const int* u_idxs, const int* i_idxs, const float* beta_u,
+                              const float* beta_i, const int* nbr_idx, const float* nbr_val, const int* nbr_len, int B, int D, int N, int K,
+                              int n_users, int n_items, float w1, float w2, float w3, float w4, float negative_weight, float lam,
+                              float* parts, float* dUb, float* coef, float* scores, void* workspace, long workspace_bytes, void* stream);
+/* sbr_scatter_add_scaled_rows_sorted: dst[j, d] += grad[0] * S_j[d] for every row j of dst fp32 [n_rows, D] (contiguous) that a slot
+ * names, S_j[d] = the fmaf chain from +0 of coef[pos] * src[pos / slots_per_row, d] over the slot positions pos whose key is j, in
+ * ascending pos. sorted_keys int32 [n_slots]: the slots' keys after a stable ascending sort; order int64 [n_slots]: the position each
+ * sorted entry came from (torch.sort(stable=True)). A key outside [0, n_rows), the sentinel of a padded slot, belongs to no row and
+ * is skipped on the device; nothing is counted on the host. coef fp32 [n_slots]; src fp32 [n_slots / slots_per_row, D]; grad: one fp32
+ * on the device. One wave per row of dst (its segment by two binary searches), one writer per row, one rounded multiplication by grad
+ * and one rounded addition per element; rows that no slot names are not touched. 1 <= D <= 256, n_slots < 2^31. The only form: valid
+ * in deterministic mode. UltraGCN's item-table gradient: keys = the slots' item indices, src = Ub. New (additive to ABI 4). */
+int sbr_scatter_add_scaled_rows_sorted(const float* coef, const float* src, const int* sorted_keys, const long* order, long n_slots,
+                                       int slots_per_row, const float* grad, float* dst, int n_rows, int D, void* stream);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

@@ -7,6 +7,7 @@
 // operation order, so both entries give the same bits on every run and are valid in deterministic mode.
 #include "common.h"
 #include "csr_walk.h"
+#include "cooc_topk.h"
 
 #define KNN_THREADS 1024
 #define KNN_WAVES (KNN_THREADS / 64)
@@ -55,68 +56,26 @@ __device__ __forceinline__ float knn_value(int sim, unsigned int c, int ni, int 
   return v * s;
 }
 
-// One histogram add. Similarities crowd into a few exponents, so in the leading radix passes most lanes of a wave name the same
-// bin: when they all do, one lane adds the wave's count instead of up to 64 adds queueing on one address. Called by whole waves.
-__device__ __forceinline__ void knn_hist_add(unsigned int* hist, bool active, unsigned int digit) {
-  const unsigned long long act = __ballot(active);
-  if (act == 0ull) return;
-  const int src = __ffsll((long long)act) - 1;
-  const unsigned int first = (unsigned int)__shfl((int)digit, src, 64);
-  if (__ballot(active && digit == first) == act) {
-    if ((int)(threadIdx.x & 63) == src) atomicAdd(&hist[first], (unsigned int)__popcll(act));
-  } else if (active) {
-    atomicAdd(&hist[digit], 1u);
-  }
-}
-
-// The radix step of wave 0: the bin d (from 255 down) at which the running count reaches `need`; -> true in the lane that holds it,
-// with the count of the bins above it and the bin's own count. Lane l owns the bins 255 - 4 l ... 252 - 4 l. total: all bins.
-__device__ __forceinline__ bool knn_find_bin(const unsigned int* hist, unsigned int need, int lane, int& d, unsigned int& above,
-                                             unsigned int& own, unsigned int& total) {
-  unsigned int h[4], s = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { h[q] = hist[255 - 4 * lane - q]; s += h[q]; }
-  unsigned int incl = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned int up = (unsigned int)__shfl_up((int)incl, o, 64);
-    if (lane >= o) incl += up;
-  }
-  total = (unsigned int)__shfl((int)incl, 63, 64);
-  unsigned int a = incl - s;
-  bool found = false;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (!found && a + h[q] >= need) { found = true; d = 255 - 4 * lane - q; above = a; own = h[q]; }
-    a += h[q];
-  }
-  const unsigned long long f = __ballot(found);
-  return found && lane == __ffsll((long long)f) - 1;
-}
-
 // One workgroup per row i of X. The entity columns are covered by tiles of `tw` u32 counters in LDS. Per tile:
 //   count    wave w takes the features w, w + 16, ... of row i and walks X^T's row of each (entered at the tile's start by a lower
-//            bound), adding 1 to cnt[j - t0];
+//            bound), adding 1 to cnt[j - t0]                                                             (sbr_cooc_count_tile, csr_walk.h);
 //   value    every counter c > 0 with j != i is replaced in place by the bits of its similarity (> 0, so the bits order like the
 //            values), everything else by 0;
-//   select   the k largest composites (value bits << 32 | 0xFFFFFFFF - j: value descending, index ascending) among the list carried
-//            from the earlier tiles and this tile's entries, by radix select on the composite (4 passes on the value; 4 more on the
-//            index only when equal values straddle the k-th place), then compaction into the second list buffer.
-// After the last tile the list is sorted (bitonic) and written with its length and the (-1, 0) padding.
+//   select   the k largest composites among the list carried from the earlier tiles and this tile's entries
+//                                                                                                 (sbr_topk_select_tile, cooc_topk.h).
+// After the last tile the list is sorted (bitonic) and written with its length and the (-1, 0) padding (sbr_topk_sort_write).
 __global__ __launch_bounds__(KNN_THREADS) void knn_topk_kernel(const long* __restrict__ indptr, const int* __restrict__ indices,
                                                                 const long* __restrict__ t_indptr, const int* __restrict__ t_indices,
                                                                 int n, int r0, int sim, float alpha, float beta, float shrinkage, int k,
                                                                 int kpad, int tw, int* __restrict__ nbr_idx, float* __restrict__ nbr_val,
                                                                 int* __restrict__ nbr_len) {
   extern __shared__ unsigned int cnt[];
-  __shared__ unsigned long long lists[2][KNN_K_MAX];
-  __shared__ unsigned int hist[256];
-  __shared__ unsigned int s_prefix_hi, s_prefix_lo, s_need, s_take_all, s_done, s_cnt;
+  __shared__ SbrTopkLds<KNN_K_MAX> sel;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int i = r0 + (int)blockIdx.x;
   const long f_beg = indptr[i], f_end = indptr[i + 1];
   const int ni = (int)(f_end - f_beg);
-  int cur = 0;                 // lists[cur]: the list carried so far, n_list entries, unsorted
+  int cur = 0;                 // sel.lists[cur]: the list carried so far, n_list entries, unsorted
   unsigned int n_list = 0;
 
   for (int t0 = 0; t0 < n && ni > 0; t0 += tw) {
@@ -132,100 +91,10 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_topk_kernel(const long* __res
       const int j = t0 + x;
       if (c != 0u) cnt[x] = j == i ? 0u : __float_as_uint(knn_value(sim, c, ni, (int)(indptr[j + 1] - indptr[j]), alpha, beta, shrinkage));
     }
-    if (t == 0) { s_take_all = 0u; s_done = 0u; }
-    __syncthreads();
-    // ---- select: the composite of the k-th largest entry of (carried list, tile)
-    unsigned int pre_hi = 0u, pre_lo = 0u, need = (unsigned int)k;
-    for (int pass = 0; pass < 8; ++pass) {
-      const int shift = 24 - 8 * (pass & 3);
-      const bool on_index = pass >= 4;
-      const unsigned int hi_mask = (pass & 3) == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
-      if (t < 256) hist[t] = 0u;
-      __syncthreads();
-      for (int x = t; x < (int)n_list; x += KNN_THREADS) {
-        const unsigned long long e = lists[cur][x];
-        const unsigned int vb = (unsigned int)(e >> 32), ib = (unsigned int)e;
-        const bool in = on_index ? (vb == pre_hi && (ib & hi_mask) == pre_lo) : ((vb & hi_mask) == pre_hi);
-        if (in) atomicAdd(&hist[((on_index ? ib : vb) >> shift) & 255u], 1u);
-      }
-      for (int x0 = 0; x0 < width; x0 += KNN_THREADS) {
-        const int x = x0 + t;
-        const unsigned int vb = x < width ? cnt[x] : 0u, ib = 0xFFFFFFFFu - (unsigned int)(t0 + x);
-        const bool in = vb != 0u && (on_index ? (vb == pre_hi && (ib & hi_mask) == pre_lo) : ((vb & hi_mask) == pre_hi));
-        knn_hist_add(hist, in, ((on_index ? ib : vb) >> shift) & 255u);
-      }
-      __syncthreads();
-      if (w == 0) {
-        int d = 0;
-        unsigned int above = 0u, own = 0u, total = 0u;
-        const bool mine = knn_find_bin(hist, need, lane, d, above, own, total);
-        if (pass == 0 && total <= (unsigned int)k) {
-          if (lane == 0) s_take_all = 1u;                           // everything fits: no threshold
-        } else if (mine) {                                          // (a bin is always found: the prefix group holds >= need entries)
-          if (on_index) s_prefix_lo = pre_lo | ((unsigned int)d << shift);
-          else { s_prefix_hi = pre_hi | ((unsigned int)d << shift); s_prefix_lo = 0u; }
-          s_need = need - above;
-          // the value is fixed after pass 3: if every entry that has it is needed, the index does not matter
-          if (pass == 3 && own == need - above) s_done = 1u;
-        }
-      }
-      __syncthreads();
-      pre_hi = s_prefix_hi;
-      pre_lo = s_prefix_lo;
-      need = s_need;
-      if (s_take_all || s_done) break;             // uniform: read behind the barrier, written before it
-    }
-    const unsigned long long thr = s_take_all ? 1ull : (((unsigned long long)pre_hi << 32) | (unsigned long long)pre_lo);
-    // ---- compaction of every composite >= thr into the other buffer (the order is fixed by the final sort)
-    if (t == 0) s_cnt = 0u;
-    __syncthreads();
-    const int nxt = cur ^ 1;
-    for (int x = t; x < (int)n_list; x += KNN_THREADS) {
-      const unsigned long long e = lists[cur][x];
-      if (e >= thr) {
-        const unsigned int pos = atomicAdd(&s_cnt, 1u);
-        if (pos < (unsigned int)k) lists[nxt][pos] = e;
-      }
-    }
-    for (int x = t; x < width; x += KNN_THREADS) {
-      const unsigned int vb = cnt[x];
-      if (vb != 0u) {
-        const unsigned long long e = ((unsigned long long)vb << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned int)(t0 + x));
-        if (e >= thr) {
-          const unsigned int pos = atomicAdd(&s_cnt, 1u);
-          if (pos < (unsigned int)k) lists[nxt][pos] = e;             // (pos < k always: the guard keeps a wrong count inside the buffer)
-        }
-      }
-    }
-    __syncthreads();
-    n_list = s_cnt < (unsigned int)k ? s_cnt : (unsigned int)k;
-    cur = nxt;
-    __syncthreads();
+    // ---- select
+    sbr_topk_select_tile<KNN_THREADS>(sel, cnt, width, t0, k, cur, n_list);
   }
-
-  // ---- sort (descending composites; the zero padding sorts last) and write
-  for (int x = (int)n_list + t; x < kpad; x += KNN_THREADS) lists[cur][x] = 0ull;
-  __syncthreads();
-  for (int size = 2; size <= kpad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (t < kpad) {
-        const int j = t ^ stride;
-        if (j > t) {
-          const bool desc = (t & size) == 0;
-          const unsigned long long a = lists[cur][t], b = lists[cur][j];
-          if ((a < b) == desc) { lists[cur][t] = b; lists[cur][j] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (t < k) {
-    const unsigned long long e = lists[cur][t];
-    const bool real = t < (int)n_list;
-    nbr_idx[(long)i * k + t] = real ? (int)(0xFFFFFFFFu - (unsigned int)(e & 0xFFFFFFFFull)) : -1;
-    nbr_val[(long)i * k + t] = real ? __uint_as_float((unsigned int)(e >> 32)) : 0.f;
-  }
-  if (t == 0) nbr_len[i] = (int)n_list;
+  sbr_topk_sort_write<KNN_THREADS>(sel, cur, n_list, k, kpad, i, nbr_idx, nbr_val, nbr_len);
 }
 
 extern "C" int sbr_knn_topk(const long* indptr, const int* indices, const long* t_indptr, const int* t_indices, int n, int m, int r0,
@@ -237,7 +106,7 @@ extern "C" int sbr_knn_topk(const long* indptr, const int* indices, const long* 
   SBR_REQUIRE(alpha >= 0.f && beta >= 0.f, "sbr_knn_topk: negative alpha / beta (%g, %g)", (double)alpha, (double)beta);
   SBR_REQUIRE(n >= 0 && m >= 0 && m <= KNN_M_MAX, "sbr_knn_topk: shape [%d, %d] outside [0, 2^31) x [0, 2^24]", n, m);
   SBR_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= n, "sbr_knn_topk: row range [%d, %d) outside [0, %d]", r0, r1, n);
-  const long fixed = 2L * KNN_K_MAX * 8 + 256 * 4 + 64;         // the kernel's static LDS: two lists, the histogram, the scalars
+  const long fixed = (long)sizeof(SbrTopkLds<KNN_K_MAX>) + 40;   // the kernel's static LDS: two lists, the histogram, the scalars
   static SbrLdsSlot lds_slot;
   const int tw = sbr_row_tile("sbr_knn_topk", (const void*)knn_topk_kernel, &lds_slot, n, tile_cols, fixed, r1 - r0,
                               indptr && indices && t_indptr && t_indices && nbr_idx && nbr_val && nbr_len);

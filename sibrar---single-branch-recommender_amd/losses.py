@@ -81,11 +81,21 @@ class RecAlignmentLoss(RecommenderSystemLoss):
         return total / n_pos
 
 
+class RecNoLoss(RecommenderSystemLoss):
+    """``rec_loss: none``: a zero scalar on the logits' device, for a model that owns its whole objective and hands it over through
+    ``get_and_reset_other_loss`` (``UltraGCN``: its training ``forward`` returns detached scores, and ``train/reg_loss`` is the loss).
+    The loader's ``n_negative_samples`` still decides how many negatives the model sees. Not part of the reference."""
+
+    def compute_loss(self, logits, labels):
+        return torch.zeros((), device=logits.device, dtype=torch.float32)
+
+
 class RecommenderSystemLossesEnum(Enum):
     bce = RecBinaryCrossEntropy
     bpr = RecBayesianPersonalizedRankingLoss
     sampled_softmax = RecSampledSoftmaxLoss
     align = RecAlignmentLoss
+    none = RecNoLoss
 
 
 class InfoNCE(nn.Module):

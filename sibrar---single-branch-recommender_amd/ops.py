@@ -1862,6 +1862,139 @@ class AlignLossFn(Function):
         return d, None, None
 
 
+# ---- UltraGCN (csrc/ultragcn.hip) --------------------------------------------------------------------------------------------------------
+COOC_MAX_K = 64                   # the longest list of sbr_cooc_weight_topk, and the most neighbour slots of the fused loss
+ULTRAGCN_MAX_D = 256
+
+
+def _f32_vec(who, name, t, n):
+    if t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f'{who}: {name} must be a contiguous float32 [{n}], got {t.dtype} {tuple(t.shape)}')
+    return t
+
+
+def cooc_weight_topk(csr, row_scale: torch.Tensor, col_scale: torch.Tensor, k: int, include_self: bool = True, rows=None,
+                     tile_cols: int = 0):
+    """The ``k`` heaviest co-occurrence partners of every COLUMN (item) of a binary resident ``features.DeviceCSR`` X [n, m]: with
+    ``G = X^T X`` the value of the pair (i, j), ``G_ij > 0``, is ``(float(G_ij) * row_scale[i]) * col_scale[j]`` in float32
+    (``sbr_cooc_weight_topk`` with X^T as its matrix) -> ``(idx int32 [m, k], val float32 [m, k], len int32 [m])``, every list sorted by
+    (value descending, index ascending), (-1, 0) behind its length. ``include_self``: item i is a candidate of its own list.
+    ``rows=(r0, r1)`` computes that range of items only (the others come back empty): the same bits as the whole. 1 <= k <= 64. Nothing
+    of size m x m exists; integer atomics only."""
+    _need_cuda(csr.indptr, row_scale, col_scale)
+    if csr.data is not None:
+        raise ValueError('cooc_weight_topk: co-occurrence counts are stated for 0/1 data; this matrix has values')
+    n, m = csr.shape
+    dev = csr.indptr.device
+    _f32_vec('cooc_weight_topk', 'row_scale', row_scale, m)
+    _f32_vec('cooc_weight_topk', 'col_scale', col_scale, m)
+    r0, r1, whole = _row_range(rows, m)
+    t_indptr, t_indices, _ = csr.transposed()
+    idx = (torch.empty if whole else partial(torch.full, fill_value=-1))((m, k), device=dev, dtype=torch.int32)
+    val = (torch.empty if whole else torch.zeros)((m, k), device=dev, dtype=torch.float32)
+    length = (torch.empty if whole else torch.zeros)((m,), device=dev, dtype=torch.int32)
+    # the items are the rows of X^T: X^T is the entry's matrix, X its transpose
+    call('sbr_cooc_weight_topk', ptr(t_indptr), ptr(t_indices), ptr(csr.indptr), ptr(csr.indices), m, n, r0, r1, ptr(row_scale), ptr(col_scale),
+         1 if include_self else 0, int(k), int(tile_cols), ptr(idx), ptr(val), ptr(length), stream())
+    return idx, val, length
+
+
+def ultragcn_scales(csr):
+    """UltraGCN's degree vectors of the binary resident users x items matrix X, on its device, nothing read back:
+    ``(beta_u [n_users], beta_i [n_items], row_scale [n_items], col_scale [n_items])`` float32 with ``beta_u = sqrt(d_u + 1) / d_u`` (0 where
+    ``d_u = 0``), ``beta_i = 1 / sqrt(d_i + 1)``, ``row_scale = sqrt(g + 1) / g`` (0 where ``g = 0``), ``col_scale = 1 / sqrt(g + 1)`` and
+    ``g_i = sum over the users u of item i of d_u``, the row sums of ``X^T X``. The degrees and g are exact integers (row lengths; one
+    int64 prefix sum over X^T's entries); each scale is evaluated in float64 and rounded to float32 once."""
+    _need_cuda(csr.indptr)
+    t_indptr, t_indices, _ = csr.transposed()
+    d_u = csr.indptr[1:] - csr.indptr[:-1]
+    d_i = t_indptr[1:] - t_indptr[:-1]
+    run = torch.zeros(t_indices.numel() + 1, device=d_u.device, dtype=torch.int64)
+    run[1:] = torch.cumsum(d_u[t_indices.long()], 0)
+    g = run[t_indptr[1:]] - run[t_indptr[:-1]]
+
+    def up(x):                    # sqrt(x + 1) / x, 0 where x = 0
+        xd = x.double()
+        return torch.where(x > 0, torch.sqrt(xd + 1) / xd.clamp(min=1), torch.zeros_like(xd)).float()
+
+    def down(x):                  # 1 / sqrt(x + 1)
+        return (1 / torch.sqrt(x.double() + 1)).float()
+
+    return up(d_u), down(d_i), up(g), down(g)
+
+
+def _ultragcn_operands(Ub, V, u_idxs, i_idxs, beta_u, beta_i, nbr_idx, nbr_val, nbr_len):
+    who = 'UltraGCNLossFn'
+    _need_cuda(Ub, V, u_idxs, i_idxs, beta_u, beta_i, nbr_idx, nbr_val, nbr_len)
+    if V.dim() != 2 or V.dtype != torch.float32 or not V.is_contiguous():
+        raise ValueError(f'{who}: the item table must be a contiguous float32 matrix [n_items, D] (its rows are read in place), got '
+                         f'{V.dtype} {tuple(V.shape)} strides {V.stride()}')
+    n_items, D = int(V.shape[0]), int(V.shape[1])
+    if i_idxs.dim() != 2 or u_idxs.dim() != 1 or u_idxs.shape[0] != i_idxs.shape[0] or tuple(Ub.shape) != (u_idxs.shape[0], D):
+        raise ValueError(f'{who}: needs u_idxs [B], i_idxs [B, 1 + N] and Ub [B, {D}], got {tuple(u_idxs.shape)}, {tuple(i_idxs.shape)} and '
+                         f'{tuple(Ub.shape)}')
+    B, N = int(i_idxs.shape[0]), int(i_idxs.shape[1]) - 1
+    if nbr_idx.dim() != 2 or nbr_idx.shape[0] != n_items or nbr_val.shape != nbr_idx.shape or tuple(nbr_len.shape) != (n_items,) \
+            or nbr_idx.dtype != torch.int32 or nbr_len.dtype != torch.int32 or nbr_val.dtype != torch.float32 \
+            or not (nbr_idx.is_contiguous() and nbr_val.is_contiguous() and nbr_len.is_contiguous()):
+        raise ValueError(f'{who}: the neighbour lists must be contiguous (int32 [{n_items}, K], float32 [{n_items}, K], int32 [{n_items}])')
+    _f32_vec(who, 'beta_i', beta_i, n_items)
+    _f32_vec(who, 'beta_u', beta_u, beta_u.shape[0] if beta_u.dim() == 1 else -1)
+    return (_f32c(Ub), V, u_idxs.to(torch.int32).contiguous(), i_idxs.to(torch.int32).contiguous(), B, D, N, int(nbr_idx.shape[1]),
+            int(beta_u.shape[0]), n_items)
+
+
+class UltraGCNLossFn(Function):
+    """UltraGCN's objective on a batch (Mao et al., CIKM 2021) -> ``(loss, parts [3], scores [B, 1 + N])``: ``loss = pos +
+    negative_weight * neg + lam * nbr`` summed over the batch, ``parts = (pos, neg, nbr)`` and the dot products of the sampled slots, the
+    last two without a gradient. ``Ub`` [B, D]: the users' rows (``LookupFn``: the user table's gradient takes the existing path); ``V``
+    [n_items, D]: the item table itself, contiguous, read in place; ``i_idxs`` [B, 1 + N] with the positive in column 0; ``beta_u`` /
+    ``beta_i`` and the lists of ``cooc_weight_topk`` as in include/sibrar_hip.h. The forward pass is one call of
+    ``sbr_ultragcn_loss_fwd_bwd``, which also leaves dL/dUb and the coefficients dL/ds [B, 1 + N + K]; no [B, 1 + N + K, D] copy of item
+    rows or of their gradient exists. The backward pass scales dL/dUb and gathers the item table's gradient from the coefficients
+    (``sbr_scatter_add_scaled_rows_sorted`` behind a stable sort of the slots' item indices, padded slots under a sentinel key; the
+    upstream scalar is read on the device). Fixed order, no atomics: the only form, valid in deterministic mode. 1 <= D <= 256, N >= 1,
+    1 <= K <= 64."""
+
+    @staticmethod
+    def forward(ctx, Ub, V, u_idxs, i_idxs, beta_u, beta_i, nbr_idx, nbr_val, nbr_len, w1, w2, w3, w4, negative_weight, lam):
+        Ub, V, u32, i32, B, D, N, K, n_users, n_items = _ultragcn_operands(Ub.detach(), V.detach(), u_idxs, i_idxs, beta_u, beta_i, nbr_idx,
+                                                                            nbr_val, nbr_len)
+        dev = V.device
+        parts = torch.empty(4, device=dev, dtype=torch.float32)
+        dUb = torch.empty(B, D, device=dev, dtype=torch.float32)
+        coef = torch.empty(B, 1 + max(N, 0) + K, device=dev, dtype=torch.float32)
+        scores = torch.empty(B, 1 + max(N, 0), device=dev, dtype=torch.float32)
+        ws, ws_bytes = _entry_ws(dev, 'sbr_ultragcn_loss', B, dtype=torch.float64)
+        call('sbr_ultragcn_loss_fwd_bwd', ptr(Ub), ptr(V), ptr(u32), ptr(i32), ptr(beta_u), ptr(beta_i), ptr(nbr_idx), ptr(nbr_val),
+             ptr(nbr_len), B, D, N, K, n_users, n_items, float(w1), float(w2), float(w3), float(w4), float(negative_weight), float(lam),
+             ptr(parts), ptr(dUb), ptr(coef), ptr(scores), ws, ws_bytes, stream())
+        ctx.save_for_backward(Ub, dUb, coef, i32, nbr_idx)
+        ctx.v_shape = (n_items, D)
+        loss, three = parts[3].clone(), parts[:3].clone()
+        ctx.mark_non_differentiable(three, scores)
+        return loss, three, scores
+
+    @staticmethod
+    def backward(ctx, g, _g_parts, _g_scores):
+        Ub, dUb, coef, i32, nbr_idx = ctx.saved_tensors
+        n_items, D = ctx.v_shape
+        g = g.reshape(1).to(torch.float32).contiguous()
+        d_ub = dUb * g if ctx.needs_input_grad[0] else None
+        dV = None
+        if ctx.needs_input_grad[1]:
+            dV = torch.zeros(n_items, D, device=coef.device, dtype=torch.float32)
+            if coef.numel() > 0:
+                # the slots' keys: the item each slot names; padded neighbour slots (-1) and indices outside the table take the sentinel
+                p = i32[:, 0].long().clamp(0, max(n_items - 1, 0))
+                keys = torch.cat([i32, nbr_idx[p]], dim=1).reshape(-1)
+                keys = torch.where((keys < 0) | (keys >= n_items), torch.full_like(keys, n_items), keys)
+                skeys, order = torch.sort(keys, stable=True)
+                call('sbr_scatter_add_scaled_rows_sorted', ptr(coef), ptr(Ub), ptr(skeys), ptr(order), keys.numel(), coef.shape[1], ptr(g),
+                     ptr(dV), n_items, D, stream())
+        return (d_ub, dV) + (None,) * 13
+
+
 # ---- implicit-feedback ALS (csrc/als.hip) -------------------------------------------------------------------------------------------
 def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
     """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a
