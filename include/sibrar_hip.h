@@ -1181,6 +1181,50 @@ int sbr_ultragcn_loss_fwd_bwd(const float* Ub, const float* V, const int* u_idxs
 int sbr_scatter_add_scaled_rows_sorted(const float* coef, const float* src, const int* sorted_keys, const long* order, long n_slots,
                                        int slots_per_row, const float* grad, float* dst, int n_rows, int D, void* stream);
 
+/* ---- SimpleX (csrc/simplex.hip) ---------------------------------------------------------------------------------------------------
+ * Mao et al., CIKM 2021; the reference has no such model. The definitions are the authors' code as remembered.
+ *
+ * sbr_ccl_loss_fwd_bwd: the cosine contrastive loss of a batch, its gradient by the user representations and the two coefficient
+ * arrays that carry the item table's gradient, in one pass. H fp32 [B, D]: the user representations (contiguous). V fp32 [n_items, D]:
+ * the item table, contiguous, row j at (long)j * D, read in place. i_idxs int32 [B, 1 + N]: the positive in column 0, N negatives
+ * behind it. The row belongs to a group of G lanes, the geometry of sbr_ultragcn_loss_fwd_bwd: 4 columns per chunk when D % 4 == 0 (H, V,
+ * dH must then start on a 16-byte boundary), else 1; G = the smallest power of two with G * (4 or 1) >= D, 64 at the most; lane l owns
+ * the chunks l, l + G, ... . Every dot product is the lane's fmaf chain over its columns in ascending order from +0, then an xor
+ * butterfly over the group from offset G / 2 down to 1. Every operation below is one rounded fp32 operation in the order written
+ * (sqrtf and the divisions correctly rounded, nothing contracted):
+ *   hh = <H[b], H[b]>   rh = sqrtf(hh)   nh = max(rh, eps)
+ *   per slot c, item j = i_idxs[b, c], H[b] in registers and V[j] read once:
+ *     s = <H[b], V[j]>   vv = <V[j], V[j]>   rv = sqrtf(vv)   nv = max(rv, eps)   den = nh * nv   y = s / den
+ *     c = 0    term = 1 - y                 g = -fl(1 / B)
+ *     c >= 1   term = max(y - margin, 0)    g = y > margin ? fl(fl(negative_weight / N) * fl(1 / B)) : +0      (strictly above)
+ *     g == 0:  coef_a = coef_s = +0
+ *     else     coef_a = g / den   gy = g * y   sgy = sgy + gy (from +0, ascending c)   coef_s = rv < eps ? +0 : -(gy / (nv * nv))
+ *   dH[b, d] = fmaf(-k, H[b, d], A[d])   A[d] = one fmaf chain from +0 of coef_a * V[j][d] over the slots in ascending c
+ *                                        k = rh < eps ? +0 : sgy / (nh * nh)             (the clamp has no gradient)
+ * A slot whose index lies outside [0, n_items) reads no table row (an index of -1 never addresses the table), has y = 0, both
+ * coefficients +0 and adds no term. The terms of a row are added in double in ascending c, the positive's and the negatives' apart;
+ * the negatives' sum is divided by N. The rows' partials (workspace: 16 B bytes, sbr_ccl_loss_workspace) are folded in double by a
+ * second, one-wave launch: lane l adds the rows l, l + 64, ... in ascending order, then an xor butterfly from offset 32 down to 1.
+ * All orders are functions of (B, D, N) alone. parts fp32 [3] = (pos / B, neg / B, (pos + negative_weight * neg) / B), each rounded
+ * once; dH fp32 [B, D]; coef_a, coef_s fp32 [B, 1 + N]: dL/dV[j] = sum over the slots that name j of coef_a * H[b] + coef_s * V[j];
+ * scores fp32 [B, 1 + N] = y (may be NULL). 1 <= D <= 256, N >= 1, B (1 + N) < 2^31, eps > 0. No atomics: valid in deterministic
+ * mode. New (additive to ABI 4). */
+long sbr_ccl_loss_workspace(int B);
+int sbr_ccl_loss_fwd_bwd(const float* H, const float* V, const int* i_idxs, int B, int D, int N, int n_items, float margin,
+                         float negative_weight, float eps, float* parts, float* dH, float* coef_a, float* coef_s, float* scores,
+                         void* workspace, long workspace_bytes, void* stream);
+/* sbr_scatter_add_cos_rows_sorted: dst[j, d] += grad[0] * (S_j[d] + T_j * V[j, d]) for every row j of dst fp32 [n_rows, D] (contiguous)
+ * that a slot names. S_j[d] = the fmaf chain from +0 of coef_a[pos] * src[pos / slots_per_row, d] over the slot positions pos whose key
+ * is j, in ascending pos; T_j = the sum from +0 of coef_s[pos] over the same positions in the same order (T = T + coef_s[pos]); then
+ * r = fmaf(T_j, V[j, d], S_j[d]), t = grad[0] * r, dst[j, d] = dst[j, d] + t, one rounding each. sorted_keys, order, the sentinel key
+ * of a padded slot, grad, the wave per row and the one writer per row are those of sbr_scatter_add_scaled_rows_sorted, whose segment
+ * search and row walk this entry shares (csrc/slot_rows.h). coef_a, coef_s fp32 [n_slots]; src fp32 [n_slots / slots_per_row, D];
+ * V fp32 [n_rows, D] contiguous; rows that no slot names are not touched. 1 <= D <= 256, n_slots < 2^31. The only form: valid in
+ * deterministic mode. SimpleX's item-table gradient: keys = the slots' item indices, src = H. New (additive to ABI 4). */
+int sbr_scatter_add_cos_rows_sorted(const float* coef_a, const float* coef_s, const float* src, const float* V, const int* sorted_keys,
+                                    const long* order, long n_slots, int slots_per_row, const float* grad, float* dst, int n_rows, int D,
+                                    void* stream);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

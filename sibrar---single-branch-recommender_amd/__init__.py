@@ -31,6 +31,7 @@ from .recvae import RecVAE                                                      
 from .directau import DirectAU                                                              # noqa: F401
 from .simgcl import SimGCL, XSimGCL                                                         # noqa: F401
 from .ultragcn import UltraGCN                                                              # noqa: F401
+from .simplex import SimpleX                                                                # noqa: F401
 from .als import AlternatingLeastSquare                                                     # noqa: F401
 from .svd import SVDAlgorithm                                                               # noqa: F401
 from .rbmf import RBMF                                                                      # noqa: F401
@@ -63,7 +64,7 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
 # .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .slim / .p3alpha / .als / .svd / .rbmf / .pop / .rand -> class
-# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae', 'multdae', 'recvae', 'directau', 'simgcl', 'xsimgcl' and 'ultragcn' are this package's own: the reference has
+# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae', 'multdae', 'recvae', 'directau', 'simgcl', 'xsimgcl', 'ultragcn' and 'simplex' are this package's own: the reference has
 # no trained graph model, no autoencoder over the interaction row, no model trained on alignment and uniformity and no contrastive one
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
@@ -71,4 +72,4 @@ ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixF
               'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ifknn': ItemFeatureKNN, 'ease': EASE,
               'slim': SLIM, 'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF,
               'pop': PopularItems, 'rand': RandomItems, 'lightgcn': LightGCN, 'multvae': MultVAE, 'multdae': MultDAE, 'recvae': RecVAE,
-              'directau': DirectAU, 'simgcl': SimGCL, 'xsimgcl': XSimGCL, 'ultragcn': UltraGCN}
+              'directau': DirectAU, 'simgcl': SimGCL, 'xsimgcl': XSimGCL, 'ultragcn': UltraGCN, 'simplex': SimpleX}

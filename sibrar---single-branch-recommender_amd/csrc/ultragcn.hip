@@ -10,6 +10,7 @@
 #include "common.h"
 #include "csr_walk.h"
 #include "cooc_topk.h"
+#include "slot_rows.h"
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // neighbour lists
@@ -83,19 +84,6 @@ extern "C" int sbr_cooc_weight_topk(const long* indptr, const int* indices, cons
 #define UG_K_MAX 64
 #define UG_UNROLL 4                  // item rows in flight per lane group (the additions stay in slot order)
 
-template <int V> struct UgVec;
-template <> struct UgVec<4> {
-  static __device__ __forceinline__ void load(const float* p, float* v) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-  static __device__ __forceinline__ void store(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct UgVec<1> {
-  static __device__ __forceinline__ void load(const float* p, float* v) { v[0] = *p; }
-  static __device__ __forceinline__ void store(float* p, const float* v) { *p = v[0]; }
-};
-
 struct UgScalars {
   float w1, w2, w3, w4, neg_coef, lam;     // neg_coef = negative_weight / N, rounded once on the host side of the launch
 };
@@ -137,7 +125,7 @@ __global__ __launch_bounds__(64) void ultragcn_loss_kernel(const float* __restri
     const int col = (gl + k * G) * V;
 #pragma unroll
     for (int j = 0; j < V; ++j) { ub[k][j] = 0.f; acc[k][j] = 0.f; }
-    if (col < D) UgVec<V>::load(Ub + b * D + col, ub[k]);
+    if (col < D) SbrRowChunk<V>::load(Ub + b * D + col, ub[k]);
   }
   const int u = u_idxs[b];
   const float bu = (unsigned int)u < (unsigned int)n_users ? beta_u[u] : 0.f;
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(64) void ultragcn_loss_kernel(const float* __restri
 #pragma unroll
             for (int k = 0; k < C; ++k) {
               const int col = (gl + k * G) * V;
-              if (col < D) UgVec<V>::load(vr + col, v[q][k]);
+              if (col < D) SbrRowChunk<V>::load(vr + col, v[q][k]);
             }
           }
         }
@@ -227,7 +215,7 @@ __global__ __launch_bounds__(64) void ultragcn_loss_kernel(const float* __restri
 #pragma unroll
   for (int k = 0; k < C; ++k) {
     const int col = (gl + k * G) * V;
-    if (col < D) UgVec<V>::store(dUb + b * D + col, acc[k]);
+    if (col < D) SbrRowChunk<V>::store(dUb + b * D + col, acc[k]);
   }
   if (gl == 0) {
     row_parts[3 * b] = part[0];
@@ -282,16 +270,14 @@ extern "C" int sbr_ultragcn_loss_fwd_bwd(const float* Ub, const float* V, const 
               sbr_ultragcn_loss_workspace(B));
   SBR_REQUIRE(B == 0 || (Ub && V && u_idxs && i_idxs && beta_u && beta_i && nbr_idx && nbr_val && nbr_len && dUb && coef && workspace),
               "%s: null operand", who);
-  const bool vec = D % 4 == 0;
+  const SbrLaneGroup lg = sbr_lane_group(D);
+  const bool vec = lg.vec;
+  const int gshift = lg.gshift, per_lane = lg.per_lane;
   SBR_REQUIRE(!vec || ((uintptr_t)Ub | (uintptr_t)V | (uintptr_t)dUb) % 16 == 0, "%s: D=%d is read in 16-byte chunks: Ub, V and dUb must "
               "start on a 16-byte boundary", who, D);
   SBR_REQUIRE((uintptr_t)workspace % 8 == 0, "%s: the workspace must start on an 8-byte boundary", who);
   hipStream_t st = (hipStream_t)stream;
   if (B > 0) {
-    const int chunks = vec ? D / 4 : D;
-    int gshift = 0;
-    while (gshift < 6 && (1 << gshift) < chunks) ++gshift;
-    const int per_lane = (chunks + (1 << gshift) - 1) >> gshift;
     UgScalars sc;
     sc.w1 = w1; sc.w2 = w2; sc.w3 = w3; sc.w4 = w4; sc.lam = lam;
     sc.neg_coef = negative_weight / (float)N;
@@ -310,60 +296,28 @@ extern "C" int sbr_ultragcn_loss_fwd_bwd(const float* Ub, const float* V, const 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // the item-side gradient
 // ---------------------------------------------------------------------------------------------------------------------------------------
-#define SS_WAVES 4
-#define SS_D_MAX 256
-
 // One wave per row j of dst. sorted_keys [n_slots] ascending: the wave finds its segment [lo, hi) by two binary searches (a row that no
 // slot names is left alone; a key outside [0, n_rows) — the sentinel of a padded slot — is looked for by nobody). It reads the
 // segment's slot positions order[q] 64 at a time, one per lane, and takes them in ascending q: lane l owns the columns l, l + 64, ...
 // and adds acc = fmaf(coef[order[q]], src[order[q] / slots_per_row][col], acc) from +0; then dst[j][col] += grad[0] * acc (one rounded
 // multiplication, one rounded addition). A position outside [0, n_slots) is skipped.
-__global__ __launch_bounds__(64 * SS_WAVES) void scatter_scaled_sorted_kernel(const float* __restrict__ coef, const float* __restrict__ src,
+__global__ __launch_bounds__(64 * SBR_SORTED_WAVES) void scatter_scaled_sorted_kernel(const float* __restrict__ coef, const float* __restrict__ src,
                                                                               const int* __restrict__ sorted_keys,
                                                                               const long* __restrict__ order, long n_slots,
                                                                               int slots_per_row, const float* __restrict__ grad,
                                                                               float* __restrict__ dst, int n_rows, int D) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
-  const long j = (long)blockIdx.x * SS_WAVES + (threadIdx.x >> 6);
+  const long j = (long)blockIdx.x * SBR_SORTED_WAVES + (threadIdx.x >> 6);
   if (j >= n_rows) return;
-  long lo = 0, hi = n_slots;
-  while (lo < hi) {                                               // the first position whose key is >= j
-    const long mid = (lo + hi) >> 1;
-    if (sorted_keys[mid] < (int)j) lo = mid + 1; else hi = mid;
-  }
-  const long beg = lo;
-  hi = n_slots;
-  while (lo < hi) {                                               // the first position whose key is > j
-    const long mid = (lo + hi) >> 1;
-    if (sorted_keys[mid] <= (int)j) lo = mid + 1; else hi = mid;
-  }
-  const long end = lo;
+  long beg, end;
+  sbr_sorted_segment(sorted_keys, n_slots, (int)j, beg, end);
   if (beg == end) return;
-  float acc[SS_D_MAX / 64] = {0.f, 0.f, 0.f, 0.f};
-  for (long q0 = beg; q0 < end; q0 += 64) {
-    const int n_e = end - q0 < 64 ? (int)(end - q0) : 64;
-    long my_row = -1;
-    float my_c = 0.f;
-    if (lane < n_e) {
-      const long pos = order[q0 + lane];
-      if (pos >= 0 && pos < n_slots) { my_row = pos / slots_per_row; my_c = coef[pos]; }
-    }
-    for (int e = 0; e < n_e; ++e) {
-      const long row = __shfl(my_row, e, 64);
-      const float c = __shfl(my_c, e, 64);
-      if (row < 0) continue;
-      const float* sr = src + row * D;
-#pragma unroll
-      for (int k = 0; k < SS_D_MAX / 64; ++k) {
-        const int col = lane + 64 * k;
-        if (col < D) acc[k] = fmaf(c, sr[col], acc[k]);
-      }
-    }
-  }
+  float acc[SBR_SORTED_D_MAX / 64] = {0.f, 0.f, 0.f, 0.f}, unused = 0.f;
+  sbr_sorted_row_walk<false>(coef, nullptr, src, order, beg, end, n_slots, slots_per_row, D, lane, acc, unused);
   const float g = grad[0];
 #pragma unroll
-  for (int k = 0; k < SS_D_MAX / 64; ++k) {
+  for (int k = 0; k < SBR_SORTED_D_MAX / 64; ++k) {
     const int col = lane + 64 * k;
     if (col < D) {
       const float t = g * acc[k];
@@ -375,13 +329,13 @@ __global__ __launch_bounds__(64 * SS_WAVES) void scatter_scaled_sorted_kernel(co
 extern "C" int sbr_scatter_add_scaled_rows_sorted(const float* coef, const float* src, const int* sorted_keys, const long* order, long n_slots,
                                                   int slots_per_row, const float* grad, float* dst, int n_rows, int D, void* stream) {
   const char* who = "sbr_scatter_add_scaled_rows_sorted";
-  SBR_REQUIRE(D >= 1 && D <= SS_D_MAX, "%s: D=%d outside [1, %d]", who, D, SS_D_MAX);
+  SBR_REQUIRE(D >= 1 && D <= SBR_SORTED_D_MAX, "%s: D=%d outside [1, %d]", who, D, SBR_SORTED_D_MAX);
   SBR_REQUIRE(n_slots >= 0 && n_slots <= 0x7FFFFFFFL && slots_per_row >= 1 && n_rows >= 0, "%s: bad shape (n_slots=%ld, slots_per_row=%d, "
               "n_rows=%d)", who, n_slots, slots_per_row, n_rows);
   SBR_REQUIRE(n_slots % slots_per_row == 0, "%s: %ld slots are no whole number of rows of %d", who, n_slots, slots_per_row);
   if (n_slots == 0 || n_rows == 0) return SBR_OK;
   SBR_REQUIRE(coef && src && sorted_keys && order && grad && dst, "%s: null operand", who);
-  scatter_scaled_sorted_kernel<<<(unsigned)((n_rows + SS_WAVES - 1) / SS_WAVES), 64 * SS_WAVES, 0, (hipStream_t)stream>>>(
+  scatter_scaled_sorted_kernel<<<(unsigned)((n_rows + SBR_SORTED_WAVES - 1) / SBR_SORTED_WAVES), 64 * SBR_SORTED_WAVES, 0, (hipStream_t)stream>>>(
       coef, src, sorted_keys, order, n_slots, slots_per_row, grad, dst, n_rows, D);
   SBR_CHECK_LAUNCH(who);
   return SBR_OK;

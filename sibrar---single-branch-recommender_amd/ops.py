@@ -1995,6 +1995,69 @@ class UltraGCNLossFn(Function):
         return (d_ub, dV) + (None,) * 13
 
 
+# ---- SimpleX (csrc/simplex.hip) -----------------------------------------------------------------------------------------------------------
+CCL_MAX_D = 256
+
+
+def _ccl_operands(H, V, i_idxs):
+    who = 'CCLLossFn'
+    _need_cuda(H, V, i_idxs)
+    if V.dim() != 2 or V.dtype != torch.float32 or not V.is_contiguous():
+        raise ValueError(f'{who}: the item table must be a contiguous float32 matrix [n_items, D] (its rows are read in place), got '
+                         f'{V.dtype} {tuple(V.shape)} strides {V.stride()}')
+    n_items, D = int(V.shape[0]), int(V.shape[1])
+    if i_idxs.dim() != 2 or H.dim() != 2 or tuple(H.shape) != (i_idxs.shape[0], D):
+        raise ValueError(f'{who}: needs i_idxs [B, 1 + N] and H [B, {D}], got {tuple(i_idxs.shape)} and {tuple(H.shape)}')
+    return _f32c(H), V, i_idxs.to(torch.int32).contiguous(), int(i_idxs.shape[0]), D, int(i_idxs.shape[1]) - 1, n_items
+
+
+class CCLLossFn(Function):
+    """SimpleX's cosine contrastive loss on a batch (Mao et al., CIKM 2021) -> ``(loss, parts [2], scores [B, 1 + N])``: with ``y`` the
+    cosine of ``H[b]`` and an item row (norms clamped at ``COS_EPS``), ``loss = mean_b ((1 - y(b, p)) + (negative_weight / N) sum_c
+    max(0, y(b, j_c) - margin))``, ``parts = (mean positive term, mean negative term)`` and the cosines of the sampled slots, the last
+    two without a gradient. ``H`` [B, D]: the user representations; ``V`` [n_items, D]: the item table itself, contiguous, read in
+    place; ``i_idxs`` [B, 1 + N] with the positive in column 0. The forward pass is one call of ``sbr_ccl_loss_fwd_bwd``, which also
+    leaves dL/dH and the two coefficient arrays [B, 1 + N] of the item table's gradient (include/sibrar_hip.h); no [B, 1 + N, D] copy
+    of item rows or of their gradient exists. The backward pass scales dL/dH and gathers the item table's gradient from the
+    coefficients (``sbr_scatter_add_cos_rows_sorted`` behind a stable sort of the slots' item indices, indices outside the table under
+    a sentinel key; the upstream scalar is read on the device). Fixed order, no atomics: the only form, valid in deterministic mode.
+    1 <= D <= 256, N >= 1."""
+
+    @staticmethod
+    def forward(ctx, H, V, i_idxs, margin, negative_weight):
+        H, V, i32, B, D, N, n_items = _ccl_operands(H.detach(), V.detach(), i_idxs)
+        dev = V.device
+        parts = torch.empty(3, device=dev, dtype=torch.float32)
+        dH = torch.empty(B, D, device=dev, dtype=torch.float32)
+        coef_a = torch.empty(B, 1 + max(N, 0), device=dev, dtype=torch.float32)
+        coef_s = torch.empty_like(coef_a)
+        scores = torch.empty_like(coef_a)
+        ws, ws_bytes = _entry_ws(dev, 'sbr_ccl_loss', B, dtype=torch.float64)
+        call('sbr_ccl_loss_fwd_bwd', ptr(H), ptr(V), ptr(i32), B, D, N, n_items, float(margin), float(negative_weight), COS_EPS, ptr(parts),
+             ptr(dH), ptr(coef_a), ptr(coef_s), ptr(scores), ws, ws_bytes, stream())
+        ctx.save_for_backward(H, V, dH, coef_a, coef_s, i32)
+        loss, two = parts[2].clone(), parts[:2].clone()
+        ctx.mark_non_differentiable(two, scores)
+        return loss, two, scores
+
+    @staticmethod
+    def backward(ctx, g, _g_parts, _g_scores):
+        H, V, dH, coef_a, coef_s, i32 = ctx.saved_tensors
+        n_items, D = V.shape
+        g = g.reshape(1).to(torch.float32).contiguous()
+        d_h = dH * g if ctx.needs_input_grad[0] else None
+        dV = None
+        if ctx.needs_input_grad[1]:
+            dV = torch.zeros(n_items, D, device=V.device, dtype=torch.float32)
+            if coef_a.numel() > 0:
+                keys = i32.reshape(-1)                            # the item each slot names; indices outside the table take the sentinel
+                keys = torch.where((keys < 0) | (keys >= n_items), torch.full_like(keys, n_items), keys)
+                skeys, order = torch.sort(keys, stable=True)
+                call('sbr_scatter_add_cos_rows_sorted', ptr(coef_a), ptr(coef_s), ptr(H), ptr(V), ptr(skeys), ptr(order), keys.numel(),
+                     coef_a.shape[1], ptr(g), ptr(dV), n_items, D, stream())
+        return d_h, dV, None, None, None
+
+
 # ---- implicit-feedback ALS (csrc/als.hip) -------------------------------------------------------------------------------------------
 def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
     """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a
