@@ -1225,6 +1225,38 @@ int sbr_scatter_add_cos_rows_sorted(const float* coef_a, const float* coef_s, co
                                     const long* order, long n_slots, int slots_per_row, const float* grad, float* dst, int n_rows, int D,
                                     void* stream);
 
+/* ---- NeuMF (csrc/neumf.hip) --------------------------------------------------------------------------------------------------------
+ * He et al., "Neural Collaborative Filtering", WWW 2017; the reference has no such model. The definitions are the paper as remembered
+ * (DESIGN.md §4.36).
+ *
+ * sbr_neumf_score_all: the MLP term of every (user, item) pair without the [Bu, I, H1] activation. The first layer is separable, so it
+ * arrives split by side: A fp32 [Bu, H1] = W1u pm_u + b1 (row u at (long)u * stride_a), Bt fp32 [I, H1] = W1i qm_i (row i at
+ * (long)i * stride_b). tail fp32 [tail_len]: the packed rest of the network for the widths (h1 .. h_L), L = n_layers, unused widths
+ * ignored: W_2 .. W_L row-major [H_l, H_{l-1}], then b_2 .. b_L, then w_h [H_L], then c; tail_len must be exactly that many floats.
+ * Per pair, every operation one rounded fp32 operation in the order written, nothing contracted:
+ *   z_1[k] = relu(A[u, k] + Bt[i, k])
+ *   z_l[j] = relu(t),  t = b_l[j];  t = fmaf(W_l[j, k], z_{l-1}[k], t) for k = 0, 1, ... ascending               l = 2 .. L
+ *   m      = t,        t = +0;      t = fmaf(w_h[k], z_L[k], t)        for k = 0, 1, ... ascending
+ *   s      = m + c
+ *   out[u, i] = accumulate ? out[u, i] + s : s                    out fp32 [Bu, I], row u at (long)u * stride_o
+ * relu(x) = x < 0 ? 0 : x (a NaN stays a NaN). Each chain runs on to the next multiple of 4 over +0 weights and +0 inputs, which
+ * changes no value (only a -0 sum to +0). The order depends on the widths alone, never on the pair's place in a tile, on Bu, on I or on
+ * the launch: a pair has the same bits however the users are chunked and the items sharded, and through sbr_neumf_score_pairs, which
+ * runs the same device function. A lane owns one item of a 64-item tile and keeps its Bt row in registers; a workgroup of four waves
+ * walks a block of 32 users whose A rows and the padded weights sit in LDS (at most 58,384 bytes, under the 64 KiB default limit) and
+ * are read as broadcasts. No atomics: valid in deterministic mode. 1 <= n_layers <= 4, 1 <= H_l <= 64; Bu = 0 or I = 0 returns
+ * without a launch; ceil(I / 64) * ceil(Bu / 32) <= 2^24 workgroups. With accumulate = 1 the caller has laid the GMF term down in out first (the
+ * fp32 GEMM). The three row strides are in elements and at least the row lengths; all offsets are 64-bit.
+ * New (additive to ABI 4). */
+int sbr_neumf_score_all(const float* A, long stride_a, const float* Bt, long stride_b, const float* tail, long tail_len, int n_layers,
+                        int h1, int h2, int h3, int h4, float* out, long stride_o, int Bu, int I, int accumulate, void* stream);
+/* sbr_neumf_score_pairs: the same score for R listed pairs: out[r] = accumulate ? out[r] + s : s with s of the pair (A row u_slot[r],
+ * Bt row i_slot[r]); u_slot, i_slot int32 [R]; out fp32 [R]. A slot outside [0, Bu) or [0, I) reads no row and gives a NaN. R = 0
+ * returns without a launch; at most 2^24 workgroups of 1,024, 512 or 256 pairs (widest layer up to 16, 32, 64). The operands, the order and the limits are those of sbr_neumf_score_all. New (additive to ABI 4). */
+int sbr_neumf_score_pairs(const float* A, long stride_a, int Bu, const float* Bt, long stride_b, int I, const int* u_slot,
+                          const int* i_slot, const float* tail, long tail_len, int n_layers, int h1, int h2, int h3, int h4, float* out,
+                          long R, int accumulate, void* stream);
+
 /* ---- native batch producer (csrc/producer.hip) --------------------------------------------------------------------------------
  * One C++ thread runs the host side of the training step ahead of the launch thread: the default collate of the reference
  * (data/dataloader.py:154-198: bit-exact draws from numpy's legacy MT19937 stream, `v in positives` on the resident interaction

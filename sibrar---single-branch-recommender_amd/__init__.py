@@ -32,6 +32,7 @@ from .directau import DirectAU                                                  
 from .simgcl import SimGCL, XSimGCL                                                         # noqa: F401
 from .ultragcn import UltraGCN                                                              # noqa: F401
 from .simplex import SimpleX                                                                # noqa: F401
+from .neumf import NeuMF                                                                    # noqa: F401
 from .als import AlternatingLeastSquare                                                     # noqa: F401
 from .svd import SVDAlgorithm                                                               # noqa: F401
 from .rbmf import RBMF                                                                      # noqa: F401
@@ -64,12 +65,14 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
 # .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .slim / .p3alpha / .als / .svd / .rbmf / .pop / .rand -> class
-# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae', 'multdae', 'recvae', 'directau', 'simgcl', 'xsimgcl', 'ultragcn' and 'simplex' are this package's own: the reference has
-# no trained graph model, no autoencoder over the interaction row, no model trained on alignment and uniformity and no contrastive one
+# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae', 'multdae', 'recvae', 'directau', 'simgcl', 'xsimgcl', 'ultragcn', 'simplex' and 'neumf' are this package's own: the reference has
+# no trained graph model, no autoencoder over the interaction row, no model trained on alignment and uniformity, no contrastive one and
+# none whose score is a learned non-linear function of the pair
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
               'uiprotomfs': UIProtoMFs, 'acf': ACF, 'ecf': ECF, 'uknn': UserKNN, 'iknn': ItemKNN, 'ifknn': ItemFeatureKNN, 'ease': EASE,
               'slim': SLIM, 'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF,
               'pop': PopularItems, 'rand': RandomItems, 'lightgcn': LightGCN, 'multvae': MultVAE, 'multdae': MultDAE, 'recvae': RecVAE,
-              'directau': DirectAU, 'simgcl': SimGCL, 'xsimgcl': XSimGCL, 'ultragcn': UltraGCN, 'simplex': SimpleX}
+              'directau': DirectAU, 'simgcl': SimGCL, 'xsimgcl': XSimGCL, 'ultragcn': UltraGCN, 'simplex': SimpleX,
+              'neumf': NeuMF}

@@ -362,6 +362,11 @@ def _score_split(alg, eval_loader, evaluator: FullEvaluator, device, scorer, use
         }
         # a tuple item side is scored by the fused kernels only if the model names the one matrix its dot-product score uses (ACF:
         # ``fused_score_transform()[0]`` picks i_repr[0]); every other tuple model scores through its own combine on the fp32 path
+        # a model with a plain item side whose score is NOT the dot product of the two representations (NeuMF with MLP layers: a learned
+        # non-linear function of the pair) says so with ``dot_product_score = False`` and is scored by its own combine on the fp32 path
+        if scorer in fused_routes and not getattr(alg, 'dot_product_score', True):
+            logging.info(f'{scorer} scorer: the score of {getattr(alg, "name", type(alg).__name__)} is not a dot product, using the fp32 path')
+            scorer = 'fp32'
         fused_items = i_repr if plain else None
         if not plain and scorer in fused_routes and hasattr(alg, 'fused_score_transform'):
             pick = alg.fused_score_transform()[0]

@@ -2058,6 +2058,96 @@ class CCLLossFn(Function):
         return d_h, dV, None, None, None
 
 
+# ---- NeuMF (csrc/neumf.hip) -----------------------------------------------------------------------------------------------------------
+NEUMF_MAX_H = 64                  # the widest MLP layer (NEUMF_MAX_H in neumf.hip)
+NEUMF_MAX_LAYERS = 4              # H1 .. H4 (NEUMF_MAX_LAYERS in neumf.hip)
+
+
+def neumf_tail_len(widths) -> int:
+    """floats of the packed tail for the layer widths (H1, ..., HL): W_2 .. W_L, b_2 .. b_L, w_h, c"""
+    return sum(widths[l] * widths[l - 1] + widths[l] for l in range(1, len(widths))) + widths[-1] + 1
+
+
+def neumf_pack_tail(weights, biases, w_h, c) -> torch.Tensor:
+    """One float32 buffer ``[W_2 .. W_L | b_2 .. b_L | w_h | c]`` (each ``W_l`` [H_l, H_{l-1}] row-major) for ``neumf_score_all``: a model
+    builds it once per evaluation, not once per user chunk."""
+    parts = [w.detach().reshape(-1) for w in weights] + [b.detach().reshape(-1) for b in biases] + [w_h.detach().reshape(-1),
+                                                                                                      c.detach().reshape(-1)]
+    return torch.cat([p.to(torch.float32) for p in parts]).contiguous()
+
+
+def _neumf_widths(who, widths, tail):
+    widths = tuple(int(w) for w in widths)
+    if not 1 <= len(widths) <= NEUMF_MAX_LAYERS:
+        raise ValueError(f'{who}: {len(widths)} layer widths outside [1, {NEUMF_MAX_LAYERS}]')
+    if any(not 1 <= w <= NEUMF_MAX_H for w in widths):
+        raise ValueError(f'{who}: layer widths {widths} outside [1, {NEUMF_MAX_H}]')
+    if tail.dim() != 1 or tail.dtype != torch.float32 or not tail.is_contiguous() or tail.numel() != neumf_tail_len(widths):
+        raise ValueError(f'{who}: the packed tail must be a contiguous float32 vector of {neumf_tail_len(widths)} elements for the widths '
+                         f'{widths} (ops.neumf_pack_tail), got {tail.dtype} {tuple(tail.shape)}')
+    return widths + (0,) * (NEUMF_MAX_LAYERS - len(widths))
+
+
+def _neumf_rows(who, name, t, h1):
+    """-> the row stride of the float32 matrix ``t`` [n, h1], whose rows are contiguous and may lie any distance apart"""
+    if t.dim() != 2 or t.dtype != torch.float32 or t.shape[1] != h1:
+        raise ValueError(f'{who}: {name} must be a float32 matrix [n, {h1}], got {t.dtype} {tuple(t.shape)}')
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f'{who}: the rows of {name} must be contiguous and apart by at least their length, got strides {t.stride()}')
+    return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def neumf_score_all(A: torch.Tensor, Bt: torch.Tensor, tail: torch.Tensor, widths, out: Optional[torch.Tensor] = None,
+                    accumulate: bool = False) -> torch.Tensor:
+    """NeuMF's MLP term of every user against every item without the [Bu, I, H1] activation (``sbr_neumf_score_all``), no autograd:
+    ``out[u, i] = <w_h, z_L> + c`` with ``z_1 = relu(A[u] + Bt[i])`` and ``z_l = relu(W_l z_{l-1} + b_l)``. ``A`` [Bu, H1] is the user
+    half of the first layer with its bias, ``Bt`` [I, H1] the item half; ``tail`` is ``neumf_pack_tail`` for ``widths`` = (H1, ..., HL).
+    All three matrices are float32 with contiguous rows at any row stride. ``accumulate``: add onto ``out`` (the GMF term, laid down by
+    the fp32 GEMM) instead of overwriting it. A pair's bits do not depend on how users are chunked or items sharded."""
+    who = 'neumf_score_all'
+    _need_cuda(A, Bt, tail, out)
+    h = _neumf_widths(who, widths, tail)
+    lda, ldb = _neumf_rows(who, 'A', A, h[0]), _neumf_rows(who, 'Bt', Bt, h[0])
+    Bu, I = int(A.shape[0]), int(Bt.shape[0])
+    if out is None:
+        if accumulate:
+            raise ValueError(f'{who}: accumulate=True adds onto out, which is missing')
+        out = torch.empty(Bu, I, device=A.device, dtype=torch.float32)
+    if tuple(out.shape) != (Bu, I):
+        raise ValueError(f'{who}: out must be [{Bu}, {I}], got {tuple(out.shape)}')
+    ldo = _neumf_rows(who, 'out', out, I)
+    if Bu == 0 or I == 0:
+        return out
+    call('sbr_neumf_score_all', ptr(A), lda, ptr(Bt), ldb, ptr(tail), tail.numel(), len(tuple(widths)), *h, ptr(out), ldo, Bu, I,
+         1 if accumulate else 0, stream())
+    return out
+
+
+def neumf_score_pairs(A: torch.Tensor, Bt: torch.Tensor, u_slot: torch.Tensor, i_slot: torch.Tensor, tail: torch.Tensor, widths,
+                      out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """The score of ``neumf_score_all`` for the listed pairs (``sbr_neumf_score_pairs``): ``out[r]`` is the pair (row ``u_slot[r]`` of
+    ``A``, row ``i_slot[r]`` of ``Bt``), bit for bit what ``neumf_score_all`` gives that pair. A slot outside its matrix gives a NaN."""
+    who = 'neumf_score_pairs'
+    _need_cuda(A, Bt, tail, u_slot, i_slot, out)
+    h = _neumf_widths(who, widths, tail)
+    lda, ldb = _neumf_rows(who, 'A', A, h[0]), _neumf_rows(who, 'Bt', Bt, h[0])
+    if u_slot.dim() != 1 or u_slot.shape != i_slot.shape:
+        raise ValueError(f'{who}: u_slot and i_slot must be vectors of one length, got {tuple(u_slot.shape)} and {tuple(i_slot.shape)}')
+    R = int(u_slot.numel())
+    if out is None:
+        if accumulate:
+            raise ValueError(f'{who}: accumulate=True adds onto out, which is missing')
+        out = torch.empty(R, device=A.device, dtype=torch.float32)
+    if tuple(out.shape) != (R,) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f'{who}: out must be a contiguous float32 vector [{R}], got {out.dtype} {tuple(out.shape)}')
+    if R == 0:
+        return out
+    u32, i32 = u_slot.to(torch.int32).contiguous(), i_slot.to(torch.int32).contiguous()
+    call('sbr_neumf_score_pairs', ptr(A), lda, int(A.shape[0]), ptr(Bt), ldb, int(Bt.shape[0]), ptr(u32), ptr(i32), ptr(tail),
+         tail.numel(), len(tuple(widths)), *h, ptr(out), R, 1 if accumulate else 0, stream())
+    return out
+
+
 # ---- implicit-feedback ALS (csrc/als.hip) -------------------------------------------------------------------------------------------
 def als_gram(Y: torch.Tensor, reg: float) -> torch.Tensor:
     """``Y^T Y + reg I`` as float32 [f, f] for the factor matrix ``Y`` [n, f], f <= 128: the part of the ALS system every row of a
