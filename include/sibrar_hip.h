@@ -853,6 +853,57 @@ int sbr_graph_propagate_noise_f32(const long* u_indptr, const int* u_indices, co
                                   int n_items, long r0, long r1, const float* x, float* y, float* sum, float sum_scale, int D, float eps,
                                   unsigned long seed, unsigned long stream_id, void* stream);
 
+/* ---- NGCF's layer on 0/1 data (csrc/ngcf.hip) ------------------------------------------------------------------------------------------
+ * One layer of NGCF (Wang et al., SIGIR 2019) in one launch: the gather of sbr_graph_propagate_f32, the two products, LeakyReLU, message
+ * dropout and the row normalisation. Graph operands, their preconditions and the row range as for sbr_graph_propagate_f32. x [n, Din]
+ * (n = n_users + n_items) and h [n, Dout] are contiguous fp32 tables (row stride = width); W1 and W2 are [Din, Dout] row-major, bias
+ * [Dout]; out is a column slice of a wider table: element (r, j) is out[r * out_ld + j], out_ld >= Dout, and nothing outside the Dout
+ * columns of the rows of [r0, r1) is written. 1 <= Din, Dout <= 128. For every row r of [r0, r1):
+ *   s[k] = y[r][k] of sbr_graph_propagate_f32 on x, bit for bit: the same scales, the same fmaf chain in ascending CSR order, the same
+ *     final multiplication;
+ *   a[k] = s[k] + x[r][k]: one addition;  b[k] = s[k] * x[r][k]: one multiplication; nothing fused;
+ *   z[j]: acc starts at +0.0f, takes acc = fmaf(a[k], W1[k][j], acc) over k = 0 .. Din - 1 ascending, then acc = fmaf(b[k], W2[k][j], acc)
+ *     over k ascending, then z[j] = acc + bias[j]: one addition. The order is a function of (Din, Dout) alone;
+ *   h[j] = z[j] > 0 ? z[j] : slope * z[j];
+ *   if p > 0: u = Philox4x32-10 keyed as in sbr_graph_propagate_noise_f32 (key = the halves of seed, counter = (r, j / 4, low half of
+ *     stream_id, high half of stream_id), word j % 4, mapped to (x >> 8) * 2^-24); where u >= p, h[j] = h[j] * inv_keep with inv_keep =
+ *     1.0f / (1.0f - p) computed once on the host in fp32; elsewhere h[j] = +0.0f. With p == 0 no Philox call is made and h passes;
+ *   q = the sum of h[j]^2 in this order, the same for every Dout: partial sum l (0 <= l < 16) starts at +0.0f and takes t = t + h[j] *
+ *     h[j] (one multiplication, then one addition, not fused) over the columns j with (j / 4) % 16 == l in ascending order; the partial
+ *     sums combine by an xor butterfly over the offsets 1, 2, 4, 8: every t_l becomes t_l + t_(l xor o), all of a step at once;
+ *   nrm = fmaxf(sqrtf(q), 1e-12f): one correctly rounded square root;  out[j] = h[j] / nrm: one correctly rounded division.
+ * h (after the dropout) is the next layer's x. A row whose h is all zeros (every element dropped, or z == 0 throughout) writes +0.0f
+ * to h and to out. The mask is a pure function of (seed, stream_id, r, j) and every bit of h and out a function of the row alone: not
+ * of r0, r1, the launch geometry, the alignment of the tables or the run. Every element has one owner: no atomics, valid in
+ * deterministic mode. Refused before any launch: what sbr_graph_propagate_f32 refuses, a width outside [1, 128], out_ld < Dout, a
+ * slope outside (0, 1] or not finite, p outside [0, 1), x, W1, W2 or bias overlapping h or out, h overlapping out, and a NULL
+ * u_indptr, i_indptr, x, W1, W2, bias, h or out. An empty range returns at once. Nothing is saved for the backward pass: it takes x and
+ * h and recomputes s, the mask and nrm. New (additive to ABI 4). */
+int sbr_ngcf_layer_fwd(const long* u_indptr, const int* u_indices, const long* i_indptr, const int* i_indices, int n_users, int n_items,
+                       long r0, long r1, const float* x, int Din, const float* W1, const float* W2, const float* bias, int Dout, float slope,
+                       float p, unsigned long seed, unsigned long stream_id, float* h, float* out, long out_ld, void* stream);
+/* Bytes of workspace sbr_ngcf_layer_bwd needs for a range of n_rows rows (0 for an empty range or widths outside the cap). */
+long sbr_ngcf_layer_bwd_workspace(long n_rows, int Din, int Dout);
+/* The backward pass of sbr_ngcf_layer_fwd over the rows of [r0, r1), from the same graph, x, W1, W2, slope, p, seed and stream_id and
+ * the h the forward pass wrote. g_out is the gradient with respect to out (strided by out_ld like out), g_h the gradient with
+ * respect to h that the next layer sends back (NULL: none, the last layer). With nrm and the mask recomputed as above (the same bits),
+ * o = h / nrm and f = 1 where sqrtf(q) >= 1e-12f, else 0:
+ *   dh[j] = (g_out[j] - f * o[j] * <g_out, o>) / nrm + g_h[j];   dz[j] = dh[j] * (kept ? inv_keep : 0) * (h[j] > 0 ? 1 : slope);
+ *   da = dz W1^T, db = dz W2^T;   ds[r][k] = da[k] + db[k] * x[r][k];   dx_direct[r][k] = da[k] + db[k] * s[k]
+ * (ds and dx_direct contiguous [n, Din]; only the rows of the range are written). The gradient of x is dx_direct + A^ ds: the caller
+ * runs sbr_graph_propagate_f32 on ds with sum = dx_direct and sum_scale = 1 (A^ is symmetric). dW1 = a^T dz, dW2 = b^T dz [Din, Dout]
+ * and dbias = colsum(dz) [Dout] over the rows of the range are OVERWRITTEN: a workgroup adds its row tiles into a partial of its own
+ * in the workspace, in ascending row order, and the partials are added in workgroup order in double and rounded once. No atomics: the
+ * same bits on every run (they depend on the number of rows of the range), valid in deterministic mode. workspace: at least
+ * sbr_ngcf_layer_bwd_workspace(r1 - r0, Din, Dout) bytes. Refused before any launch: what the forward entry refuses, any written table
+ * (ds, dx_direct, dW1, dW2, dbias, the workspace) overlapping any other operand, a NULL operand other than g_h, a workspace that is
+ * too small. An empty range returns at once and writes nothing. New (additive to ABI 4). */
+int sbr_ngcf_layer_bwd(const long* u_indptr, const int* u_indices, const long* i_indptr, const int* i_indices, int n_users, int n_items,
+                       long r0, long r1, const float* x, int Din, const float* W1, const float* W2, int Dout, float slope, float p,
+                       unsigned long seed, unsigned long stream_id, const float* h, const float* g_out, long out_ld, const float* g_h,
+                       float* ds, float* dx_direct, float* dW1, float* dW2, float* dbias, void* workspace, long workspace_bytes,
+                       void* stream);
+
 /* ---- the multinomial log-likelihood of Mult-VAE / Mult-DAE on 0/1 data (csrc/multinomial.hip) ----------------------------------------
  * The loss of Liang et al. (WWW 2018, equation 2) for a logit matrix [B, n_items] against the users' rows of a users x items binary
  * CSR matrix (indptr int64, indices int32 ascending and unique within a row and below n_items), with its gradient, in one launch.

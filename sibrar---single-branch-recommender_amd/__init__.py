@@ -33,6 +33,7 @@ from .simgcl import SimGCL, XSimGCL                                             
 from .ultragcn import UltraGCN                                                              # noqa: F401
 from .simplex import SimpleX                                                                # noqa: F401
 from .neumf import NeuMF                                                                    # noqa: F401
+from .ngcf import NGCF                                                                      # noqa: F401
 from .als import AlternatingLeastSquare                                                     # noqa: F401
 from .svd import SVDAlgorithm                                                               # noqa: F401
 from .rbmf import RBMF                                                                      # noqa: F401
@@ -65,9 +66,10 @@ def reproducible(seed: int, deterministic: bool = True) -> None:
 
 # the reference's registry: AlgorithmsEnum.sbnet / .sgdbias / .mf / .dmf / .uprotomf / .iprotomf / .uiprotomf / .uprotomfs / .iprotomfs /
 # .uiprotomfs / .acf / .ecf / .uknn / .iknn / .ifknn / .ease / .slim / .p3alpha / .als / .svd / .rbmf / .pop / .rand -> class
-# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae', 'multdae', 'recvae', 'directau', 'simgcl', 'xsimgcl', 'ultragcn', 'simplex' and 'neumf' are this package's own: the reference has
+# (algorithms/algorithms_utils.py); 'lightgcn', 'multvae', 'multdae', 'recvae', 'directau', 'simgcl', 'xsimgcl', 'ultragcn', 'simplex', 'neumf' and 'ngcf' are this package's own: the reference has
 # no trained graph model, no autoencoder over the interaction row, no model trained on alignment and uniformity, no contrastive one and
-# none whose score is a learned non-linear function of the pair
+# none whose score is a learned non-linear function of the pair ('ngcf' is the graph model with weights in its layers that 'lightgcn'
+# simplifies)
 ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixFactorization,
               'ifeatmf': ItemFeatureMatrixFactorization, 'ufeatmf': UserFeatureMatrixFactorization, 'dropoutnet': DropoutNet, 'dmf': DeepMatrixFactorization,
               'uprotomf': UProtoMF, 'iprotomf': IProtoMF, 'uiprotomf': UIProtoMF, 'uprotomfs': UProtoMFs, 'iprotomfs': IProtoMFs,
@@ -75,4 +77,4 @@ ALGORITHMS = {'sbnet': SingleBranchNet, 'sgdbias': SGDBaseline, 'mf': SGDMatrixF
               'slim': SLIM, 'p3alpha': P3alpha, 'als': AlternatingLeastSquare, 'svd': SVDAlgorithm, 'rbmf': RBMF,
               'pop': PopularItems, 'rand': RandomItems, 'lightgcn': LightGCN, 'multvae': MultVAE, 'multdae': MultDAE, 'recvae': RecVAE,
               'directau': DirectAU, 'simgcl': SimGCL, 'xsimgcl': XSimGCL, 'ultragcn': UltraGCN, 'simplex': SimpleX,
-              'neumf': NeuMF}
+              'neumf': NeuMF, 'ngcf': NGCF}

@@ -1604,6 +1604,164 @@ class NoisyPropagateFn(Function):
         return (None, graph_propagate(ctx.csr, t)) + (None,) * 6
 
 
+# ---- NGCF's layer (csrc/ngcf.hip) -------------------------------------------------------------------------------------------------------
+NGCF_MAX_WIDTH = 128
+
+
+def _ngcf_slice(who, name, t, n, d):
+    """a float32 [n, d] column slice of a wider row-major table (or a contiguous table) -> its leading dimension"""
+    if t.dtype != torch.float32 or tuple(t.shape) != (n, d) or (d > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < d):
+        raise ValueError(f'{who}: {name} must be float32 {[n, d]} with unit column stride (a column slice of a row-major table), got '
+                         f'{t.dtype} {tuple(t.shape)} strides {t.stride()}')
+    return max(int(t.stride(0)), d) if n > 1 else d
+
+
+def _ngcf_operands(who, csr, x, W1, W2, slope, p, seed, stream_id):
+    if csr.data is not None:
+        raise ValueError(f'{who}: the normalised adjacency is stated for 0/1 data only (degrees are entry counts); this matrix has values')
+    n_users, n_items = csr.shape
+    n = n_users + n_items
+    if x.dim() != 2 or W1.dim() != 2:
+        raise ValueError(f'{who}: x must be a table [{n}, Din] and W1 a matrix [Din, Dout], got shapes {tuple(x.shape)} and {tuple(W1.shape)}')
+    din, dout = int(W1.shape[0]), int(W1.shape[1])
+    if not (1 <= din <= NGCF_MAX_WIDTH and 1 <= dout <= NGCF_MAX_WIDTH):
+        raise ValueError(f'{who}: widths Din={din}, Dout={dout} outside [1, {NGCF_MAX_WIDTH}]')
+    _graph_table(who, 'x', x, (n, din))
+    _graph_table(who, 'W1', W1, (din, dout))
+    _graph_table(who, 'W2', W2, (din, dout))
+    for name, v in (('seed', seed), ('stream_id', stream_id)):
+        if int(v) != v or not 0 <= v < 1 << 64:
+            raise ValueError(f'{who}: {name}={v!r} must be an integer in [0, 2^64)')
+    t_indptr, t_indices, _ = csr.transposed()
+    graph = (ptr(csr.indptr), ptr(csr.indices), ptr(t_indptr), ptr(t_indices), n_users, n_items)
+    return graph, n, din, dout, (float(slope), float(p), int(seed), int(stream_id))
+
+
+def ngcf_layer(csr, x: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor, bias: torch.Tensor, slope: float = 0.2, p: float = 0.0,
+               seed: int = 0, stream_id: int = 0, h=None, out=None, rows=None):
+    """One NGCF layer over the joint row space of a binary resident ``features.DeviceCSR`` in one launch (``sbr_ngcf_layer_fwd``):
+    ``s = A^ x``, ``z = (s + x) W1 + (s * x) W2 + bias``, ``h = dropout_p(LeakyReLU_slope(z))``, ``out = h / max(|h|, 1e-12)`` row-wise
+    -> ``(h, out)``. ``x`` [n, Din], ``W1`` / ``W2`` [Din, Dout] and ``bias`` [Dout] are contiguous float32, widths up to 128; ``h`` is a
+    contiguous [n, Dout] table to write into, ``out`` may be a column slice of a wider row-major table (the concatenated representation:
+    nothing outside the slice is written). The dropout mask is Philox4x32-10 of ``(seed, stream_id, row, column)``; ``p = 0`` draws
+    nothing. Fixed order, no atomics: the same bits on every run and for every split of the rows (``rows=(r0, r1)``; rows outside
+    keep what they hold, those of a new result are zero). No CPU fallback."""
+    who = 'ngcf_layer'
+    _need_cuda(csr.indptr, x, W1, W2, bias, h, out)
+    graph, n, din, dout, tail = _ngcf_operands(who, csr, x, W1, W2, slope, p, seed, stream_id)
+    _graph_table(who, 'bias', bias, (dout,))
+    r0, r1, whole = _row_range(rows, n)
+    make = torch.empty if whole else torch.zeros
+    if h is None:
+        h = make((n, dout), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = make((n, dout), device=x.device, dtype=torch.float32)
+    _graph_table(who, 'h', h, (n, dout))
+    ld = _ngcf_slice(who, 'out', out, n, dout)
+    call('sbr_ngcf_layer_fwd', *graph, r0, r1, ptr(x), din, ptr(W1), ptr(W2), ptr(bias), dout, *tail, ptr(h), ptr(out), ld, stream())
+    return h, out
+
+
+def ngcf_layer_bwd(csr, x: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor, h: torch.Tensor, g_out: torch.Tensor, g_h=None,
+                   slope: float = 0.2, p: float = 0.0, seed: int = 0, stream_id: int = 0, rows=None):
+    """The backward pass of ``ngcf_layer`` (``sbr_ngcf_layer_bwd``) from the layer's input ``x``, its output ``h`` and the gradients
+    ``g_out`` (of ``out``; may be a column slice) and ``g_h`` (of ``h``, from the next layer; None for the last)
+    -> ``(ds, dx_direct, dW1, dW2, dbias)``: the gradient of ``x`` is ``dx_direct + A^ ds`` (``graph_propagate(csr, ds, sum=dx_direct)``).
+    The gather, the mask and the norm are recomputed. The weight gradients are per-workgroup partials folded in workgroup order: no
+    atomics, the same bits on every run."""
+    who = 'ngcf_layer_bwd'
+    _need_cuda(csr.indptr, x, W1, W2, h, g_out, g_h)
+    graph, n, din, dout, tail = _ngcf_operands(who, csr, x, W1, W2, slope, p, seed, stream_id)
+    _graph_table(who, 'h', h, (n, dout))
+    if g_h is not None:
+        _graph_table(who, 'g_h', g_h, (n, dout))
+    ld = _ngcf_slice(who, 'g_out', g_out, n, dout)
+    r0, r1, whole = _row_range(rows, n)
+    make = torch.empty if whole else torch.zeros
+    ds, dxd = (make((n, din), device=x.device, dtype=torch.float32) for _ in range(2))
+    dW1, dW2 = (torch.zeros((din, dout), device=x.device, dtype=torch.float32) for _ in range(2))
+    dbias = torch.zeros(dout, device=x.device, dtype=torch.float32)
+    ws, ws_bytes = _entry_ws(x.device, 'sbr_ngcf_layer_bwd', r1 - r0, din, dout)
+    call('sbr_ngcf_layer_bwd', *graph, r0, r1, ptr(x), din, ptr(W1), ptr(W2), dout, *tail, ptr(h), ptr(g_out), ld, ptr(g_h), ptr(ds), ptr(dxd),
+         ptr(dW1), ptr(dW2), ptr(dbias), ws, ws_bytes, stream())
+    return ds, dxd, dW1, dW2, dbias
+
+
+def _ngcf_input_grad(csr, x, W1, W2, h, g_out, g_h, tail):
+    """-> (dx, dW1, dW2, dbias) of one layer: the fused backward launch, then the graph part of dx through the propagation's ``sum``"""
+    ds, dxd, dW1, dW2, dbias = ngcf_layer_bwd(csr, x, W1, W2, h, g_out, g_h, *tail)
+    graph_propagate(csr, ds, out=_graph_scratch(0, ds), sum=dxd, sum_scale=1.0)
+    return dxd, dW1, dW2, dbias
+
+
+class NGCFLayerFn(Function):
+    """One NGCF layer on the autograd tape: ``(h, out) = NGCFLayerFn.apply(csr, x, W1, W2, bias, slope, p, seed, stream_id)`` as
+    ``ngcf_layer`` computes them. Backward: one ``sbr_ngcf_layer_bwd`` launch and one ``sbr_graph_propagate_f32`` (A^ is symmetric).
+    Fixed order, no atomics: valid in deterministic mode."""
+
+    @staticmethod
+    def forward(ctx, csr, x, W1, W2, bias, slope: float = 0.2, p: float = 0.0, seed: int = 0, stream_id: int = 0):
+        x, W1, W2, bias = _f32c(x), _f32c(W1), _f32c(W2), _f32c(bias)
+        h, out = ngcf_layer(csr, x, W1, W2, bias, slope, p, seed, stream_id)
+        ctx.csr, ctx.tail = csr, (float(slope), float(p), int(seed), int(stream_id))
+        ctx.save_for_backward(x, W1, W2, h)
+        return h, out
+
+    @staticmethod
+    def backward(ctx, g_h, g_out):
+        x, W1, W2, h = ctx.saved_tensors
+        dx, dW1, dW2, dbias = _ngcf_input_grad(ctx.csr, x, W1, W2, h, _f32c(g_out), _f32c(g_h), ctx.tail)
+        return (None, dx, dW1, dW2, dbias) + (None,) * 4
+
+
+class NGCFPropagateFn(Function):
+    """NGCF's layer stack: ``table = NGCFPropagateFn.apply(csr, e0, slope, p, seed, W1_1, W2_1, bias_1, ..., W1_L, W2_L, bias_L)`` is
+    ``[e0 | normalize(E_1) | ... | normalize(E_L)]`` [n, D0 + sum of the layer widths] with ``E_l`` the ``h`` of ``ngcf_layer`` on
+    ``E_(l-1)``: L launches, every layer writes its normalised rows straight into its column slice. Layer l (1-based) draws its
+    dropout from ``stream_id = l``. Backward: per layer, from the last, one ``sbr_ngcf_layer_bwd`` on the slice of the incoming
+    gradient and the gradient the next layer sent back, and one ``sbr_graph_propagate_f32``. No layer returns ``e0`` and launches
+    nothing."""
+
+    @staticmethod
+    def forward(ctx, csr, e0, slope, p, seed, *params):
+        if len(params) % 3:
+            raise ValueError('NGCFPropagateFn: the parameters come as (W1, W2, bias) per layer')
+        n_layers = len(params) // 3
+        ctx.csr, ctx.n_layers = csr, n_layers
+        if n_layers == 0:
+            return e0.view_as(e0)
+        _need_cuda(e0)
+        x = _f32c(e0)
+        params = [_f32c(t) for t in params]
+        widths = [int(x.shape[1])] + [int(params[3 * k].shape[1]) for k in range(n_layers)]
+        table = torch.empty((x.shape[0], sum(widths)), device=x.device, dtype=torch.float32)
+        table[:, :widths[0]] = x
+        saved, off = [x], widths[0]
+        for k in range(n_layers):
+            W1, W2, bias = params[3 * k:3 * k + 3]
+            x, _ = ngcf_layer(csr, x, W1, W2, bias, slope, p, seed, k + 1, out=table[:, off:off + widths[k + 1]])
+            saved.append(x)
+            off += widths[k + 1]
+        ctx.tail, ctx.widths = (float(slope), float(p), int(seed)), widths
+        ctx.save_for_backward(*saved, *params)
+        return table
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.n_layers == 0:
+            return (None, g) + (None,) * 3
+        L, widths = ctx.n_layers, ctx.widths
+        xs, params = ctx.saved_tensors[:L + 1], ctx.saved_tensors[L + 1:]
+        g = _f32c(g)
+        grads, dx, off = [None] * (3 * L), None, sum(widths)
+        for k in range(L - 1, -1, -1):
+            off -= widths[k + 1]
+            W1, W2 = params[3 * k], params[3 * k + 1]
+            dx, dW1, dW2, dbias = _ngcf_input_grad(ctx.csr, xs[k], W1, W2, xs[k + 1], g[:, off:off + widths[k + 1]], dx, ctx.tail + (k + 1,))
+            grads[3 * k:3 * k + 3] = dW1, dW2, dbias
+        return (None, g[:, :widths[0]] + dx, None, None, None, *grads)
+
+
 # ---- the multinomial log-likelihood of Mult-VAE / Mult-DAE (csrc/multinomial.hip) ------------------------------------------------------
 def _multinomial_nll(who, csr, rows, logits, grad_scale, inplace):
     """the launch behind ``multinomial_nll`` and ``MultinomialNLLFn``; nothing here synchronises"""
